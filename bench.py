@@ -25,6 +25,10 @@ decoder levels compute only the outputs that the tile's useful centre (what the 
 the loop with whole-tile layers instead, and the default run reports that rate and the difference of the two canvases under
 `whole_tiles`.
 
+`--dump-outputs DIR` writes, right after the timed steps, the canvas the last timed step stitched (DIR/canvas.npy; a fixed seeded
+sample of it above 64 MB).  The frames and weights are seeded, so the same arguments give the same inputs on every run, and the
+dumps of two builds compare value for value.
+
 One JSON line on rank 0:
   roofline      the dominant kernel by time (conv_w2d, the fused 1-D Winograd 3x3 kernel on the fp32 path): MFMA-EXECUTED
                 FLOP / HIP-event time on the launch stream / MFMA peak (<= 1 by construction); the algorithmic
@@ -117,7 +121,13 @@ def parse():
     ap.add_argument("--whole-tiles", action="store_true",
                     help="compute every layer on the whole tile, as UtNet.forward does (ND_FLAG_FULL_TILES); default: the last decoder "
                          "levels compute only what the useful centre [pad, cs - pad) of a tile depends on -- same canvas")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the stitched canvas of the last timed step (rank 0's last frame) as DIR/canvas.npy, "
+                         "float32; a canvas above the size cap is written as a fixed seeded sample of its values (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ rank launcher
@@ -400,6 +410,38 @@ def canvas_parity(net, img, frame_shape, cs, ucs, ol, batch, ids, outs):
             "launches": len(by_launch)}
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+
+DUMP_MAX_BYTES = 64_000_000     # all arrays of one dump together, .npy headers included
+DUMP_NPY_HEADER = 128           # bytes of a .npy header for the shapes written here
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, arrays):
+    """Write every array of `arrays` (name -> torch tensor or numpy array) as out_dir/<name>.npy, float64 kept, anything else as
+    float32.  An array above its share of DUMP_MAX_BYTES is written as a sample of its flattened values: the sorted distinct
+    indices among numpy default_rng(DUMP_SEED).integers(0, size, share / itemsize), the same indices for the same shape on every
+    run, so that two builds' dumps compare value for value.  Returns a description of what was written."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(arrays)) - DUMP_NPY_HEADER
+    desc = {}
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        row = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if a.nbytes > share:
+            draws = share // a.itemsize
+            row["sample"] = f"values at the sorted distinct flat indices of numpy default_rng({DUMP_SEED}).integers(0, {a.size}, {draws})"
+            a = a.reshape(-1)[np.unique(np.random.default_rng(DUMP_SEED).integers(0, a.size, draws))]
+        row["values"] = int(a.size)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        desc[name] = row
+    return desc
+
+
 # ------------------------------------------------------------------------------------------------ single-GPU legs
 
 def time_frames(net, img, canvas, cs, ucs, ol, batch, steps, warmup):
@@ -551,13 +593,14 @@ def main():
                 compute(pool[k % len(pool)], canvas, 0, total)
 
     stream = None
+    last_canvas = [canvas]      # rank 0: the stitched canvas of the last frame through run_steps
     if mode == "tile-stream":
         stream = ndist.ShardedFrameStream(compute, geo, dev)
 
         def run_steps(n):
             src = (pool[k % len(pool)] for k in range(n)) if rank == 0 else None
-            for _k, _cv in stream.run(src, n):
-                pass
+            for _k, cv in stream.run(src, n):
+                last_canvas[0] = cv
         frames_per_step = 1
     elif mode == "single":
         def run_steps(n):
@@ -582,6 +625,12 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     log(f"timed {args.steps} steps in {dt:.3f} s")
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before any later leg reuses the canvas (the ring slot of the tile stream, the whole-tile leg's canvas)
+        dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, {"canvas": last_canvas[0]}),
+                  "what": "the stitched [3, H, W] canvas of the last timed step (of rank 0's last frame when a step holds several)"}
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
 
     def max_over_ranks(x):
         if world == 1:
@@ -674,6 +723,8 @@ def main():
         },
     }
     out.update(extra)
+    if dumped:
+        out["dump_outputs"] = dumped
     if bcast:
         out["weight_broadcast"] = bcast
 

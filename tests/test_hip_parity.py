@@ -1680,7 +1680,7 @@ def test_pipelined_frame_stream_with_hip_compute(dev, world):
             assert np.abs(got[k] - ref).max() <= 1e-6 and (got[k] == ref).mean() > 0.7
 
 
-def test_bench_n2_rehearsal_line(dev):
+def test_bench_n2_rehearsal_line(dev, tmp_path):
     """`bench.py --gpus 2` end to end on the one-GPU box (ND_BENCH_REHEARSAL=1: both ranks on GPU 0, messages over gloo): the launcher
     spawns the ranks, the default N > 1 mode is the pipelined tile-shard stream, the parameters are broadcast from rank 0, rank 0
     prints ONE JSON line that names the partition and carries the pipeline / replicas keys."""
@@ -1689,8 +1689,8 @@ def test_bench_n2_rehearsal_line(dev):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, ND_BENCH_REHEARSAL="1")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--width", "1500",
-                        "--height", "1100", "--funit", "16", "--batch", "32", "--no-roofline"], env=env, cwd=root, capture_output=True,
-                       text=True, timeout=600)
+                        "--height", "1100", "--funit", "16", "--batch", "32", "--no-roofline", "--dump-outputs", str(tmp_path / "dump")],
+                       env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -1700,6 +1700,38 @@ def test_bench_n2_rehearsal_line(dev):
     assert d["pipeline"]["compute_only_ms_largest_shard"] > 0 and 0 < d["pipeline"]["exchange_hidden_frac"] <= 1
     assert d["frame_shard"]["frames_per_step"] == 2 and "REPLICAS" in d["frame_shard"]["note"]
     assert d["weight_broadcast"]["bytes"] > 0 and "REHEARSAL" in d["data"]
+    # --dump-outputs on the tile stream: rank 0's canvas of the last timed frame, the third of the cycled frames (seed 26); the
+    # shards' canvas bands are added on rank 0, so the sums differ from the single-GPU loop's in the last bits
+    from nind_denoise_amd import pipeline
+    from nind_denoise_amd.networks.UtNet import UtNet
+    got = np.load(tmp_path / "dump" / "canvas.npy")
+    net = UtNet(funit=16)
+    net.load_state_dict(synth.make_utnet_state_dict(funit=16, seed=123))
+    net = net.eval().to(dev)
+    want = pipeline.denoise_frame(net, torch.from_numpy(synth.make_frame(1500, 1100, seed=26)).to(dev), 264, 200, 64, batch=32).cpu().numpy()
+    assert got.shape == want.shape and np.abs(got - want).max() <= 1e-4
+
+
+def test_bench_dump_outputs_is_the_timed_canvas(dev, tmp_path):
+    """`bench.py --dump-outputs DIR` on one GPU: DIR/canvas.npy (whole below the size cap) is the canvas of the last timed step, bit for
+    bit what pipeline.denoise_frame gives for the same seeded frame and weights in this process; the line reports the steps run."""
+    import subprocess
+    import sys
+    from nind_denoise_amd import pipeline
+    from nind_denoise_amd.networks.UtNet import UtNet
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--width", "1500",
+                        "--height", "1100", "--funit", "16", "--batch", "32", "--no-roofline", "--no-host-leg", "--no-whole-leg",
+                        "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "dump")], cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and "sample" not in d["dump_outputs"]["arrays"]["canvas"]
+    got = np.load(tmp_path / "dump" / "canvas.npy")
+    net = UtNet(funit=16)
+    net.load_state_dict(synth.make_utnet_state_dict(funit=16, seed=123))
+    net = net.eval().to(dev)
+    want = pipeline.denoise_frame(net, torch.from_numpy(synth.make_frame(1500, 1100, seed=24)).to(dev), 264, 200, 64, batch=32)
+    assert got.dtype == np.float32 and np.array_equal(got, want.cpu().numpy())
 
 
 # ---------------------------------------------------------------------------- fixtures executed by the reference itself

@@ -329,3 +329,19 @@ def test_thin_client_protocol(tmp_path):
     r = subprocess.run([sys.executable, "-m", "nind_denoise_amd.denoise_image", "-i", "a.tif"], env=dict(env, NIND_DENOISE_SERVER=str(tmp_path / "none.sock")),
                        cwd=tmp_path, capture_output=True, text=True, timeout=60)
     assert r.returncode == 111 and "no worker at" in r.stderr
+
+
+def test_bench_dump_outputs_cap_and_sample(tmp_path):
+    """bench.py --dump-outputs: arrays within the cap are written whole as float32 (float64 kept); a bench-sized canvas becomes a
+    sample under 64 MB whose indices depend only on the shape, so two dumps of the same canvas are identical."""
+    import bench
+    small = torch.arange(3 * 10 * 12, dtype=torch.float32).reshape(3, 10, 12)
+    d = bench.dump_outputs(str(tmp_path / "s"), {"canvas": small, "f64": np.linspace(0, 1, 7), "f16": np.ones(4, np.float16)})
+    assert np.array_equal(np.load(tmp_path / "s" / "canvas.npy"), small.numpy()) and d["canvas"]["values"] == small.numel()
+    assert np.load(tmp_path / "s" / "f64.npy").dtype == np.float64 and np.load(tmp_path / "s" / "f16.npy").dtype == np.float32
+    big = np.random.default_rng(3).random((3, 4000, 6000), dtype=np.float32)
+    for sub in ("a", "b"):
+        d = bench.dump_outputs(str(tmp_path / sub), {"canvas": torch.from_numpy(big)})
+        assert os.path.getsize(tmp_path / sub / "canvas.npy") <= 64e6 and "sample" in d["canvas"]
+    a, b = np.load(tmp_path / "a" / "canvas.npy"), np.load(tmp_path / "b" / "canvas.npy")
+    assert a.dtype == np.float32 and a.size == d["canvas"]["values"] > big.size // 8 and np.array_equal(a, b)
