@@ -70,7 +70,7 @@ typedef enum nd_flags {
                                  the network output before the canvas +=) -- same canvas, 19 % less work at cs 264 / ucs 200    */
 } nd_flags;
 
-int nd_version(void);   /* 103 = this header */
+int nd_version(void);   /* 104 = this header */
 const char *nd_last_error(void);
 
 /* ---------------------------------------------------------------- tile geometry (host, pure integer)
@@ -230,13 +230,30 @@ int nd_utnet_train_step(int funit, int flags, const float *params, float *grads,
  * nd_utnet_train_backward = the whole backward from gy = d loss / d output [batch,3,cs,cs] into the flat gradient buffer.
  * act: ND_ACT_PRELU | ND_ACT_ELU | ND_ACT_HARDSWISH (networks/UtNet.py:17-26; tensors of the parameter layout that the
  * activation does not have -- PReLU slopes -- are ignored and their gradients left untouched).  `workspace` and `blobs`
- * carry the forward's state to the backward call: nothing else may use them in between.  The gradient of the input image
- * is not produced. */
+ * carry the forward's state to the backward call: nothing else may use them in between.  These square-crop forms produce
+ * the parameter gradients only. */
 int nd_utnet_train_forward(int funit, int act, int flags, const float *params, void *blobs, const float *x_nchw, float *y_out_nchw,
                            int batch, int cs, void *workspace, size_t workspace_bytes, void *stream);
 int nd_utnet_train_backward(int funit, int act, int flags, const float *params, float *grads, void *blobs, const float *gy_nchw,
                             int batch, int cs, void *workspace, size_t workspace_bytes, void *stream, void *const *bucket_events,
                             int n_events);
+/* The same on h x w crops (each side 16k+56; with h = w = cs the square entry points above are these, bit for bit).
+ * nd_utnet_train_backward_hw: grads (nullable) = the flat parameter gradients -- null skips every parameter-gradient launch
+ * and bucket event (a frozen network costs forward + data gradients only); dx_nchw (nullable) = d loss / d x [batch,3,h,w],
+ * the first layer's data gradient through the ReflectionPad2d(2) of the input; at least one of the two.
+ * nd_utnet_train_step_hw: nd_utnet_train_step_ev on h x w crops, bucket_events nullable; loss_cs > 0 crops an
+ * loss_cs x loss_cs square at y0 = (h - loss_cs) / 2, x0 = (w - loss_cs) / 2 (pt_ops.pt_crop_batch), 0 = the whole output. */
+size_t nd_utnet_train_workspace_bytes_hw(int funit, int h, int w, int batch);
+int nd_utnet_train_workspace_init_hw(void *workspace, size_t workspace_bytes, int funit, int h, int w, int batch, void *stream);
+int nd_utnet_train_forward_hw(int funit, int act, int flags, const float *params, void *blobs, const float *x_nchw,
+                              float *y_out_nchw, int batch, int h, int w, void *workspace, size_t workspace_bytes, void *stream);
+int nd_utnet_train_backward_hw(int funit, int act, int flags, const float *params, float *grads, void *blobs, const float *gy_nchw,
+                               float *dx_nchw, int batch, int h, int w, void *workspace, size_t workspace_bytes, void *stream,
+                               void *const *bucket_events, int n_events);
+int nd_utnet_train_step_hw(int funit, int flags, const float *params, float *grads, void *blobs, const float *x_nchw,
+                           const float *target_nchw, float *y_out_nchw, float w_l1, float w_mse, float w_ssim, float w_msssim,
+                           float *loss_out, int batch, int h, int w, int loss_cs, void *workspace, size_t workspace_bytes,
+                           void *stream, void *const *bucket_events, int n_events);
 /* Data-parallel training that overlaps the gradient reduction with the backward pass (BASELINE configs[4]): the flat gradient
  * buffer is cut into nd_utnet_grad_buckets = 9 contiguous ranges, one per decoder / encoder level, numbered in the order the
  * backward pass completes them; bucket_events[k] (hipEvent_t, nullable array) is recorded on `stream` when bucket k is final,

@@ -94,6 +94,15 @@ _SIGNATURES = {
     "nd_utnet_train_step_ev": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                        c_float, c_float, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, POINTER(c_void_p),
                                        c_int]),
+    "nd_utnet_train_workspace_bytes_hw": (c_size_t, [c_int] * 4),
+    "nd_utnet_train_workspace_init_hw": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p]),
+    "nd_utnet_train_forward_hw": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                          c_size_t, c_void_p]),
+    "nd_utnet_train_backward_hw": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                           c_void_p, c_size_t, c_void_p, POINTER(c_void_p), c_int]),
+    "nd_utnet_train_step_hw": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
+                                       c_float, c_float, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
+                                       POINTER(c_void_p), c_int]),
     "nd_adam_step": (c_int, [c_void_p] * 5 + [c_size_t, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p]),
     "nd_ssim_workspace_bytes": (c_size_t, [c_int] * 4),
     "nd_ssim": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_size_t, c_void_p]),

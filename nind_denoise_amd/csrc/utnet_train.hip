@@ -152,27 +152,28 @@ __global__ void k_add_clip_grad(const float *__restrict__ y, const float *__rest
     }
 }
 
-// pt_ops.pt_crop_batch (common/libs/pt_ops.py:1-8; nn_train.py:319-323): centre crop [N,S,S] -> [N,L,L], x0 = y0 = (S - L) / 2
-__global__ void k_center_crop(const float *__restrict__ src, int S, int L, long n_out, float *__restrict__ dst) {
-    const int o = (S - L) / 2;
+// pt_ops.pt_crop_batch (common/libs/pt_ops.py:1-8; nn_train.py:319-323): centre crop [N,H,W] -> [N,Lh,Lw],
+// y0 = (H - Lh) / 2, x0 = (W - Lw) / 2
+__global__ void k_center_crop(const float *__restrict__ src, int H, int W, int Lh, int Lw, long n_out, float *__restrict__ dst) {
+    const int oy = (H - Lh) / 2, ox = (W - Lw) / 2;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_out; i += (long)gridDim.x * blockDim.x) {
-        const int x = (int)(i % L), y = (int)((i / L) % L);
-        const long img = i / ((long)L * L);
-        dst[i] = src[(img * S + y + o) * S + x + o];
+        const int x = (int)(i % Lw), y = (int)((i / Lw) % Lh);
+        const long img = i / ((long)Lh * Lw);
+        dst[i] = src[(img * H + y + oy) * W + x + ox];
     }
 }
 // the gradient on the crop back onto the full output: zero outside the crop
-__global__ void k_center_uncrop(const float *__restrict__ g, int S, int L, long n_full, float *__restrict__ dst) {
-    const int o = (S - L) / 2;
+__global__ void k_center_uncrop(const float *__restrict__ g, int H, int W, int Lh, int Lw, long n_full, float *__restrict__ dst) {
+    const int oy = (H - Lh) / 2, ox = (W - Lw) / 2;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_full; i += (long)gridDim.x * blockDim.x) {
-        const int x = (int)(i % S) - o, y = (int)((i / S) % S) - o;
-        const long img = i / ((long)S * S);
-        dst[i] = (x >= 0 && x < L && y >= 0 && y < L) ? g[(img * L + y) * L + x] : 0.f;
+        const int x = (int)(i % W) - ox, y = (int)((i / W) % H) - oy;
+        const long img = i / ((long)H * W);
+        dst[i] = (x >= 0 && x < Lw && y >= 0 && y < Lh) ? g[(img * Lh + y) * Lw + x] : 0.f;
     }
 }
 
 // data gradient of the final Conv2d(f,3,1) + crop: g[c][b][Y][X] = sum_co gy[co][b][Y-crop][X-crop] * w[co][c] (0 outside)
-__global__ void k_final_bwd_data(const float *__restrict__ gy, int S, const float *__restrict__ w, int cin, int crop,
+__global__ void k_final_bwd_data(const float *__restrict__ gy, int H, int W, const float *__restrict__ w, int cin, int crop,
                                  f32x4 *__restrict__ g, long gnp, int Hb, int Wb, int B) {
     const int X = blockIdx.x * blockDim.x + threadIdx.x;
     const int Y = blockIdx.y;
@@ -180,9 +181,9 @@ __global__ void k_final_bwd_data(const float *__restrict__ gy, int S, const floa
     if (X >= Wb) return;
     f32x4 o = {0.f, 0.f, 0.f, 0.f};
     const int yy = Y - crop, xx = X - crop;
-    if (yy >= 0 && yy < S && xx >= 0 && xx < S) {
-        const float *p = gy + ((long)b * 3 * S + yy) * S + xx;
-        const float g0 = p[0], g1 = p[(long)S * S], g2 = p[2 * (long)S * S];
+    if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
+        const float *p = gy + ((long)b * 3 * H + yy) * W + xx;
+        const float g0 = p[0], g1 = p[(long)H * W], g2 = p[2 * (long)H * W];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int c = 4 * q + e;
@@ -193,16 +194,16 @@ __global__ void k_final_bwd_data(const float *__restrict__ gy, int S, const floa
 }
 
 // weight / bias gradient of the final 1x1, stage 1: one workgroup per (co, plane, image) -> partial[(co*planes+q)*B + b] (x,y,z,w = dw, then db)
-__global__ __launch_bounds__(256) void k_final_wgrad1(const float *__restrict__ gy, int S, const f32x4 *__restrict__ act, long anp,
+__global__ __launch_bounds__(256) void k_final_wgrad1(const float *__restrict__ gy, int H, int W, const f32x4 *__restrict__ act, long anp,
                                                       int Hb, int Wb, int crop, f32x4 *__restrict__ pw, float *__restrict__ pb) {
     __shared__ f32x4 red[256];
     __shared__ float redb[256];
     const int co = blockIdx.x, q = blockIdx.y, b = blockIdx.z;
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     float accb = 0.f;
-    for (int i = threadIdx.x; i < S * S; i += 256) {
-        const int y = i / S, x = i - y * S;
-        const float gv = gy[(((long)b * 3 + co) * S + y) * S + x];
+    for (int i = threadIdx.x; i < H * W; i += 256) {
+        const int y = i / W, x = i - y * W;
+        const float gv = gy[(((long)b * 3 + co) * H + y) * W + x];
         acc += act[(long)q * anp + ((long)b * Hb + y + crop) * Wb + x + crop] * gv;
         accb += gv;
     }
@@ -236,6 +237,64 @@ __global__ __launch_bounds__(64) void k_final_wgrad2(const f32x4 *__restrict__ p
         for (int b = 0; b < B; ++b) acc += pb[o + b];
         db[co] = acc;
     }
+}
+
+// d loss / d input image: the data gradient of the first Conv2d(3, f, 3) fused with the adjoint of ReflectionPad2d(2) (UtNet.py:27,98).
+// g1 = d loss / d pre-activation of convs1.0: f/4 planes of an (H+2) x (W+2) grid inside a zero border of gpad >= 2;
+// w0 = convs1.0.weight [f][3][3][3]; dx [B,3,H,W] NCHW.  On the (H+4) x (W+4) padded input grid
+//     gP[c][v][u] = sum_co sum_ky,kx g1[co][v-ky][u-kx] * w0[co][c][ky][kx]        (g1 zero outside its grid: the border)
+// and dx[c][y][x] = sum of gP[c][v][u] over the (v, u) that the reflection maps onto (y, x): v = y + 2, plus v = 2 - y for
+// y = 1, 2 and v = 2H - y for y = H-3, H-2 (the mirror that does not repeat the edge, reflect_nr); the same along x.
+// gP is linear in g1, so a lane sums the 1, 2 or 4 source windows of g1 first and contracts once with w0.  A workgroup = one
+// 16 x 4 pixel patch of one image x kIgGroups plane groups (wave w takes planes w, w + kIgGroups, ...: short dependent chains,
+// four times the waves in flight); the groups' partial sums meet in LDS in a fixed order.  The patch shape keeps a wave's 3 x 3
+// windows within 6 rows of 18 pixels (L1 reuse), and only waves on the image's edge take the mirror branches.  w0 indices are
+// uniform (scalar loads).  Every output written once, no atomics.
+constexpr int kIgGroups = 4;
+__global__ __launch_bounds__(64 * kIgGroups) void k_input_grad(const f32x4 *__restrict__ g1, long gnp, int gHb, int gWb, int gpad,
+                                                               int planes, const float *__restrict__ w0, int H, int W,
+                                                               float *__restrict__ dx) {
+    __shared__ float part[kIgGroups][3][64];
+    const int lane = threadIdx.x & 63, grp = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: scalar weight loads
+    const int b = blockIdx.z;
+    const bool live = (int)blockIdx.x * 16 + (lane & 15) < W && (int)blockIdx.y * 4 + (lane >> 4) < H;
+    const int x = live ? blockIdx.x * 16 + (lane & 15) : 0, y = live ? blockIdx.y * 4 + (lane >> 4) : 0;
+    // bordered row of g1 for padded row v and tap ky: v - ky + gpad; rows of the second source as an offset from the first
+    const int vm = (y == 1 || y == 2) ? 2 - y : ((y == H - 2 || y == H - 3) ? 2 * H - y : -1);
+    const int um = (x == 1 || x == 2) ? 2 - x : ((x == W - 2 || x == W - 3) ? 2 * W - x : -1);
+    const long drow = vm >= 0 ? (long)(vm - (y + 2)) * gWb : 0;
+    const int dcol = um >= 0 ? um - (x + 2) : 0;
+    const f32x4 *gb = g1 + ((long)b * gHb + y + 2 + gpad) * gWb + x + 2 + gpad;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    for (int q = grp; q < planes; q += kIgGroups) {
+        const f32x4 *gq = gb + (long)q * gnp;
+        const float *wq = w0 + (long)q * 4 * 27;   // co = 4q .. 4q+3: 108 contiguous floats [e][c][ky][kx]
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int ky = t / 3, kx = t - 3 * ky;
+            const f32x4 *p = gq - (long)ky * gWb - kx;
+            f32x4 s = p[0];
+            if (vm >= 0) s += p[drow];
+            if (um >= 0) s += p[dcol];
+            if (vm >= 0 && um >= 0) s += p[drow + dcol];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                a0 = fmaf(s[e], wq[e * 27 + t], a0);
+                a1 = fmaf(s[e], wq[e * 27 + 9 + t], a1);
+                a2 = fmaf(s[e], wq[e * 27 + 18 + t], a2);
+            }
+        }
+    }
+    part[grp][0][lane] = a0;
+    part[grp][1][lane] = a1;
+    part[grp][2][lane] = a2;
+    __syncthreads();
+    if (grp >= 3 || !live) return;
+    const int c = grp;   // waves 0, 1, 2 write channels 0, 1, 2
+    float v = part[0][c][lane];
+#pragma unroll
+    for (int k = 1; k < kIgGroups; ++k) v += part[k][c][lane];
+    dx[(((long)b * 3 + c) * H + y) * W + x] = v;
 }
 
 // Adam with amsgrad, torch.optim.Adam semantics (nn_common.py:185): no weight decay
@@ -343,10 +402,10 @@ struct TrainPlan {
     float *partial;         // wgrad K-slice partial sums
     size_t partial_floats;
     float *red;             // reduction scratch
-    float *gy;              // d loss / d output  [B,3,S,S]
-    float *yclip, *gssim;   // SSIM / MS-SSIM terms: clip(y, 0, 1) and the gradient with respect to it  [B,3,S,S]
-    float *ycrop, *tcrop, *gcrop;   // loss_cs < cs: centre crops of output / target and the gradient on the crop  [B,3,L,L]
-    char *ssim_ws;          // nd_ssim_loss_workspace_bytes(B, 3, S, S)
+    float *gy;              // d loss / d output  [B,3,H,W]
+    float *yclip, *gssim;   // SSIM / MS-SSIM terms: clip(y, 0, 1) and the gradient with respect to it  [B,3,H,W]
+    float *ycrop, *tcrop, *gcrop;   // a loss crop smaller than the output: centre crops of output / target and the gradient on the crop
+    char *ssim_ws;          // nd_ssim_loss_workspace_bytes(B, 3, H, W)
     size_t ssim_ws_bytes;
     size_t bytes;
 };
@@ -366,9 +425,9 @@ int grad_pad(Buf id) {
     }
 }
 
-TrainPlan make_train_plan(int f, int cs, int B, char *base) {
+TrainPlan make_train_plan(int f, int h, int w, int B, char *base) {
     TrainPlan t;
-    t.fwd = make_plan(f, cs, cs, B, B, base, ND_F32);
+    t.fwd = make_plan(f, h, w, B, B, base, ND_F32);
     size_t off = t.fwd.bytes;
     auto alloc = [&](QpBuf &q, int planes, int Hb, int Wb, int pad) {
         q.planes = planes;
@@ -430,18 +489,18 @@ TrainPlan make_train_plan(int f, int cs, int B, char *base) {
     t.red = (float *)(base ? base + off : nullptr);
     off += kRedFloats * 4;
     t.gy = (float *)(base ? base + off : nullptr);
-    off += (size_t)B * 3 * cs * cs * 4;
+    off += (size_t)B * 3 * h * w * 4;
     off = (off + 255) & ~(size_t)255;
     t.yclip = (float *)(base ? base + off : nullptr);
-    off += ((size_t)B * 3 * cs * cs * 4 + 255) & ~(size_t)255;
+    off += ((size_t)B * 3 * h * w * 4 + 255) & ~(size_t)255;
     t.gssim = (float *)(base ? base + off : nullptr);
-    off += ((size_t)B * 3 * cs * cs * 4 + 255) & ~(size_t)255;
+    off += ((size_t)B * 3 * h * w * 4 + 255) & ~(size_t)255;
     for (float **pp : {&t.ycrop, &t.tcrop, &t.gcrop}) {
         *pp = (float *)(base ? base + off : nullptr);
-        off += ((size_t)B * 3 * cs * cs * 4 + 255) & ~(size_t)255;
+        off += ((size_t)B * 3 * h * w * 4 + 255) & ~(size_t)255;
     }
     t.ssim_ws = base ? base + off : nullptr;
-    t.ssim_ws_bytes = nd_ssim_loss_workspace_bytes(B, 3, cs, cs);
+    t.ssim_ws_bytes = nd_ssim_loss_workspace_bytes(B, 3, h, w);
     off += (t.ssim_ws_bytes + 255) & ~(size_t)255;
     t.bytes = off;
     return t;
@@ -459,9 +518,10 @@ QpBuf scratch_view(const TrainPlan &t, int planes, int B, int H, int W) {
     return q;
 }
 
-int check_train(int funit, int cs, int batch) {
+int check_train(int funit, int h, int w, int batch) {
     if (funit < 8 || funit % 8) ND_FAIL(ND_EINVAL, "UtNet training: funit=%d must be a positive multiple of 8", funit);
-    if (!valid_cs(cs)) ND_FAIL(ND_EINVAL, "UtNet training: crop size %d is not of the form 16k+56 (e.g. 136, 184)", cs);
+    for (int cs : {h, w})
+        if (!valid_cs(cs)) ND_FAIL(ND_EINVAL, "UtNet training: crop side %d is not of the form 16k+56 (e.g. 136, 184)", cs);
     if (batch <= 0) ND_FAIL(ND_EINVAL, "UtNet training: batch=%d", batch);
     return ND_OK;
 }
@@ -482,23 +542,29 @@ extern "C" size_t nd_utnet_train_blob_bytes(int funit) {
     if (funit < 8 || funit % 8) return 0;
     return (blob_layout(funit, ND_F32, false, true).total + bwd_blob_layout(funit).total) * sizeof(float);
 }
-extern "C" size_t nd_utnet_train_workspace_bytes(int funit, int cs, int batch) {
-    if (check_train(funit, cs, batch) != ND_OK) return 0;
-    return make_train_plan(funit, cs, batch, nullptr).bytes;
+extern "C" size_t nd_utnet_train_workspace_bytes_hw(int funit, int h, int w, int batch) {
+    if (check_train(funit, h, w, batch) != ND_OK) return 0;
+    return make_train_plan(funit, h, w, batch, nullptr).bytes;
 }
-extern "C" int nd_utnet_train_workspace_init(void *ws, size_t ws_bytes, int funit, int cs, int batch, void *stream) {
-    ND_TRY(check_train(funit, cs, batch));
-    const size_t need = make_train_plan(funit, cs, batch, nullptr).bytes;
+extern "C" size_t nd_utnet_train_workspace_bytes(int funit, int cs, int batch) {
+    return nd_utnet_train_workspace_bytes_hw(funit, cs, cs, batch);
+}
+extern "C" int nd_utnet_train_workspace_init_hw(void *ws, size_t ws_bytes, int funit, int h, int w, int batch, void *stream) {
+    ND_TRY(check_train(funit, h, w, batch));
+    const size_t need = make_train_plan(funit, h, w, batch, nullptr).bytes;
     if (!ws || ws_bytes < need) ND_FAIL(ND_ENOMEM, "UtNet training workspace: %zu B given, %zu B needed", ws_bytes, need);
     ND_HIP(hipMemsetAsync(ws, 0, need, (hipStream_t)stream));   // zero borders of activations AND gradients, slack
     return ND_OK;
+}
+extern "C" int nd_utnet_train_workspace_init(void *ws, size_t ws_bytes, int funit, int cs, int batch, void *stream) {
+    return nd_utnet_train_workspace_init_hw(ws, ws_bytes, funit, cs, cs, batch, stream);
 }
 
 // ---- the step in two halves: (1) weight packing + forward with the pre-activations kept, (2) backward from d loss / d output.
 // nd_utnet_train_step runs both with the loss between them; nd_utnet_train_forward / nd_utnet_train_backward expose the halves
 // to torch.autograd (networks/UtNet.py: model(x).clip(0, 1), loss.backward() of nn_common.py:198-218 then work unchanged).
 struct TrainCtx {
-    int f, B, cs, flags, act;
+    int f, B, H, W, flags, act;
     TrainPlan t;
     ParamLayout pl;
     BlobLayout bl;
@@ -509,18 +575,19 @@ struct TrainCtx {
     hipStream_t s;
 };
 
-static int train_ctx(TrainCtx &c, int funit, int flags, int act, const float *params, void *blobs, int batch, int cs, void *ws,
+static int train_ctx(TrainCtx &c, int funit, int flags, int act, const float *params, void *blobs, int batch, int h, int w, void *ws,
                      size_t ws_bytes, void *stream) {
     ND_TRY(nd_check_flags(flags));
-    ND_TRY(check_train(funit, cs, batch));
+    ND_TRY(check_train(funit, h, w, batch));
     if (act < ND_ACT_PRELU || act > ND_ACT_HARDSWISH) ND_FAIL(ND_EINVAL, "UtNet training: unknown activation %d", act);
     if (!params || !blobs || !ws) ND_FAIL(ND_EINVAL, "train step: null pointer");
     c.f = funit;
     c.B = batch;
-    c.cs = cs;
+    c.H = h;
+    c.W = w;
     c.flags = flags;
     c.act = act;
-    c.t = make_train_plan(funit, cs, batch, (char *)ws);
+    c.t = make_train_plan(funit, h, w, batch, (char *)ws);
     if (ws_bytes < c.t.bytes) ND_FAIL(ND_ENOMEM, "UtNet training workspace: %zu B given, %zu B needed", ws_bytes, c.t.bytes);
     c.s = (hipStream_t)stream;
     c.pl = param_layout(funit);
@@ -547,9 +614,9 @@ static int train_ctx(TrainCtx &c, int funit, int flags, int act, const float *pa
 }
 
 // (1) pack the weights on the device (forward roles, and transposed roles for the data gradients), forward with the
-// pre-activations kept; y_out: [batch,3,cs,cs]
+// pre-activations kept; y_out: [batch,3,H,W]
 static int train_forward(TrainCtx &c, const float *params, const float *x, float *y_out) {
-    const int f = c.f, B = c.B, cs = c.cs;
+    const int f = c.f, B = c.B, H = c.H, W = c.W;
     hipStream_t s = c.s;
     const BlobLayout &bl = c.bl;
     const BwdBlob &bb = c.bb;
@@ -581,16 +648,27 @@ static int train_forward(TrainCtx &c, const float *params, const float *x, float
     if (c.act == ND_ACT_PRELU)
         for (int k = 0; k < kNumSlopes; ++k)
             ND_HIP(hipMemcpyAsync(fblob + k, c.slopes[k], sizeof(float), hipMemcpyDeviceToDevice, s));
-    ND_TRY(nd_launch_reflect_pack(x, B, cs, cs, c.t.fwd.buf[X0], s));
+    ND_TRY(nd_launch_reflect_pack(x, B, H, W, c.t.fwd.buf[X0], s));
     ND_TRY(run_stack(f, c.act, ND_F32, fblob, c.t.fwd, s, c.flags, nullptr, c.t.pre, nullptr, c.fwd_w1));
     const float *fw = fblob + bl.off[kNumLayers - 1];
-    ND_TRY(nd_launch_final1x1(c.t.fwd.buf[T4B], f, fw, fw + 3 * f, 2, y_out, cs, cs, s));
+    ND_TRY(nd_launch_final1x1(c.t.fwd.buf[T4B], f, fw, fw + 3 * f, 2, y_out, H, W, s));
     return ND_OK;
 }
 
-// (2) backward: gy = d loss / d output [batch,3,cs,cs]; every parameter gradient into the flat buffer `grads`
-static int train_backward(TrainCtx &c, float *grads, const float *gy, void *const *bucket_ev = nullptr) {
-    const int f = c.f, B = c.B, cs = c.cs, flags = c.flags;
+int nd_launch_input_grad(const QpBuf &g1, const float *w0, int H, int W, float *dx, hipStream_t s) {
+    if (g1.dt != ND_F32 || g1.pad < 2 || g1.Hb != H + 2 + 2 * g1.pad || g1.Wb != W + 2 + 2 * g1.pad)
+        ND_FAIL(ND_EINVAL, "input gradient: bad source geometry");
+    dim3 grid((unsigned)((W + 15) / 16), (unsigned)((H + 3) / 4), g1.B);
+    hipLaunchKernelGGL(k_input_grad, grid, dim3(64 * kIgGroups), 0, s, (const f32x4 *)g1.base, g1.np(), g1.Hb, g1.Wb, g1.pad,
+                       g1.planes, w0, H, W, dx);
+    ND_HIP(hipGetLastError());
+    return ND_OK;
+}
+
+// (2) backward: gy = d loss / d output [batch,3,H,W].  grads (nullable): every parameter gradient into the flat buffer;
+// dx (nullable): d loss / d input image [batch,3,H,W].  Parameter-gradient launches and bucket events run only with grads.
+static int train_backward(TrainCtx &c, const float *params, float *grads, const float *gy, float *dx, void *const *bucket_ev = nullptr) {
+    const int f = c.f, B = c.B, H = c.H, W = c.W, flags = c.flags;
     hipStream_t s = c.s;
     TrainPlan &t = c.t;
     const BlobLayout &bl = c.bl;
@@ -605,12 +683,14 @@ static int train_backward(TrainCtx &c, float *grads, const float *gy, void *cons
         const QpBuf &a = t.fwd.buf[T4B], &g = t.g[T4B];
         f32x4 *pw = (f32x4 *)t.red;
         float *pb = t.red + (size_t)4 * 3 * (f / 4) * B;
-        hipLaunchKernelGGL(k_final_wgrad1, dim3(3, f / 4, B), dim3(256), 0, s, gy, cs, (const f32x4 *)a.base,
-                           a.np(), a.Hb, a.Wb, 2, pw, pb);
-        hipLaunchKernelGGL(k_final_wgrad2, dim3(3, f / 4), dim3(64), 0, s, (const f32x4 *)pw, (const float *)pb, f / 4, B, f,
-                           G("tconvs4.4.weight"), G("tconvs4.4.bias"));
+        if (grads) {
+            hipLaunchKernelGGL(k_final_wgrad1, dim3(3, f / 4, B), dim3(256), 0, s, gy, H, W, (const f32x4 *)a.base,
+                               a.np(), a.Hb, a.Wb, 2, pw, pb);
+            hipLaunchKernelGGL(k_final_wgrad2, dim3(3, f / 4), dim3(64), 0, s, (const f32x4 *)pw, (const float *)pb, f / 4, B, f,
+                               G("tconvs4.4.weight"), G("tconvs4.4.bias"));
+        }
         dim3 grid((g.Wb + 127) / 128, g.Hb, B * (f / 4));
-        hipLaunchKernelGGL(k_final_bwd_data, grid, dim3(128), 0, s, gy, cs, fw, f, 2, (f32x4 *)g.base, g.np(), g.Hb,
+        hipLaunchKernelGGL(k_final_bwd_data, grid, dim3(128), 0, s, gy, H, W, fw, f, 2, (f32x4 *)g.base, g.np(), g.Hb,
                            g.Wb, B);
         ND_HIP(hipGetLastError());
     }
@@ -642,7 +722,9 @@ static int train_backward(TrainCtx &c, float *grads, const float *gy, void *cons
             if (c.act == ND_ACT_PRELU) {
                 hipLaunchKernelGGL(k_act_bwd<ND_ACT_PRELU>, dim3(B, oplanes), dim3(256), 0, s, gq, go.np(), go.Hb, go.Wb, go.pad,
                                    (const f32x4 *)pr.base, pr.np(), oh, ow, slopes[l.prelu], t.red);
-                hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, (const float *)t.red, B * oplanes, 1.f, G(prelu_name(l.key)));
+                if (grads)
+                    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, (const float *)t.red, B * oplanes, 1.f,
+                                       G(prelu_name(l.key)));
             } else if (c.act == ND_ACT_ELU) {
                 hipLaunchKernelGGL(k_act_bwd<ND_ACT_ELU>, dim3(B, oplanes), dim3(256), 0, s, gq, go.np(), go.Hb, go.Wb, go.pad,
                                    (const f32x4 *)pr.base, pr.np(), oh, ow, (const float *)nullptr, t.red);
@@ -653,19 +735,19 @@ static int train_backward(TrainCtx &c, float *grads, const float *gy, void *cons
             ND_HIP(hipGetLastError());
         }
         // bias gradient
-        ND_TRY(nd_launch_channel_sum(go, oplane0, co, G(std::string(l.key) + ".bias"), t.red, s));
-        // weight gradient
-        float *dw = G(std::string(l.key) + ".weight");
-        if (l.kind == ND_CONV3) {
+        if (grads) ND_TRY(nd_launch_channel_sum(go, oplane0, co, G(std::string(l.key) + ".bias"), t.red, s));
+        // weight gradient (none without `grads`: frozen parameters)
+        float *dw = grads ? G(std::string(l.key) + ".weight") : nullptr;
+        if (grads && l.kind == ND_CONV3) {
             QpBuf a = scratch_view(t, oplanes, B, in.Hb, in.Wb);
             ND_TRY(nd_launch_repitch(go, oplane0, oplanes, 1, 0, 0, a, 0, 0, oh, ow, s));
             ND_TRY(nd_launch_wgrad(a, 0, co, in, 0, ci, 9, 9, 0, t.partial, t.partial_floats, dw, s));
-        } else if (l.kind == ND_CONVT3) {
+        } else if (grads && l.kind == ND_CONVT3) {
             QpBuf a = scratch_view(t, (ci + 3) / 4, B, oh, ow);
             ND_TRY(nd_launch_repitch(in, 0, (ci + 3) / 4, 1, 0, 0, a, 0, 0, ih, iw, s));
             QpBuf gb = go;   // pad 0 by construction: the whole buffer is the grid
             ND_TRY(nd_launch_wgrad(a, 0, ci, gb, oplane0, co, 9, 9, 0, t.partial, t.partial_floats, dw, s));
-        } else {   // ConvTranspose2d(2, s=2): four 1-tap problems on the input grid
+        } else if (grads) {   // ConvTranspose2d(2, s=2): four 1-tap problems on the input grid
             for (int ab = 0; ab < 4; ++ab) {
                 QpBuf bq = scratch_view(t, oplanes, B, ih, iw);
                 ND_TRY(nd_launch_repitch(go, oplane0, oplanes, 2, ab >> 1, ab & 1, bq, 0, 0, ih, iw, s));
@@ -701,9 +783,12 @@ static int train_backward(TrainCtx &c, float *grads, const float *gy, void *cons
             } else {
                 ND_TRY(nd_launch_conv(d, s));
             }
+        } else if (dx) {
+            // the input image's gradient: first layer's data gradient + the adjoint of ReflectionPad2d(2), one kernel
+            ND_TRY(nd_launch_input_grad(go, params + c.pl.off[tensor_index("convs1.0.weight")], H, W, dx, s));
         }
         // every parameter gradient of this layer's level is final once the level's first layer is done: tell the reducer
-        if (bucket_ev) {
+        if (grads && bucket_ev) {
             const int k = bucket_of_key(l.key);
             if (k >= 0 && bucket_tail_layer(k) == st.layer) ND_HIP(hipEventRecord((hipEvent_t)bucket_ev[k], s));
         }
@@ -715,32 +800,34 @@ static int train_backward(TrainCtx &c, float *grads, const float *gy, void *cons
 //   loss = w_l1 * mean|g - target| + w_mse * mean (g - target)^2 + w_ssim * mean_n(1 - SSIM_n(g, target))
 //          + w_msssim * mean_n(1 - MS-SSIM_n(g, target)),      g = clip(y, 0, 1)          (nn_common.py:198-199, 226-241)
 // and the backward pass.  params / grads: flat fp32 buffers in state-dict order (nd_utnet_param_range);
-// x, target, y_out: [batch,3,cs,cs] NCHW fp32; loss_out: one float in HBM; blobs: nd_utnet_train_blob_bytes scratch.
+// x, target, y_out: [batch,3,h,w] NCHW fp32; loss_out: one float in HBM; blobs: nd_utnet_train_blob_bytes scratch.
 static int train_step_impl(int funit, int flags, const float *params, float *grads, void *blobs, const float *x,
                            const float *target, float *y_out, float w_l1, float w_mse, float w_ssim, float w_msssim,
-                           float *loss_out, int batch, int cs, int loss_cs, void *ws, size_t ws_bytes, void *stream,
+                           float *loss_out, int batch, int h, int w, int loss_cs, void *ws, size_t ws_bytes, void *stream,
                            void *const *bucket_ev) {
-    const int L = loss_cs > 0 ? loss_cs : cs;   // the criteria see the centre crop of this size (nn_train.py:319-323)
-    if (L > cs) ND_FAIL(ND_EINVAL, "UtNet training: loss_cs=%d exceeds the crop size %d", L, cs);
+    // the criteria see the centre loss_cs x loss_cs crop (nn_train.py:319-323, pt_ops.pt_crop_batch), or the whole output
+    const int Lh = loss_cs > 0 ? loss_cs : h, Lw = loss_cs > 0 ? loss_cs : w, L = Lh < Lw ? Lh : Lw;
+    if (Lh > h || Lw > w) ND_FAIL(ND_EINVAL, "UtNet training: loss_cs=%d exceeds the crop size %dx%d", loss_cs, h, w);
     if (w_msssim != 0.f && L < 161)
         ND_FAIL(ND_EINVAL, "UtNet training: the MS-SSIM loss needs crops of at least 161 pixels (five scales of an 11-tap window), "
                            "got %d; the reference fails on them too (pt_losses.py:20-28)", L);
     if (w_ssim != 0.f && L < 11) ND_FAIL(ND_EINVAL, "UtNet training: the SSIM loss needs at least 11 pixels, got %d", L);
     if (!grads || !x || !target || !y_out || !loss_out) ND_FAIL(ND_EINVAL, "train step: null pointer");
     TrainCtx c;
-    ND_TRY(train_ctx(c, funit, flags, ND_ACT_PRELU, params, blobs, batch, cs, ws, ws_bytes, stream));
+    ND_TRY(train_ctx(c, funit, flags, ND_ACT_PRELU, params, blobs, batch, h, w, ws, ws_bytes, stream));
     ND_TRY(train_forward(c, params, x, y_out));
     TrainPlan &t = c.t;
     hipStream_t s = c.s;
     const int B = batch;
-    // ---- 3. loss and its gradient, on the centre crop of loss_cs pixels (the whole output when loss_cs == cs)
-    const long nfull = (long)B * 3 * cs * cs, nout = (long)B * 3 * L * L;
+    const bool crop = Lh != h || Lw != w;
+    // ---- 3. loss and its gradient, on the centre crop (the whole output when there is none)
+    const long nfull = (long)B * 3 * h * w, nout = (long)B * 3 * Lh * Lw;
     const int lblocks = 1024;
     const float *yl = y_out, *tl = target;
     float *gl = t.gy;
-    if (L != cs) {
-        hipLaunchKernelGGL(k_center_crop, dim3(1024), dim3(256), 0, s, (const float *)y_out, cs, L, nout, t.ycrop);
-        hipLaunchKernelGGL(k_center_crop, dim3(1024), dim3(256), 0, s, target, cs, L, nout, t.tcrop);
+    if (crop) {
+        hipLaunchKernelGGL(k_center_crop, dim3(1024), dim3(256), 0, s, (const float *)y_out, h, w, Lh, Lw, nout, t.ycrop);
+        hipLaunchKernelGGL(k_center_crop, dim3(1024), dim3(256), 0, s, target, h, w, Lh, Lw, nout, t.tcrop);
         yl = t.ycrop;
         tl = t.tcrop;
         gl = t.gcrop;
@@ -752,26 +839,26 @@ static int train_step_impl(int funit, int flags, const float *params, float *gra
         hipLaunchKernelGGL(k_clip01, dim3(1024), dim3(256), 0, s, yl, nout, t.yclip);
         int acc = 0;
         if (w_ssim != 0.f) {
-            ND_TRY(nd_ssim_loss_grad(t.yclip, tl, B, 3, L, L, 0, w_ssim, loss_out, t.gssim, acc, t.ssim_ws, t.ssim_ws_bytes, s));
+            ND_TRY(nd_ssim_loss_grad(t.yclip, tl, B, 3, Lh, Lw, 0, w_ssim, loss_out, t.gssim, acc, t.ssim_ws, t.ssim_ws_bytes, s));
             acc = 1;
         }
         if (w_msssim != 0.f)
-            ND_TRY(nd_ssim_loss_grad(t.yclip, tl, B, 3, L, L, 1, w_msssim, loss_out, t.gssim, acc, t.ssim_ws, t.ssim_ws_bytes, s));
+            ND_TRY(nd_ssim_loss_grad(t.yclip, tl, B, 3, Lh, Lw, 1, w_msssim, loss_out, t.gssim, acc, t.ssim_ws, t.ssim_ws_bytes, s));
         hipLaunchKernelGGL(k_add_clip_grad, dim3(1024), dim3(256), 0, s, yl, (const float *)t.gssim, nout, gl);
         ND_HIP(hipGetLastError());
     }
-    if (L != cs) {
-        hipLaunchKernelGGL(k_center_uncrop, dim3(1024), dim3(256), 0, s, (const float *)t.gcrop, cs, L, nfull, t.gy);
+    if (crop) {
+        hipLaunchKernelGGL(k_center_uncrop, dim3(1024), dim3(256), 0, s, (const float *)t.gcrop, h, w, Lh, Lw, nfull, t.gy);
         ND_HIP(hipGetLastError());
     }
 
-    return train_backward(c, grads, t.gy, bucket_ev);
+    return train_backward(c, params, grads, t.gy, nullptr, bucket_ev);
 }
 extern "C" int nd_utnet_train_step(int funit, int flags, const float *params, float *grads, void *blobs, const float *x,
                                    const float *target, float *y_out, float w_l1, float w_mse, float w_ssim, float w_msssim,
                                    float *loss_out, int batch, int cs, int loss_cs, void *ws, size_t ws_bytes, void *stream) {
     return train_step_impl(funit, flags, params, grads, blobs, x, target, y_out, w_l1, w_mse, w_ssim, w_msssim, loss_out, batch, cs,
-                           loss_cs, ws, ws_bytes, stream, nullptr);
+                           cs, loss_cs, ws, ws_bytes, stream, nullptr);
 }
 // The same step for a data-parallel run that overlaps the gradient reduction with the backward pass: bucket_events[k]
 // (hipEvent_t, nd_utnet_grad_buckets of them) is recorded on `stream` as soon as every gradient of bucket k is final.
@@ -781,7 +868,16 @@ extern "C" int nd_utnet_train_step_ev(int funit, int flags, const float *params,
                                       void *const *bucket_events, int n_events) {
     if (!bucket_events || n_events != kNumBuckets) ND_FAIL(ND_EINVAL, "train step: %d bucket events expected", kNumBuckets);
     return train_step_impl(funit, flags, params, grads, blobs, x, target, y_out, w_l1, w_mse, w_ssim, w_msssim, loss_out, batch, cs,
-                           loss_cs, ws, ws_bytes, stream, bucket_events);
+                           cs, loss_cs, ws, ws_bytes, stream, bucket_events);
+}
+// The step on h x w crops (each side 16k+56); bucket_events nullable (else nd_utnet_grad_buckets of them)
+extern "C" int nd_utnet_train_step_hw(int funit, int flags, const float *params, float *grads, void *blobs, const float *x,
+                                      const float *target, float *y_out, float w_l1, float w_mse, float w_ssim, float w_msssim,
+                                      float *loss_out, int batch, int h, int w, int loss_cs, void *ws, size_t ws_bytes, void *stream,
+                                      void *const *bucket_events, int n_events) {
+    if (bucket_events && n_events != kNumBuckets) ND_FAIL(ND_EINVAL, "train step: %d bucket events expected", kNumBuckets);
+    return train_step_impl(funit, flags, params, grads, blobs, x, target, y_out, w_l1, w_mse, w_ssim, w_msssim, loss_out, batch, h,
+                           w, loss_cs, ws, ws_bytes, stream, bucket_events);
 }
 // Buckets of the flat gradient buffer in the order the backward pass completes them (one per decoder / encoder level):
 // offsets / counts in floats.  Returns the number of buckets (9); fills at most `max` entries.
@@ -805,23 +901,35 @@ extern "C" int nd_utnet_grad_buckets(int funit, size_t *offsets, size_t *counts,
 
 // The two halves for torch.autograd (act: ND_ACT_PRELU | ND_ACT_ELU | ND_ACT_HARDSWISH, the reference constructor's choices,
 // networks/UtNet.py:17-26).  `ws` and `blobs` carry the forward's activations, pre-activations and packed weights to the
-// backward call: the caller keeps both untouched in between.  The input's own gradient is not produced (the first layer's data
-// gradient is skipped, as in the fused step): images are not trained.
-extern "C" int nd_utnet_train_forward(int funit, int act, int flags, const float *params, void *blobs, const float *x, float *y_out,
-                                      int batch, int cs, void *ws, size_t ws_bytes, void *stream) {
+// backward call: the caller keeps both untouched in between.  The backward produces the parameter gradients (grads, nullable)
+// and the input image's gradient (dx, nullable: the first layer's data gradient through the reflection padding); at least one.
+extern "C" int nd_utnet_train_forward_hw(int funit, int act, int flags, const float *params, void *blobs, const float *x, float *y_out,
+                                         int batch, int h, int w, void *ws, size_t ws_bytes, void *stream) {
     if (!x || !y_out) ND_FAIL(ND_EINVAL, "train forward: null pointer");
     TrainCtx c;
-    ND_TRY(train_ctx(c, funit, flags, act, params, blobs, batch, cs, ws, ws_bytes, stream));
+    ND_TRY(train_ctx(c, funit, flags, act, params, blobs, batch, h, w, ws, ws_bytes, stream));
     return train_forward(c, params, x, y_out);
+}
+extern "C" int nd_utnet_train_backward_hw(int funit, int act, int flags, const float *params, float *grads, void *blobs,
+                                          const float *gy, float *dx, int batch, int h, int w, void *ws, size_t ws_bytes, void *stream,
+                                          void *const *bucket_events, int n_events) {
+    if (!gy) ND_FAIL(ND_EINVAL, "train backward: null pointer");
+    if (!grads && !dx) ND_FAIL(ND_EINVAL, "train backward: neither parameter gradients nor the input gradient requested");
+    if (bucket_events && n_events != kNumBuckets) ND_FAIL(ND_EINVAL, "train backward: %d bucket events expected", kNumBuckets);
+    TrainCtx c;
+    ND_TRY(train_ctx(c, funit, flags, act, params, blobs, batch, h, w, ws, ws_bytes, stream));
+    return train_backward(c, params, grads, gy, dx, bucket_events);
+}
+extern "C" int nd_utnet_train_forward(int funit, int act, int flags, const float *params, void *blobs, const float *x, float *y_out,
+                                      int batch, int cs, void *ws, size_t ws_bytes, void *stream) {
+    return nd_utnet_train_forward_hw(funit, act, flags, params, blobs, x, y_out, batch, cs, cs, ws, ws_bytes, stream);
 }
 extern "C" int nd_utnet_train_backward(int funit, int act, int flags, const float *params, float *grads, void *blobs, const float *gy,
                                        int batch, int cs, void *ws, size_t ws_bytes, void *stream, void *const *bucket_events,
                                        int n_events) {
     if (!grads || !gy) ND_FAIL(ND_EINVAL, "train backward: null pointer");
-    if (bucket_events && n_events != kNumBuckets) ND_FAIL(ND_EINVAL, "train backward: %d bucket events expected", kNumBuckets);
-    TrainCtx c;
-    ND_TRY(train_ctx(c, funit, flags, act, params, blobs, batch, cs, ws, ws_bytes, stream));
-    return train_backward(c, grads, gy, bucket_events);
+    return nd_utnet_train_backward_hw(funit, act, flags, params, grads, blobs, gy, nullptr, batch, cs, cs, ws, ws_bytes, stream,
+                                      bucket_events, n_events);
 }
 
 // torch.optim.Adam(params, lr, betas=(b1,b2), eps, amsgrad) on flat buffers; step = 1, 2, ...

@@ -30,7 +30,7 @@ def nearest_valid_cs(cs):
 
 class _TrainState:
     """Flat parameter / gradient buffers, packed-weight blobs and the training workspace of one module on one device
-    (nd_utnet_train_forward / nd_utnet_train_backward of include/nind_hip.h)."""
+    (nd_utnet_train_forward_hw / nd_utnet_train_backward_hw of include/nind_hip.h)."""
 
     def __init__(self, model, device):
         lib = _lib.load()
@@ -49,25 +49,26 @@ class _TrainState:
         self.ws, self.ws_key = None, None
         self.generation = 0          # bumped by every forward: a backward must follow ITS forward
 
-    def workspace(self, model, cs, batch):
-        if self.ws_key != (cs, batch):
+    def workspace(self, model, h, w, batch):
+        if self.ws_key != (h, w, batch):
             lib = _lib.load()
-            nbytes = lib.nd_utnet_train_workspace_bytes(model.funit, cs, batch)
+            nbytes = lib.nd_utnet_train_workspace_bytes_hw(model.funit, h, w, batch)
             if nbytes == 0:
-                _lib.check(lib.nd_utnet_train_workspace_init(None, 0, model.funit, cs, batch, None), "UtNet training")
+                _lib.check(lib.nd_utnet_train_workspace_init_hw(None, 0, model.funit, h, w, batch, None), "UtNet training")
             self.ws = None
             self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(lib.nd_utnet_train_workspace_init(self.ws.data_ptr(), nbytes, model.funit, cs, batch, _lib.stream_ptr(self.device)),
-                       "nd_utnet_train_workspace_init")
-            self.ws_key = (cs, batch)
+            _lib.check(lib.nd_utnet_train_workspace_init_hw(self.ws.data_ptr(), nbytes, model.funit, h, w, batch,
+                                                            _lib.stream_ptr(self.device)), "nd_utnet_train_workspace_init_hw")
+            self.ws_key = (h, w, batch)
         return self.ws
 
 
 class _UtNetFunction(torch.autograd.Function):
     """UtNet.forward under autograd: forward = device-side weight packing + the conv stack with the pre-activations kept
-    (nd_utnet_train_forward), backward = activation / bias / weight / data gradients of every layer (nd_utnet_train_backward),
-    the kernels of the fused training step (csrc/utnet_train.hip).  Gradients are returned for the parameters; the input image
-    gets none (the reference never trains through it)."""
+    (nd_utnet_train_forward_hw), backward = activation / bias / weight / data gradients of every layer
+    (nd_utnet_train_backward_hw), the kernels of the fused training step (csrc/utnet_train.hip).  The backward computes only
+    what autograd asks for: the parameter gradients (skipped when no parameter requires one) and the input image's gradient
+    (the first layer's data gradient through the input's reflection padding, when x requires one)."""
 
     @staticmethod
     def forward(ctx, model, names, x, *params):
@@ -76,15 +77,16 @@ class _UtNetFunction(torch.autograd.Function):
             for n, p in zip(names, params):
                 off, cnt = st.ranges[n]
                 st.flat[off:off + cnt].copy_(p.detach().reshape(-1))
-        batch, cs = x.size(0), x.size(2)
+        batch, h, w = x.size(0), x.size(2), x.size(3)
         y = torch.empty_like(x)
         with torch.cuda.device(x.device):
-            ws = st.workspace(model, cs, batch)
-            _lib.check(_lib.load().nd_utnet_train_forward(model.funit, _lib.ACT[model.activation], model.flags, st.flat.data_ptr(),
-                                                          st.blobs.data_ptr(), x.data_ptr(), y.data_ptr(), batch, cs, ws.data_ptr(),
-                                                          ws.numel(), _lib.stream_ptr(x.device)), "nd_utnet_train_forward")
+            ws = st.workspace(model, h, w, batch)
+            _lib.check(_lib.load().nd_utnet_train_forward_hw(model.funit, _lib.ACT[model.activation], model.flags,
+                                                             st.flat.data_ptr(), st.blobs.data_ptr(), x.data_ptr(), y.data_ptr(),
+                                                             batch, h, w, ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device)),
+                       "nd_utnet_train_forward_hw")
         st.generation += 1
-        ctx.model, ctx.names, ctx.geom, ctx.generation = model, names, (batch, cs), st.generation
+        ctx.model, ctx.names, ctx.geom, ctx.generation = model, names, (batch, h, w), st.generation
         ctx.shapes = [p.shape for p in params]
         return y
 
@@ -95,18 +97,21 @@ class _UtNetFunction(torch.autograd.Function):
         if st.generation != ctx.generation:
             raise RuntimeError("UtNet backward: another forward of this module ran under autograd since this graph was built; its "
                                "activations are gone (one forward/backward in flight per module -- as the reference's training loop runs)")
-        batch, cs = ctx.geom
+        batch, h, w = ctx.geom
+        want_dx, want_p = ctx.needs_input_grad[2], ctx.needs_input_grad[3:]
         gy = gy.to(torch.float32).contiguous()
+        dx = torch.empty(batch, 3, h, w, dtype=torch.float32, device=gy.device) if want_dx else None
         with torch.cuda.device(gy.device):
-            _lib.check(_lib.load().nd_utnet_train_backward(model.funit, _lib.ACT[model.activation], model.flags, st.flat.data_ptr(),
-                                                           st.grads.data_ptr(), st.blobs.data_ptr(), gy.data_ptr(), batch, cs,
-                                                           st.ws.data_ptr(), st.ws.numel(), _lib.stream_ptr(gy.device), None, 0),
-                       "nd_utnet_train_backward")
+            _lib.check(_lib.load().nd_utnet_train_backward_hw(model.funit, _lib.ACT[model.activation], model.flags,
+                                                              st.flat.data_ptr(), st.grads.data_ptr() if any(want_p) else None,
+                                                              st.blobs.data_ptr(), gy.data_ptr(), dx.data_ptr() if want_dx else None,
+                                                              batch, h, w, st.ws.data_ptr(), st.ws.numel(), _lib.stream_ptr(gy.device),
+                                                              None, 0), "nd_utnet_train_backward_hw")
         grads = []
-        for n, shape in zip(ctx.names, ctx.shapes):
+        for n, shape, want in zip(ctx.names, ctx.shapes, want_p):
             off, cnt = st.ranges[n]
-            grads.append(st.grads[off:off + cnt].view(shape).clone())
-        return (None, None, None) + tuple(grads)
+            grads.append(st.grads[off:off + cnt].view(shape).clone() if want else None)
+        return (None, None, dx) + tuple(grads)
 
 
 class UtNet(nn.Module):
@@ -249,18 +254,17 @@ class UtNet(nn.Module):
             if not valid_cs(cs):
                 raise ValueError(f"UtNet: tile size {cs} is not of the form 16k+56 (e.g. {nearest_valid_cs(cs)}); "
                                  "the reference network fails on it too")
-        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        trainable = self.training and any(p.requires_grad for p in self.parameters())
+        if torch.is_grad_enabled() and (trainable or (l.requires_grad and self.compute_dtype == "f32")):
             # the differentiable path: the reference trains through plain autograd (nn_common.py:146 `self.model.train()`,
-            # :198-218 forward / backward); an eval() module (nn_common.py:142, denoise_image.py:229) takes the inference path
-            # below, whose output carries no graph
-            if l.requires_grad:
-                raise NotImplementedError("UtNet: the gradient with respect to the input image is not produced by the HIP path")
-            if h != w:
-                raise ValueError(f"UtNet under autograd expects square crops, got {h}x{w}")
+            # :198-218 forward / backward).  It also serves an input that needs a gradient -- a frozen or eval() network as one
+            # differentiable stage of a larger graph -- and then builds the graph whatever the mode, as torch does.  An eval()
+            # module whose input needs no gradient (nn_common.py:142, denoise_image.py:229) takes the inference path below,
+            # whose output carries no graph
             if self.compute_dtype != "f32":
                 raise NotImplementedError("UtNet under autograd runs in fp32 (the training step's arithmetic)")
             named = [(n, p) for n, p in self.named_parameters()]
-            return _UtNetFunction.apply(self, tuple(n for n, _ in named), l.detach().to(torch.float32).contiguous(),
+            return _UtNetFunction.apply(self, tuple(n for n, _ in named), l.to(torch.float32).contiguous(),
                                         *[p for _, p in named])
         x = l.detach().to(torch.float32).contiguous()
         lib = _lib.load()

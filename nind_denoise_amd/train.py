@@ -66,17 +66,19 @@ class UtNetTrainer:
         # data parallel: the gradient mean runs bucket by bucket (one per network level) under the rest of the backward pass
         self.averager = BucketedGradientAverager(self.funit, self.grads, self.group)
 
-    def workspace(self, cs, batch):
-        key = (cs, batch)
+    def workspace(self, h, batch, w=None):
+        """Training workspace for [batch,3,h,w or h] crops (zero borders initialised once, then cached)."""
+        w = h if w is None else w
+        key = (h, w, batch)
         ws = self._ws.get(key)
         if ws is None:
-            nbytes = self.lib.nd_utnet_train_workspace_bytes(self.funit, cs, batch)
+            nbytes = self.lib.nd_utnet_train_workspace_bytes_hw(self.funit, h, w, batch)
             if nbytes == 0:
-                _lib.check(self.lib.nd_utnet_train_workspace_init(None, 0, self.funit, cs, batch, None), "UtNet training")
+                _lib.check(self.lib.nd_utnet_train_workspace_init_hw(None, 0, self.funit, h, w, batch, None), "UtNet training")
             self._ws.clear()
             ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(self.lib.nd_utnet_train_workspace_init(ws.data_ptr(), nbytes, self.funit, cs, batch,
-                                                              _lib.stream_ptr(self.device)), "nd_utnet_train_workspace_init")
+            _lib.check(self.lib.nd_utnet_train_workspace_init_hw(ws.data_ptr(), nbytes, self.funit, h, w, batch,
+                                                                 _lib.stream_ptr(self.device)), "nd_utnet_train_workspace_init_hw")
             self._ws[key] = ws
         return ws
 
@@ -84,21 +86,23 @@ class UtNetTrainer:
         """Forward + loss + backward; fills self.grads (averaged over the process group).  Returns (output, loss tensor)."""
         noisy = noisy.to(self.device, torch.float32).contiguous()
         clean = clean.to(self.device, torch.float32).contiguous()
-        if noisy.shape != clean.shape or noisy.dim() != 4 or noisy.size(1) != 3 or noisy.size(2) != noisy.size(3):
-            raise ValueError(f"expected two [B,3,S,S] batches, got {tuple(noisy.shape)} and {tuple(clean.shape)}")
-        batch, cs = noisy.size(0), noisy.size(2)
-        if not valid_cs(cs):
-            raise ValueError(f"crop size {cs} is not of the form 16k+56 (e.g. 136, 184)")
+        if noisy.shape != clean.shape or noisy.dim() != 4 or noisy.size(1) != 3:
+            raise ValueError(f"expected two [B,3,H,W] batches, got {tuple(noisy.shape)} and {tuple(clean.shape)}")
+        batch, h, w = noisy.size(0), noisy.size(2), noisy.size(3)
+        for cs in (h, w):
+            if not valid_cs(cs):
+                raise ValueError(f"crop side {cs} is not of the form 16k+56 (e.g. 136, 184)")
         y = torch.empty_like(noisy)
         with torch.cuda.device(self.device):
-            ws = self.workspace(cs, batch)
-            _lib.check(self.lib.nd_utnet_train_step_ev(self.funit, self.model.flags, self.flat.data_ptr(), self.grads.data_ptr(),
+            ws = self.workspace(h, batch, w)
+            # loss_cs: an L x L centre crop of the H x W output (pt_ops.pt_crop_batch), 0 = the whole output
+            _lib.check(self.lib.nd_utnet_train_step_hw(self.funit, self.model.flags, self.flat.data_ptr(), self.grads.data_ptr(),
                                                        self.blobs.data_ptr(), noisy.data_ptr(), clean.data_ptr(), y.data_ptr(),
                                                        float(self.weights.get("L1", 0.0)), float(self.weights.get("MSE", 0.0)),
                                                        float(self.weights.get("SSIM", 0.0)), float(self.weights.get("MSSSIM", 0.0)),
-                                                       self.loss.data_ptr(), batch, cs, int(self.loss_cs or 0), ws.data_ptr(), ws.numel(),
-                                                       _lib.stream_ptr(self.device), self.averager.event_ptrs, len(self.averager.buckets)),
-                       "nd_utnet_train_step_ev")
+                                                       self.loss.data_ptr(), batch, h, w, int(self.loss_cs or 0), ws.data_ptr(),
+                                                       ws.numel(), _lib.stream_ptr(self.device), self.averager.event_ptrs,
+                                                       len(self.averager.buckets)), "nd_utnet_train_step_hw")
             # RCCL: nine all-reduces (0.6 ... 57 MB for UtNet(64)), each behind its bucket's event on a side stream
             self.averager.reduce()
         return y, self.loss
