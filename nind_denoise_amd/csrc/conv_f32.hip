@@ -1,6 +1,4 @@
 // fp32 instantiations of the convolution kernel + variant table and launch code for every storage type
-#include <vector>
-
 #include "conv_qp.inc"
 
 // ------------------------------------------------------------------ variants and dispatch
@@ -96,11 +94,8 @@ static size_t variant_lds(const Variant &V, const QpBuf &in, bool *cross_out = n
 
 static const size_t kMaxLds = 160 * 1024;
 
-// ------------------------------------------------------------------ split-K tail
-// Persistent workgroups finish whole rounds of tiles at full rate, but the last, partial round leaves CUs idle (and a layer
-// with fewer tiles than CUs -- the deep levels of a small batch -- is nothing but a partial round).  The tiles of that
-// round are therefore cut along K into S slices that fill the idle CUs; slices store raw accumulators and this kernel adds
-// them in slice order (deterministic), then applies bias / activation exactly like the conv epilogue.
+// ------------------------------------------------------------------ split-K tail (launch.hip: nd_conv_schedule)
+// adds the K slices of a split tile in slice order (deterministic), then applies bias / activation exactly like the conv epilogue.
 // grid: (split tiles, MBLK/4 channel quads)
 __global__ __launch_bounds__(256) void k_split_finish(ConvParams p, int mblk, int nblk, int up, int dt) {
     const int t = blockIdx.x, quad = blockIdx.y;
@@ -165,50 +160,13 @@ __global__ __launch_bounds__(256) void k_split_finish(ConvParams p, int mblk, in
     }
 }
 
-// Time of a launch in units of "one workgroup runs one K chunk": `slots` workgroups run concurrently, `ntiles` tiles of
-// `nchunks` chunks each.  Picks the split of the partial round (S slices of cps chunks) that minimises it; kOver chunks
-// of fixed cost per work item (pipeline prologue, epilogue / partial store + its share of k_split_finish).
-struct SplitPlan { int first, S, cps; double time; };
-static SplitPlan plan_split(long ntiles, int nchunks, long slots, long max_items, double over) {
-    SplitPlan b;
-    const long full = ntiles / slots * slots, R = ntiles - full;
-    b.first = (int)ntiles;
-    b.S = 1;
-    b.cps = nchunks;
-    b.time = (double)((ntiles + slots - 1) / slots) * (nchunks + over);
-    if (R == 0 || max_items <= 0) return b;
-    const double base = (double)(full / slots) * (nchunks + over);
-    for (int S = 2; S <= nchunks && S <= 64; ++S) {
-        const int cps = (nchunks + S - 1) / S, Se = (nchunks + cps - 1) / cps;
-        if (R * Se > max_items) break;
-        const double t = base + (double)((R * Se + slots - 1) / slots) * (cps + 1.5 * over);
-        if (t < 0.93 * b.time) {
-            b.first = (int)full;
-            b.S = Se;
-            b.cps = cps;
-            b.time = t;
-        }
-    }
-    return b;
-}
-
-static std::atomic<int> g_num_cus{0};   // CU count of the device in use (every GPU of a node is the same part)
-static const double kSplitOver = 3.0;
-
-// max_items = 0 (no scratch, or ND_FLAG_NO_SPLITK on the call): never split
-void nd_plan_split(long ntiles, int nchunks, long slots, long max_items, int *first, int *S, int *cps) {
-    const SplitPlan sp = plan_split(ntiles, nchunks, slots, max_items, kSplitOver);
-    *first = sp.first;
-    *S = sp.S;
-    *cps = sp.cps;
-}
 int nd_launch_split_finish(const ConvParams &p, int n_split_tiles, int mblk, int nblk, int up, int dt, hipStream_t s) {
     hipLaunchKernelGGL(k_split_finish, dim3((unsigned)n_split_tiles, mblk / 4), dim3(256), 0, s, p, mblk, nblk, up, dt);
     ND_HIP(hipGetLastError());
     return ND_OK;
 }
 
-static int pick_variant(const ConvDesc &d, int M) {
+static int pick_variant(const ConvDesc &d, int M, int cus) {
     // (a region of interest shortens the rows of valid pixels: more row gaps per tile, a longer LDS halo image)
     const int Hr = d.roi_rows > 0 ? d.roi_rows : 0, Wr = d.roi_rows > 0 ? d.roi_cols : 0;
     const bool band2 = d.pool != nullptr;   // fused pool: 2-row band enumeration, a longer stage image
@@ -224,7 +182,6 @@ static int pick_variant(const ConvDesc &d, int M) {
             // against the CU count, so compare whole rounds.
             int Hv, Wv, st_;
             valid_grid(9, d.in, &Hv, &Wv, &st_);
-            const int cus = g_num_cus.load(std::memory_order_relaxed) > 0 ? g_num_cus.load(std::memory_order_relaxed) : 256;
             double best = 0;
             int best_v = -1;
             // (16-bit units re-measured in round 3, after the 16-byte epilogue stores, on every 3x3 layer of UtNet(64) at 160 tiles of 264:
@@ -243,7 +200,7 @@ static int pick_variant(const ConvDesc &d, int M) {
                 const long tn = cross ? ((long)d.in.B * pv + V.nblk - 1) / V.nblk : ((pv + V.nblk - 1) / V.nblk) * d.in.B;
                 const long tiles = tn * ((M + V.mblk - 1) / V.mblk);
                 const long cap = d.part && !d.nosplit && !band2 ? (long)(d.part_bytes / ((size_t)V.mblk * V.nblk * 4)) : 0;
-                const double cost = plan_split(tiles, KB / V.kbc, cus, cap, kSplitOver).time * V.nblk * c.unit;
+                const double cost = nd_conv_schedule_time(tiles, KB / V.kbc, cus, cap) * V.nblk * c.unit;
                 if (best_v < 0 || cost < best) {
                     best = cost;
                     best_v = c.v;
@@ -285,7 +242,9 @@ bool nd_conv_pool_fits(const ConvDesc &d) {
     // 0.842 -> 0.78 on the 128-pixel level, 0.621 -> 0.609 and 0.479 -> 0.480 below: the quad maxima, second rounding and pooled
     // stores cost the epilogue about what the separate kernel costs once the tensor is small -- fuse the large levels only
     if ((long)(d.in.Hb - 2) * (d.in.Wb - 2) < 100L * 100) return false;
-    const int v = pick_variant(d, d.cout);
+    int dev, cus;
+    if (nd_device(&dev, &cus) != ND_OK) return false;
+    const int v = pick_variant(d, d.cout, cus);
     if (v < 0 || v >= g_nvariants) return false;
     return variant_lds(variant_at(v), d.in, nullptr, nullptr, 0, 0, true) <= kMaxLds;
 }
@@ -294,12 +253,12 @@ bool nd_conv_pool_fits(const ConvDesc &d) {
 // buffer's rows puts many row gaps into the linear pixel range of an N tile)
 bool nd_conv_roi_fits(const ConvDesc &d) {
     const bool up = d.kind == ND_CONVT2S2;
-    const int v = pick_variant(d, up ? 4 * d.cout : d.cout);
+    int dev, cus;
+    if (nd_device(&dev, &cus) != ND_OK) return false;
+    const int v = pick_variant(d, up ? 4 * d.cout : d.cout, cus);
     if (v < 0 || v >= g_nvariants) return false;
     return variant_lds(variant_at(v), d.in, nullptr, nullptr, d.roi_rows > 0 ? d.roi_rows : 0, d.roi_rows > 0 ? d.roi_cols : 0) <= kMaxLds;
 }
-
-static std::atomic<int> g_lds_set[16][64];   // per device: function attributes belong to the device's copy of the code object
 
 int nd_launch_conv(const ConvDesc &d, hipStream_t stream) {
     const int taps = nd_taps(d.kind);
@@ -309,100 +268,49 @@ int nd_launch_conv(const ConvDesc &d, hipStream_t stream) {
     const int KB = nd_kblocks(d.cin, dt);
     const int M = up ? 4 * d.cout : d.cout;
     if (d.cout % nd_cpp(dt)) ND_FAIL(ND_EINVAL, "conv: cout=%d must be a multiple of %d", d.cout, nd_cpp(dt));
-    if (d.in.planes < d.in_plane0 + 2 * KB) ND_FAIL(ND_EINVAL, "conv: input buffer has %d planes, needs %d", d.in.planes, d.in_plane0 + 2 * KB);
-    const long NP = d.in.used();
-    if (NP >= (1L << 31)) ND_FAIL(ND_EINVAL, "conv: %ld linear pixels exceed the int32 index range", NP);
+    ND_TRY(nd_check_in_planes("conv", d, KB));
+    ND_TRY(nd_check_int32("conv", d.in));
 
     int dev = 0, ncus = 0;
-    ND_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16) ND_FAIL(ND_EINVAL, "conv: device index %d", dev);
-    ND_TRY(nd_num_cus(dev, &ncus));
-    g_num_cus.store(ncus, std::memory_order_relaxed);
-    int v = d.variant >= 0 ? d.variant : pick_variant(d, M);
+    ND_TRY(nd_device(&dev, &ncus));
+    int v = d.variant >= 0 ? d.variant : pick_variant(d, M, ncus);
     if (v < 0 || v >= g_nvariants) ND_FAIL(ND_EINVAL, "conv: unknown variant %d", v);
     const Variant &V = variant_at(v);
     if (V.taps != taps || V.up != up || V.dt != dt) ND_FAIL(ND_EINVAL, "conv: variant %s does not match layer kind %d / dtype %d", V.name, d.kind, dt);
     if (KB % V.kbc) ND_FAIL(ND_EINVAL, "conv: Cin/8=%d not a multiple of the variant's K chunk %d", KB, V.kbc);
 
-    ConvParams p = {};
-    p.in = (const f32x4 *)d.in.base + (long)d.in_plane0 * d.in.np();
-    p.wpk = d.wpk;
-    p.bias = d.bias;
-    p.out = (f32x4 *)d.out.base + (d.roi_rows > 0 ? (long)((up ? 2 : 1) * d.roi_r0) * d.out.Wb + (up ? 2 : 1) * d.roi_c0 : 0);
-    p.in_plane = d.in.np();
-    p.out_plane = d.out.np();
-    p.nimg = d.in.B;
-    p.P = d.in.Hb * d.in.Wb;
-    p.Wb = d.in.Wb;
+    ConvParams p = nd_conv_params(d, KB, M);
     valid_grid(taps, d.in, &p.Hv, &p.Wv, &p.stride);
     const bool roi = d.roi_rows > 0;
+    // region of the valid grid (of the INPUT grid for a 2x2 stride-2 transpose): same launch, shifted first pixel, smaller valid
+    // extents (the kernel takes the row / image strides from the buffer and the extents from Hv / Wv)
+    ND_TRY(nd_check_roi("conv", d, p.Hv, p.Wv, taps == 4 || d.nbatch > 1 || d.pre, "a stride-2, batched or training launch"));
     if (roi) {
-        // region of the valid grid (of the INPUT grid for a 2x2 stride-2 transpose): same launch, shifted first pixel, smaller valid
-        // extents (the kernel takes the row / image strides from the buffer and the extents from Hv / Wv)
-        if (taps == 4 || d.roi_r0 < 0 || d.roi_c0 < 0 || d.roi_cols < 1 || d.roi_r0 + d.roi_rows > p.Hv || d.roi_c0 + d.roi_cols > p.Wv || d.nbatch > 1 || d.pre)
-            ND_FAIL(ND_EINVAL, "conv: region [%d,+%d) x [%d,+%d) outside the %d x %d grid (or a batched / training launch)", d.roi_r0, d.roi_rows, d.roi_c0, d.roi_cols, p.Hv, p.Wv);
+        p.out += (long)((up ? 2 : 1) * d.roi_r0) * d.out.Wb + (up ? 2 : 1) * d.roi_c0;
         p.Hv = d.roi_rows;
         p.Wv = d.roi_cols;
     }
     p.PV = p.Hv * p.Wv;
     if (taps == 4 && ((d.in.Hb | d.in.Wb) & 1)) ND_FAIL(ND_EINVAL, "conv: the stride-2 layer reads even-sized buffers only");
     p.ioff = (taps == 9 ? 0 : d.in.pad * d.in.Wb + d.in.pad) + (roi ? d.roi_r0 * d.in.Wb + d.roi_c0 : 0);
-    p.pre = (f32x4 *)d.pre;
-    p.pre_plane = d.pre_plane;
     if (d.pre && (dt != ND_F32 || up)) ND_FAIL(ND_EINVAL, "conv: the pre-activation copy exists for fp32 non-upsampling layers only");
-    p.KB = KB;
-    p.M = M;
-    p.cout = d.cout;
-    p.Po = d.out.Hb * d.out.Wb;
-    p.Wo = d.out.Wb;
-    p.opad = d.out.pad;
-    p.out_plane0 = d.out_plane0;
-    p.act = d.act;
-    p.slope = d.slope;
-    p.slope_dev = d.slope_dev;
-
-    // destination geometry must hold the result
-    const int oh = up ? 2 * p.Hv : p.Hv, ow = up ? 2 * p.Wv : p.Wv;
-    // (a 2x2 stride-2 result may be smaller than its destination: UNet's F.pad fix-up for odd sizes, ThirdPartyNets.py:110-118)
-    const bool fits = (up || roi) ? (d.out.Hb >= oh + 2 * d.out.pad && d.out.Wb >= ow + 2 * d.out.pad)
-                                  : (d.out.Hb == oh + 2 * d.out.pad && d.out.Wb == ow + 2 * d.out.pad);
-    if (!fits || d.out.B != d.in.B)
-        ND_FAIL(ND_EINVAL, "conv: destination %dx%dx%d(pad %d) does not fit result %dx%dx%d", d.out.B, d.out.Hb, d.out.Wb,
-                d.out.pad, d.in.B, oh, ow);
-    if (d.out_plane0 + d.cout / nd_cpp(dt) > d.out.planes) ND_FAIL(ND_EINVAL, "conv: destination planes overflow");
+    // destination geometry must hold the result (a 2x2 stride-2 result may be smaller than its destination: UNet's F.pad fix-up for
+    // odd sizes, ThirdPartyNets.py:110-118)
+    ND_TRY(nd_check_out("conv", d, up ? 2 * p.Hv : p.Hv, up ? 2 * p.Wv : p.Wv, up || roi));
 
     // fused MaxPool2d(2) (16-bit storage): 2-row band enumeration of the pixels, pooled tensor written from the epilogue
     if (d.pool) {
-        const QpBuf &q = *d.pool;
         if (dt == ND_F32 || taps != 9 || up || roi || d.pre || d.nbatch > 1 || (p.Hv & 1) || (p.Wv & 1))
             ND_FAIL(ND_EINVAL, "conv: a fused pool needs a whole 16-bit 3x3 layer with even output sizes (got %d x %d, dtype %d)", p.Hv, p.Wv, dt);
-        if (q.dt != dt || q.B != d.in.B || q.Hb - 2 * q.pad != p.Hv / 2 || q.Wb - 2 * q.pad != p.Wv / 2 || q.planes < d.cout / nd_cpp(dt))
-            ND_FAIL(ND_EINVAL, "conv: pooled destination does not fit %d x %d x %d", d.cout, p.Hv / 2, p.Wv / 2);
-        p.pool = (f32x4 *)q.base;
-        p.pool_plane = q.np();
-        p.pool_P = q.Hb * q.Wb;
-        p.pool_W = q.Wb;
-        p.pool_pad = q.pad;
+        ND_TRY(nd_conv_pool("conv", d, p.Hv, p.Wv, p));
         p.band2 = 1;
     }
     bool cross = true;
     const size_t lds = variant_lds(V, d.in, &cross, &p.G, roi ? p.Hv : 0, roi ? p.Wv : 0, p.band2 != 0);
     if (lds > kMaxLds) ND_FAIL(ND_EINVAL, "conv: %zu B of LDS needed (row width %d too large for variant %s)", lds, p.Wb, V.name);
-    if ((int)lds > g_lds_set[dev][v].load(std::memory_order_relaxed)) {
-        ND_HIP(hipFuncSetAttribute((const void *)V.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        g_lds_set[dev][v].store((int)lds, std::memory_order_relaxed);
-    }
+    ND_TRY(nd_raise_lds(dev, (const void *)V.fn, lds));
 
-    if (cross) {
-        p.tpi = 0;
-        p.n_tiles_n = (int)(((long)p.nimg * p.PV + V.nblk - 1) / V.nblk);
-    } else {
-        p.tpi = (p.PV + V.nblk - 1) / V.nblk;
-        p.n_tiles_n = p.tpi * p.nimg;
-    }
-    p.n_tiles_m = (M + V.mblk - 1) / V.mblk;
-    p.tiles_per_problem = p.n_tiles_n * p.n_tiles_m;
-    p.wpx = 0;
+    nd_conv_tiles(p, cross, V.nblk, V.mblk);
     // gap-free 1-tap launch with raw output (the Winograd GEMMs): see ConvParams::linear
     p.linear = taps == 1 && !up && dt == ND_F32 && d.in.pad == 0 && d.out.pad == 0 && d.out.Hb == d.in.Hb && d.out.Wb == d.in.Wb && cross &&
                d.act == ND_ACT_NONE && d.nbatch > 1 && !d.pre && !roi;
@@ -417,13 +325,8 @@ int nd_launch_conv(const ConvDesc &d, hipStream_t stream) {
     const long slots = (long)ncus * per_cu;
     // (a layer that pools keeps its tiles whole: the split-K finish kernel sees no neighbours)
     const long cap = d.part && !d.nosplit && !p.band2 ? (long)(d.part_bytes / ((size_t)V.mblk * V.nblk * 4)) : 0;
-    const SplitPlan sp = plan_split(ntiles, KB / V.kbc, slots, cap, kSplitOver);
-    p.split_first = sp.first;
-    p.S = sp.S;
-    p.cps = sp.cps;
-    p.nitems = (int)(sp.first + (ntiles - sp.first) * sp.S);
+    const long grid = nd_conv_schedule(p, ntiles, KB / V.kbc, slots, cap);
     p.part = (f32x4 *)d.part;
-    const long grid = p.nitems < slots ? p.nitems : slots;
 #ifdef ND_QP_ABLATE
     static const int abl_env = getenv("ND_QP_ABL") ? atoi(getenv("ND_QP_ABL")) : 0;   // make ABLATE=1: see fill_slice / epilogue
     p.dbg = abl_env;
@@ -431,42 +334,18 @@ int nd_launch_conv(const ConvDesc &d, hipStream_t stream) {
 #ifdef ND_QP_STAMPS
     static const int dbg_env = getenv("ND_QP_DBG") ? atoi(getenv("ND_QP_DBG")) : 0;
     if (dbg_env & 128) {
-        // stamped diagnostic launch: no split-K (p.part carries the stamp buffer), synchronous, prints the phase split of two waves
-        static unsigned long long *buf = nullptr;
-        const size_t n = (size_t)slots * 8 * 8;
-        if (!buf) ND_HIP(hipMalloc(&buf, n * 8));
-        ND_HIP(hipMemsetAsync(buf, 0, n * 8, stream));
-        p.dbg = dbg_env;
-        p.split_first = (int)ntiles; p.S = 1; p.cps = KB / V.kbc; p.nitems = (int)ntiles; p.part = (f32x4 *)buf;
-        const long g2 = ntiles < slots ? ntiles : slots;
-        hipLaunchKernelGGL(V.fn, dim3((unsigned)g2), dim3(V.threads), lds, stream, p);
-        ND_HIP(hipStreamSynchronize(stream));
+        // stamped diagnostic launch: prints the phase split of the first and the last wave
         static int printed = 0;
-        if (printed++ < 40) {
-            std::vector<unsigned long long> h(n);
-            ND_HIP(hipMemcpy(h.data(), buf, n * 8, hipMemcpyDeviceToHost));
-            const char *names[5] = {"barrier", "issue DMA", "MFMA loop", "wait vmcnt", "epilogue+next"};
-            fprintf(stderr, "[qp stamps] %s cin %d M %d tiles %ld chunks %d G %d\n", V.name, d.cin, M, ntiles, KB / V.kbc, p.G);
-            for (int w : {0, V.threads / 64 - 1}) {
-                double tot[5] = {0}, steps = 0;
-                for (long b = 0; b < g2; ++b) {
-                    for (int k = 0; k < 5; ++k) tot[k] += (double)h[((size_t)b * 8 + w) * 8 + k];
-                    steps += (double)h[((size_t)b * 8 + w) * 8 + 6];
-                }
-                double sum = 0;
-                for (int k = 0; k < 5; ++k) sum += tot[k];
-                fprintf(stderr, "   wave %d: %.0f cycles/step:", w, sum / steps);
-                for (int k = 0; k < 5; ++k) fprintf(stderr, "  %s %.0f (%.1f%%)", names[k], tot[k] / steps, 100 * tot[k] / sum);
-                fprintf(stderr, "\n");
-            }
-        }
-        return ND_OK;
+        static const char *const names[5] = {"barrier", "issue DMA", "MFMA loop", "wait vmcnt", "epilogue+next"};
+        char header[160];
+        snprintf(header, sizeof header, "[qp stamps] %s cin %d M %d tiles %ld chunks %d G %d", V.name, d.cin, M, ntiles, KB / V.kbc, p.G);
+        p.dbg = dbg_env;
+        return nd_stamped_launch(V.fn, V.threads, lds, p, ntiles, KB / V.kbc, slots, stream, printed++ < 40, header, "   wave", names, 5,
+                                 {0, V.threads / 64 - 1});
     }
 #endif
     hipLaunchKernelGGL(V.fn, dim3((unsigned)grid), dim3(V.threads), lds, stream, p);
-    if (sp.first < ntiles)
-        hipLaunchKernelGGL(k_split_finish, dim3((unsigned)(ntiles - sp.first), V.mblk / 4), dim3(256), 0, stream, p, V.mblk,
-                           V.nblk, up ? 1 : 0, dt);
     ND_HIP(hipGetLastError());
+    if (p.split_first < ntiles) ND_TRY(nd_launch_split_finish(p, (int)(ntiles - p.split_first), V.mblk, V.nblk, up ? 1 : 0, dt, stream));
     return ND_OK;
 }

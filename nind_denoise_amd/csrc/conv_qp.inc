@@ -35,6 +35,7 @@
 // Workgroup ids are remapped so that the 32 workgroups sharing an XCD (and its L2) walk adjacent tiles.
 #include <stdlib.h>
 
+#include <initializer_list>
 #include <type_traits>
 
 #include "nd_common.h"
@@ -134,9 +135,27 @@ static inline void nd_conv_fastdivs(ConvParams &p) {
     p.fd_tpi = nd_fastdiv(p.tpi > 0 ? p.tpi : 1);
 }
 
+// ------------------------------------------------------------------ host side of the launchers (launch.hip)
+// the fields every launcher sets the same way from the layer: input / destination pointers and geometry, pre-activation copy, K
+// blocks, M rows, activation.  The launcher adds its valid grid (Hv, Wv, PV, wpx), G, stride, ioff, region shifts and schedule
+ConvParams nd_conv_params(const ConvDesc &d, int KB, int M);
+// fused MaxPool2d(2) of an Hv x Wv output into *d.pool (checked against it)
+int nd_conv_pool(const char *who, const ConvDesc &d, int Hv, int Wv, ConvParams &p);
+// tile counts: N tiles of nblk valid pixels (or groups) over the whole batch when tiles may cross images (tpi = 0), else tpi
+// tiles per image; M tiles of mblk rows
+void nd_conv_tiles(ConvParams &p, bool cross, int nblk, int mblk);
+// persistent-grid schedule of ntiles tiles of nchunks K chunks on `slots` concurrent workgroups, with split-K scratch for `cap`
+// work items (0: never split): sets split_first / S / cps / nitems and returns the grid
+long nd_conv_schedule(ConvParams &p, long ntiles, int nchunks, long slots, long cap);
+double nd_conv_schedule_time(long ntiles, int nchunks, long slots, long cap);   // its length in "one workgroup, one K chunk" units
 // shared with conv_w1d.hip (defined in conv_f32.hip)
-void nd_plan_split(long ntiles, int nchunks, long slots, long max_items, int *first, int *S, int *cps);
 int nd_launch_split_finish(const ConvParams &p, int n_split_tiles, int mblk, int nblk, int up, int dt, hipStream_t s);
+#ifdef ND_QP_STAMPS
+// diagnostic build (make STAMPS=1): the launch without split-K, p.part carrying the stamp buffer ([workgroup][wave][phases, -,
+// steps]), synchronous; if `print`, the header line and, per wave of `waves`, each phase's cycles per step
+int nd_stamped_launch(void (*fn)(ConvParams), int threads, size_t lds, ConvParams p, long ntiles, int nchunks, long slots, hipStream_t s,
+                      bool print, const char *header, const char *wave_prefix, const char *const *names, int nphases, std::initializer_list<int> waves);
+#endif
 
 __device__ __forceinline__ void glds16(const void *g, void *l) {
     // 64 lanes x 16 B: per-lane global source, LDS destination = wave-uniform base + lane*16

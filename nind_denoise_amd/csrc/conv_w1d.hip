@@ -353,7 +353,7 @@ size_t w1d_lds(const W1Shape &sh, int G) { return (size_t)kW1dStages * ((size_t)
 
 // packed layout: [32-row tile][K block][3 * (T+2) planes = ky*(T+2) + xi][lane][4] + bias[mtiles*32]   (as pack.hip)
 size_t nd_w1d_packed_floats(int T, int cin, int cout) {
-    return (size_t)nd_mtiles(ND_CONV3, cout) * nd_kblocks(cin) * 3 * (T + 2) * 256 + (size_t)nd_mtiles(ND_CONV3, cout) * 32;
+    return nd_bias_offset(ND_CONV3, cin, cout, ND_F32, T) + (size_t)nd_mtiles(ND_CONV3, cout) * 32;
 }
 
 int nd_w1d_pack(int T, int kind, int cin, int cout, const float *w, const float *bias, float *packed) {
@@ -376,7 +376,7 @@ int nd_w1d_pack(int T, int kind, int cin, int cout, const float *w, const float 
                         for (int xi = 0; xi < NP; ++xi)
                             packed[(((size_t)mt * KB + kb) * 3 * NP + ky * NP + xi) * 256 + lane * 4 + e] = (float)u[xi];
                     }
-    float *b = packed + (size_t)MT * KB * 3 * NP * 256;
+    float *b = packed + nd_bias_offset(ND_CONV3, cin, cout, ND_F32, T);
     for (int i = 0; i < MT * 32; ++i) b[i] = (bias && i < cout) ? bias[i] : 0.f;
     return ND_OK;
 }
@@ -407,38 +407,22 @@ int nd_launch_conv_w1d(int T, const ConvDesc &d, hipStream_t stream) {
     if (d.cout % 4) ND_FAIL(ND_EINVAL, "w1d: cout must be a multiple of 4");
     const W1Shape &sh = shape_of(T);
     const int KB = nd_kblocks(d.cin);
-    if (d.in.planes < d.in_plane0 + 2 * KB) ND_FAIL(ND_EINVAL, "w1d: input buffer has %d planes, needs %d", d.in.planes, d.in_plane0 + 2 * KB);
+    ND_TRY(nd_check_in_planes("w1d", d, KB));
     const int Hv = d.in.Hb - 2, Wpx = d.in.Wb - 2, Wg = (Wpx + T - 1) / T;
     if (Hv < 1 || Wpx < 1) ND_FAIL(ND_EINVAL, "w1d: input smaller than the kernel");
-    if (d.out.Hb != Hv + 2 * d.out.pad || d.out.Wb != Wpx + 2 * d.out.pad || d.out.B != d.in.B) ND_FAIL(ND_EINVAL, "w1d: destination does not fit the result");
-    if (d.out_plane0 + d.cout / 4 > d.out.planes) ND_FAIL(ND_EINVAL, "w1d: destination planes overflow");
-    if (d.in.used() >= (1L << 31)) ND_FAIL(ND_EINVAL, "w1d: input too large for int32 indexing");
+    ND_TRY(nd_check_out("w1d", d, Hv, Wpx, false));
+    ND_TRY(nd_check_int32("w1d", d.in));
 
-    static std::atomic<int> lds_set[16][2];
     int dev = 0, ncus = 0;
-    ND_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16) ND_FAIL(ND_EINVAL, "w1d: device index %d", dev);
-    ND_TRY(nd_num_cus(dev, &ncus));
+    ND_TRY(nd_device(&dev, &ncus));
     bool cross;
     size_t lds;
     const int G = w1d_geometry(sh, d.in, &cross, &lds);
     if (lds > 160 * 1024) ND_FAIL(ND_EINVAL, "w1d: %zu B of LDS needed (row width %d too large)", lds, d.in.Wb);
     void (*fn)(ConvParams) = T == 4 ? conv_w1d<4, 1, 2, 4, kW1dStages> : conv_w1d<2, 2, 1, 8, kW1dStages>;
-    if ((int)lds > lds_set[dev][T == 4].load(std::memory_order_relaxed)) {
-        ND_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        lds_set[dev][T == 4].store((int)lds, std::memory_order_relaxed);
-    }
+    ND_TRY(nd_raise_lds(dev, (const void *)fn, lds));
 
-    ConvParams p = {};
-    p.in = (const f32x4 *)d.in.base + (long)d.in_plane0 * d.in.np();
-    p.wpk = d.wpk;
-    p.bias = d.bias;
-    p.out = (f32x4 *)d.out.base;
-    p.in_plane = d.in.np();
-    p.out_plane = d.out.np();
-    p.nimg = d.in.B;
-    p.P = d.in.Hb * d.in.Wb;
-    p.Wb = d.in.Wb;
+    ConvParams p = nd_conv_params(d, KB, d.cout);
     p.Hv = Hv;
     p.Wv = Wg;              // groups per row
     p.PV = Hv * Wg;         // groups per image
@@ -446,47 +430,20 @@ int nd_launch_conv_w1d(int T, const ConvDesc &d, hipStream_t stream) {
     p.G = G;
     p.stride = 1;
     p.ioff = 0;
-    p.pre = (f32x4 *)d.pre;
-    p.pre_plane = d.pre_plane;
-    p.KB = KB;
-    p.M = d.cout;
-    p.cout = d.cout;
-    p.Po = d.out.Hb * d.out.Wb;
-    p.Wo = d.out.Wb;
-    p.opad = d.out.pad;
-    p.out_plane0 = d.out_plane0;
-    p.act = d.act;
-    p.slope = d.slope;
-    p.slope_dev = d.slope_dev;
-    if (cross) {
-        p.tpi = 0;
-        p.n_tiles_n = (int)(((long)p.nimg * p.PV + sh.groups - 1) / sh.groups);
-    } else {
-        p.tpi = (p.PV + sh.groups - 1) / sh.groups;
-        p.n_tiles_n = p.tpi * p.nimg;
-    }
-    p.n_tiles_m = (d.cout + sh.mblk - 1) / sh.mblk;
-    p.tiles_per_problem = p.n_tiles_n * p.n_tiles_m;
+    nd_conv_tiles(p, cross, sh.groups, sh.mblk);
     const long ntiles = p.tiles_per_problem;
-    const long slots = ncus;
     const long cap = d.part && !d.nosplit ? (long)(d.part_bytes / ((size_t)sh.mblk * T * sh.groups * 4)) : 0;
-    int first, S, cps;
-    nd_plan_split(ntiles, KB, slots, cap, &first, &S, &cps);
-    p.split_first = first;
-    p.S = S;
-    p.cps = cps;
-    p.nitems = (int)(first + (ntiles - first) * S);
+    const long grid = nd_conv_schedule(p, ntiles, KB, ncus, cap);
     p.part = (f32x4 *)d.part;
-    const long grid = p.nitems < slots ? p.nitems : slots;
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(sh.threads), lds, stream, p);
-    if (first < ntiles) {
+    ND_HIP(hipGetLastError());
+    if (p.split_first < ntiles) {
         // the finish kernel works in pixel slots: a tile of n groups is T*n consecutive slots of rows T*Wg slots wide
         // (slots past the real row width are skipped: ConvParams::wpx)
         ConvParams f = p;
         f.Wv = T * Wg;
         f.PV = Hv * T * Wg;
-        ND_TRY(nd_launch_split_finish(f, (int)(ntiles - first), sh.mblk, T * sh.groups, 0, ND_F32, stream));
+        ND_TRY(nd_launch_split_finish(f, (int)(ntiles - p.split_first), sh.mblk, T * sh.groups, 0, ND_F32, stream));
     }
-    ND_HIP(hipGetLastError());
     return ND_OK;
 }

@@ -16,8 +16,6 @@
 //     conflict-free: V rows are padded to 20 slots so that the 16 lanes of a read group hit 16 different bank quads), 4 MFMAs.
 // Weights: the conv_w1d packing [32-row tile][K block][ky*6 + position][lane][4], staged by LDS-DMA, two stages; V: two stages;
 // one barrier per K step.  Split-K tail and persistent XCD-aware workgroups as in conv_qp.inc.
-#include <vector>
-
 #include "conv_qp.inc"
 
 namespace {
@@ -549,27 +547,21 @@ int nd_launch_conv_w2d(const ConvDesc &d, hipStream_t stream) {
     const int KB = nd_kblocks(d.cin);
     const int Hfull = d.in.Hb - 2, Wfull = d.in.Wb - 2;
     if (Hfull < 1 || Wfull < 1) ND_FAIL(ND_EINVAL, "w2d: input smaller than the kernel");
-    const bool roi = d.roi_rows > 0;
-    if (roi && (d.roi_r0 < 0 || d.roi_c0 < 0 || d.roi_cols < 1 || d.roi_r0 + d.roi_rows > Hfull || d.roi_c0 + d.roi_cols > Wfull || d.pool))
-        ND_FAIL(ND_EINVAL, "w2d: region [%d,+%d) x [%d,+%d) outside the %d x %d output (or a pooled layer)", d.roi_r0, d.roi_rows, d.roi_c0, d.roi_cols, Hfull, Wfull);
+    ND_TRY(nd_check_roi("w2d", d, Hfull, Wfull, d.pool != nullptr, "a pooled layer"));
     // (a region is the same launch on shifted base pointers: the kernel knows row / image strides and valid extents separately)
+    const bool roi = d.roi_rows > 0;
     const int Hv = roi ? d.roi_rows : Hfull, Wpx = roi ? d.roi_cols : Wfull, Wg = (Wpx + 3) / 4, NB = (Hv + kR - 1) / kR;
-    const long roi_in = roi ? (long)d.roi_r0 * d.in.Wb + d.roi_c0 : 0, roi_out = roi ? (long)d.roi_r0 * d.out.Wb + d.roi_c0 : 0;
-    if (d.pre && (d.roi_rows > 0 || d.pool)) ND_FAIL(ND_EINVAL, "w2d: a pre-activation copy goes with whole, unpooled layers only");
+    if (d.pre && (roi || d.pool)) ND_FAIL(ND_EINVAL, "w2d: a pre-activation copy goes with whole, unpooled layers only");
     if (d.cout % 4) ND_FAIL(ND_EINVAL, "w2d: cout must be a multiple of 4");
-    if (d.in.planes < d.in_plane0 + 2 * KB) ND_FAIL(ND_EINVAL, "w2d: input buffer has %d planes, needs %d", d.in.planes, d.in_plane0 + 2 * KB);
-    if (d.out.Hb != Hfull + 2 * d.out.pad || d.out.Wb != Wfull + 2 * d.out.pad || d.out.B != d.in.B) ND_FAIL(ND_EINVAL, "w2d: destination does not fit the result");
-    if (d.out_plane0 + d.cout / 4 > d.out.planes) ND_FAIL(ND_EINVAL, "w2d: destination planes overflow");
+    ND_TRY(nd_check_in_planes("w2d", d, KB));
+    ND_TRY(nd_check_out("w2d", d, Hfull, Wfull, false));
     // a lane's float4 index inside a K block's two-plane window is 32 bits; strips of the last band / group read up to 9 rows + 5
     // pixels past the last valid pixel (the buffers carry that slack)
-    if (2 * d.in.np() * 16 + 65536 >= (1L << 32) || d.in.used() >= (1L << 31)) ND_FAIL(ND_EINVAL, "w2d: input too large for 32-bit byte offsets");
+    ND_TRY(nd_check_int32("w2d", d.in));
+    if (2 * d.in.np() * 16 + 65536 >= (1L << 32)) ND_FAIL(ND_EINVAL, "w2d: input too large for 32-bit byte offsets");
 
-    static std::atomic<int> lds_set[16];
     int dev = 0, ncus = 0;
-    ND_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16) ND_FAIL(ND_EINVAL, "w2d: device index %d", dev);
-    ND_TRY(nd_num_cus(dev, &ncus));
-    const int lds = kLds;
+    ND_TRY(nd_device(&dev, &ncus));
     void (*fn)(ConvParams) = conv_w2d<0>;
 #ifdef ND_QP_STAMPS
     // diagnostic build only (make STAMPS=1; tools/w2d_ablate.sh): ND_W2D_DBG names one of the ablation masks / the stamped kernel
@@ -589,106 +581,50 @@ int nd_launch_conv_w2d(const ConvDesc &d, hipStream_t stream) {
         case 256: fn = conv_w2d<256>; break;
         default: break;
     }
-#else
-    constexpr int dbg_env = 0;
 #endif
-    if (lds_set[dev].load(std::memory_order_relaxed) != dbg_env + 1) {
-        ND_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-        lds_set[dev].store(dbg_env + 1, std::memory_order_relaxed);
-    }
+    ND_TRY(nd_raise_lds(dev, (const void *)fn, kLds));
 
-    ConvParams p = {};
-    p.in = (const f32x4 *)d.in.base + (long)d.in_plane0 * d.in.np() + roi_in;
-    p.wpk = d.wpk;
-    p.bias = d.bias;
-    p.out = (f32x4 *)d.out.base + roi_out;
-    p.in_plane = d.in.np();
-    p.out_plane = d.out.np();
-    p.nimg = d.in.B;
-    p.P = d.in.Hb * d.in.Wb;
-    p.Wb = d.in.Wb;
+    ConvParams p = nd_conv_params(d, KB, d.cout);
+    if (roi) {
+        p.in += (long)d.roi_r0 * d.in.Wb + d.roi_c0;
+        p.out += (long)d.roi_r0 * d.out.Wb + d.roi_c0;
+    }
     p.Hv = Hv;
     p.Wv = Wg;               // groups per row
     p.PV = NB * Wg;          // strips per image
     p.wpx = Wpx;             // valid pixels per row
-    p.pre = (f32x4 *)d.pre;
-    p.pre_plane = d.pre_plane;
-    p.KB = KB;
-    p.M = d.cout;
-    p.cout = d.cout;
-    p.Po = d.out.Hb * d.out.Wb;
-    p.Wo = d.out.Wb;
-    p.opad = d.out.pad;
-    p.out_plane0 = d.out_plane0;
-    p.act = d.act;
-    p.slope = d.slope;
-    p.slope_dev = d.slope_dev;
     if (d.pool) {
-        const QpBuf &q = *d.pool;
-        if (q.dt != ND_F32 || q.B != d.in.B || q.Hb - 2 * q.pad != Hv / 2 || q.Wb - 2 * q.pad != Wpx / 2 || q.planes < d.cout / 4)
-            ND_FAIL(ND_EINVAL, "w2d: pooled destination does not fit %dx%dx%d", d.cout, Hv / 2, Wpx / 2);
-        if (q.used() * 16 >= (1L << 32)) ND_FAIL(ND_EINVAL, "w2d: pooled destination too large for 32-bit byte offsets");
-        p.pool = (f32x4 *)q.base;
-        p.pool_plane = q.np();
-        p.pool_P = q.Hb * q.Wb;
-        p.pool_W = q.Wb;
-        p.pool_pad = q.pad;
+        ND_TRY(nd_conv_pool("w2d", d, Hv, Wpx, p));
+        if (d.pool->used() * 16 >= (1L << 32)) ND_FAIL(ND_EINVAL, "w2d: pooled destination too large for 32-bit byte offsets");
     }
-    p.n_tiles_n = (int)(((long)p.nimg * p.PV + kS - 1) / kS);
-    p.n_tiles_m = (d.cout + kMTB * 32 - 1) / (kMTB * 32);
-    p.tiles_per_problem = p.n_tiles_n * p.n_tiles_m;
+    nd_conv_tiles(p, true, kS, kMTB * 32);   // strips are enumerated over the whole batch
     nd_conv_fastdivs(p);
     const long ntiles = p.tiles_per_problem;
-    const long slots = ncus;
     // (a layer with a fused pool or a pre-activation copy keeps every tile whole: the split-K finish kernel has no view of a tile's
     //  2x2 neighbours and writes no copy -- the training step sends layers with few tiles through conv_w1d, which splits)
     const long cap = d.part && !d.nosplit && !d.pool && !d.pre ? (long)(d.part_bytes / ((size_t)kMTB * 32 * kSlots * 4)) : 0;
-    int first, S, cps;
-    nd_plan_split(ntiles, KB, slots, cap, &first, &S, &cps);
-    p.split_first = first;
-    p.S = S;
-    p.cps = cps;
-    p.nitems = (int)(first + (ntiles - first) * S);
+    const long grid = nd_conv_schedule(p, ntiles, KB, ncus, cap);
     p.part = (f32x4 *)d.part;
-    const long grid = p.nitems < slots ? p.nitems : slots;
 #ifdef ND_QP_STAMPS
     if (dbg_env == 128) {
-        // stamped diagnostic launch: no split-K (p.part carries the stamp buffer), synchronous, prints the phase split per wave role
-        static unsigned long long *buf = nullptr;
-        const size_t n = (size_t)slots * 8 * 8;
-        if (!buf) ND_HIP(hipMalloc(&buf, n * 8));
-        ND_HIP(hipMemsetAsync(buf, 0, n * 8, stream));
-        p.split_first = (int)ntiles;
-        p.S = 1;
-        p.cps = KB;
-        p.nitems = (int)ntiles;
-        p.part = (f32x4 *)buf;
-        const long g2 = ntiles < slots ? ntiles : slots;
-        hipLaunchKernelGGL(fn, dim3((unsigned)g2), dim3(512), lds, stream, p);
-        ND_HIP(hipStreamSynchronize(stream));
+        // stamped diagnostic launch: prints the phase split per wave role
         static int printed = 0;
-        if (printed++ < 2) {
-            std::vector<unsigned long long> h(n);
-            ND_HIP(hipMemcpy(h.data(), buf, n * 8, hipMemcpyDeviceToHost));
-            const char *names[6] = {"issue loads + DMA", "MFMA loop", "wait vmcnt", "transform+publish (inside the loop)", "epilogue", "barrier"};
-            for (int w : {0, 1, 4}) {
-                double tot[6] = {0}, steps = 0;
-                for (long b = 0; b < g2; ++b) {
-                    for (int k = 0; k < 6; ++k) tot[k] += (double)h[((size_t)b * 8 + w) * 8 + k];
-                    steps += (double)h[((size_t)b * 8 + w) * 8 + 6];
-                }
-                double sum = 0;
-                for (int k = 0; k < 6; ++k) sum += tot[k];
-                fprintf(stderr, "[w2d stamps] wave %d: %.0f cycles/step:", w, sum / steps);
-                for (int k = 0; k < 6; ++k) fprintf(stderr, "  %s %.0f (%.1f%%)", names[k], tot[k] / steps, 100 * tot[k] / sum);
-                fprintf(stderr, "\n");
-            }
-        }
-        return ND_OK;
+        static const char *const names[6] = {"issue loads + DMA", "MFMA loop", "wait vmcnt", "transform+publish (inside the loop)", "epilogue", "barrier"};
+        return nd_stamped_launch(fn, 512, kLds, p, ntiles, KB, ncus, stream, printed++ < 2, nullptr, "[w2d stamps] wave", names, 6, {0, 1, 4});
     }
 #endif
-    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(512), lds, stream, p);
-    if (first < ntiles) hipLaunchKernelGGL(k_w2d_split_finish, dim3((unsigned)(ntiles - first), kMTB * 8), dim3(256), 0, stream, p);
+    hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(512), kLds, stream, p);
+    if (p.split_first < ntiles) hipLaunchKernelGGL(k_w2d_split_finish, dim3((unsigned)(ntiles - p.split_first), kMTB * 8), dim3(256), 0, stream, p);
     ND_HIP(hipGetLastError());
     return ND_OK;
+}
+
+// conv_w2d takes an F(4,3) layer unless ND_FLAG_W1D_REGS asks for conv_w1d or the buffer does not suit it.  A layer that keeps its
+// pre-activation copy (training forward) is never split along K in conv_w2d: it goes there only with tiles for two rounds of
+// workgroups, else to conv_w1d, which splits
+bool nd_f43_w2d(const QpBuf &in, int cout, bool pre, int flags) {
+    return !(flags & ND_FLAG_W1D_REGS) && nd_w2d_ok(in) && (!pre || nd_w2d_tiles(in, cout) >= 512);
+}
+int nd_launch_conv_f43(const ConvDesc &d, int flags, hipStream_t stream) {
+    return nd_f43_w2d(d.in, d.cout, d.pre != nullptr, flags) ? nd_launch_conv_w2d(d, stream) : nd_launch_conv_w1d(4, d, stream);
 }

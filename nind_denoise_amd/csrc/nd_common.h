@@ -2,7 +2,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -51,17 +50,17 @@ struct QpBuf {
 
 // ------------------------------------------------------------------ one conv launch
 struct ConvDesc {
-    int kind;           // nd_layer_kind
-    int act;            // nd_act
-    float slope;        // PReLU slope (used when slope_dev is null)
-    const float *slope_dev;  // PReLU slope in HBM (the packed blob), or null
-    const float *wpk;   // packed weights [mtile][kb][tap][64 lanes][4]
-    const float *bias;  // [mtiles*32]
-    int cin, cout;      // logical channels (cin is padded to 8 in the buffers)
-    QpBuf in;           // bordered input (for CONVT3 its border supplies the implicit zero padding)
-    QpBuf out;          // destination buffer (possibly a concat buffer)
-    int out_plane0;     // first destination plane (channel offset / 4) inside `out`
-    int variant;        // -1: pick automatically
+    int kind = ND_CONV3;        // nd_layer_kind
+    int act = ND_ACT_NONE;      // nd_act
+    float slope = 1.f;          // PReLU slope (used when slope_dev is null)
+    const float *slope_dev = nullptr;  // PReLU slope in HBM (the packed blob), or null
+    const float *wpk = nullptr;   // packed weights [mtile][kb][tap][64 lanes][4]
+    const float *bias = nullptr;  // [mtiles*32]
+    int cin = 0, cout = 0;      // logical channels (cin is padded to 8 in the buffers)
+    QpBuf in = {};              // bordered input (for CONVT3 its border supplies the implicit zero padding)
+    QpBuf out = {};             // destination buffer (possibly a concat buffer)
+    int out_plane0 = 0;         // first destination plane (channel offset / 4) inside `out`
+    int variant = -1;           // -1: pick automatically
     int in_plane0 = 0;  // first input plane inside `in` (a channel slice of a concat / gradient buffer)
     float *pre = nullptr;   // training: also store the pre-activation (acc + bias), compact [C/4][B][Hv][Wv] float4 planes
     long pre_plane = 0;     // 16-byte elements per plane of `pre`
@@ -85,7 +84,6 @@ static const size_t kSplitScratchBytes = (size_t)512 * 64 * 1024 * 4;
 int nd_launch_conv(const ConvDesc &d, hipStream_t stream);
 bool nd_conv_pool_fits(const ConvDesc &d);  // a 16-bit 3x3 launch with d.pool set can pool in its epilogue (else: nd_launch_maxpool2 after it)
 bool nd_conv_roi_fits(const ConvDesc &d);   // a launch restricted to d.roi_* finds a workgroup shape that fits the LDS
-static inline int nd_launch_conv_f32(const ConvDesc &d, hipStream_t stream) { return nd_launch_conv(d, stream); }
 int nd_conv_variant_count();
 int nd_conv_variant_gemm(int cin, int cout);   // 1-tap fp32 variant (256- / 128-row workgroup tiles) for a Winograd GEMM
 // Winograd F(T x T, 3 x 3), T = 2 | 4 (winograd.hip): fp32 inference path of the wide 3x3 layers
@@ -106,24 +104,29 @@ int nd_launch_conv_w1d(int T, const ConvDesc &d, hipStream_t stream);
 bool nd_w2d_ok(const QpBuf &in);
 long nd_w2d_tiles(const QpBuf &in, int cout);   // workgroup tiles of the whole layer
 int nd_launch_conv_w2d(const ConvDesc &d, hipStream_t stream);
+// an F(4,3) layer (d.wpk: nd_w1d_pack blob with T = 4) in conv_w2d where it takes the layer, else in conv_w1d (flags: nd_flags)
+bool nd_f43_w2d(const QpBuf &in, int cout, bool pre, int flags);
+int nd_launch_conv_f43(const ConvDesc &d, int flags, hipStream_t stream);
 // slack (16-byte elements) behind the last plane of an activation buffer: an N tile of the conv kernels may read a 3x3 halo past
 // the last pixel, a strip of conv_w2d up to 9 rows + 5 pixels
 static inline size_t nd_buf_slack(int Wb) { return (size_t)10 * Wb + 8 + 2048; }
-// Per-device launch caches (CU count, "dynamic LDS size already raised for this kernel") are std::atomic: entry points may be
-// called from several host threads (include/nind_hip.h), and two threads that both miss write the same value.
-// CU count of device `dev` (0 <= dev < 16), queried once per device.
-static inline int nd_num_cus(int dev, int *out) {
-    static std::atomic<int> cus[16];
-    int n = cus[dev].load(std::memory_order_relaxed);
-    if (!n) {
-        hipDeviceProp_t prop;
-        ND_HIP(hipGetDeviceProperties(&prop, dev));
-        n = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        cus[dev].store(n, std::memory_order_relaxed);
-    }
-    *out = n;
-    return ND_OK;
-}
+// ------------------------------------------------------------------ per-device launch state (launch.hip)
+// Entry points may be called from several host threads (include/nind_hip.h).  These calls are safe to race: the CU count is
+// queried once per device, and a kernel's dynamic-LDS limit is checked and raised under one lock, so it only ever grows.
+// current device (0 <= dev < 16) and, if ncus is given, its CU count
+int nd_device(int *dev, int *ncus = nullptr);
+// lets kernel fn use `bytes` of dynamic LDS on device dev; no HIP call once the limit is large enough
+int nd_raise_lds(int dev, const void *fn, size_t bytes);
+// runs init() once per device (the first caller on a device runs it; the others wait until it has succeeded)
+int nd_once_per_device(int dev, int (*init)());
+// checks of a conv layer; `who` is the launcher's error prefix.  Input planes [in_plane0, in_plane0 + 2 KB) exist
+int nd_check_in_planes(const char *who, const ConvDesc &d, int KB);
+// the destination holds B images of oh x ow plus its border (at_least: or more) and planes [out_plane0, out_plane0 + cout / cpp)
+int nd_check_out(const char *who, const ConvDesc &d, int oh, int ow, bool at_least);
+// the linear pixel index of `in` fits int32
+int nd_check_int32(const char *who, const QpBuf &in);
+// d's region of interest (if any) lies inside the Hv x Wv grid; refused: the launcher takes no region for this layer (`why`)
+int nd_check_roi(const char *who, const ConvDesc &d, int Hv, int Wv, bool refused, const char *why);
 // the arithmetic switches every flags-taking entry point accepts (include/nind_hip.h: nd_flags); unknown bits are an error
 static inline int nd_check_flags(int flags) {
     if (flags & ~(ND_FLAG_NO_SPLITK | ND_FLAG_DIRECT_CONV | ND_FLAG_W1D_REGS | ND_FLAG_FULL_TILES | ND_FLAG_UNFUSED_POOL)) ND_FAIL(ND_EINVAL, "unknown flag bits 0x%x", flags);
@@ -159,14 +162,16 @@ __host__ __device__ static inline NdUpRow nd_up_row(int m, int cout, int dt) {
 static inline int nd_taps(int kind) { return (kind == ND_CONV3 || kind == ND_CONVT3) ? 9 : (kind == ND_CONV2S2 ? 4 : 1); }
 // K block = two planes = the K extent of one ds_read_b128 per operand: 8 fp32 channels or 16 bf16/fp16 channels
 static inline int nd_kblocks(int cin, int dt = ND_F32) { return (cin + 2 * nd_cpp(dt) - 1) / (2 * nd_cpp(dt)); }
+// float offset of the fp32 bias inside a packed layer: behind the 1 KiB weight fragments [mtile][kb][plane] -- nd_taps(kind) planes
+// per K block in the direct packing, 3 * (T + 2) in the 1-D Winograd F(T,3) packing (w1d_T = T; fp32, 3x3 kinds)
+static inline size_t nd_bias_offset(int kind, int cin, int cout, int dt = ND_F32, int w1d_T = 0) {
+    return (size_t)nd_mtiles(kind, cout) * nd_kblocks(cin, dt) * (w1d_T ? 3 * (w1d_T + 2) : nd_taps(kind)) * 256;
+}
 // packed layer size in 4-byte units: 1 KiB fragment pieces [mtile][kb][tap] (any dtype) + fp32 bias[mtiles*32]
 static inline size_t nd_packed_floats(int kind, int cin, int cout, int dt = ND_F32) {
-    return (size_t)nd_mtiles(kind, cout) * nd_kblocks(cin, dt) * nd_taps(kind) * 256 + (size_t)nd_mtiles(kind, cout) * 32;
+    return nd_bias_offset(kind, cin, cout, dt) + (size_t)nd_mtiles(kind, cout) * 32;
 }
 void nd_pack_layer(int kind, int cin, int cout, int dt, const float *w, const float *bias, float *packed);
-static inline void nd_pack_layer_f32(int kind, int cin, int cout, const float *w, const float *bias, float *packed) {
-    nd_pack_layer(kind, cin, cout, ND_F32, w, bias, packed);
-}
 
 // device-side packers (pack_dev.hip): the same layouts from weights in HBM (fp32)
 int nd_pack_layer_device(int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s);

@@ -51,7 +51,7 @@ void nd_pack_layer(int kind, int cin, int cout, int dt, const float *w, const fl
     const int MT = nd_mtiles(kind, cout);
     const int M = kind == ND_CONVT2S2 ? 4 * cout : cout;
     const int cpp = nd_cpp(dt);   // channels per lane per piece
-    float *bp = packed + (size_t)MT * KB * taps * 256;
+    float *bp = packed + nd_bias_offset(kind, cin, cout, dt);
     auto weff = [&](int m, int ci, int t) -> float {
         if (m >= M || ci >= cin) return 0.f;
         switch (kind) {

@@ -138,7 +138,7 @@ __global__ void k_pack_wino_dev(int T, int kind, int cin, int cout, int KB, cons
 int nd_pack_layer_device(int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s) {
     const int MT = nd_mtiles(kind, cout), KB = nd_kblocks(cin), taps = nd_taps(kind);
     const int M = kind == ND_CONVT2S2 ? 4 * cout : cout;
-    const long nw = (long)MT * KB * taps * 256;
+    const long nw = (long)nd_bias_offset(kind, cin, cout);
     hipLaunchKernelGGL(k_pack_dev, dim3((unsigned)((nw + MT * 32 + 255) / 256)), dim3(256), 0, s, kind, cin, cout, M, KB, taps, w, bias,
                        packed, nw, MT * 32);
     ND_HIP(hipGetLastError());
@@ -148,7 +148,7 @@ int nd_pack_layer_device(int kind, int cin, int cout, const float *w, const floa
 int nd_pack_w1d_device(int T, int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s) {
     if ((T != 2 && T != 4) || (kind != ND_CONV3 && kind != ND_CONVT3)) ND_FAIL(ND_EINVAL, "device w1d packing: T = 2 | 4, 3x3 layers");
     const int MT = nd_mtiles(ND_CONV3, cout), KB = nd_kblocks(cin);
-    const long nw = (long)MT * KB * 3 * (T + 2) * 256;
+    const long nw = (long)nd_bias_offset(kind, cin, cout, ND_F32, T);
     hipLaunchKernelGGL(k_pack_w1d_dev, dim3((unsigned)((nw + MT * 32 + 255) / 256)), dim3(256), 0, s, T, kind, cin, cout, KB, w, bias,
                        packed, nw, MT * 32);
     ND_HIP(hipGetLastError());
@@ -159,7 +159,7 @@ int nd_pack_wino_device(int T, int kind, int cin, int cout, const float *w, cons
     if ((T != 2 && T != 4 && T != 6) || (kind != ND_CONV3 && kind != ND_CONVT3)) ND_FAIL(ND_EINVAL, "device Winograd packing: T = 2 | 4 | 6, 3x3 layers");
     const int P = (T + 2) * (T + 2), KB = nd_kblocks(cin);
     const long gf = (long)nd_packed_floats(ND_CONV1, cin, cout, ND_F32);
-    const long nwp = (long)nd_mtiles(ND_CONV1, cout) * KB * 256;
+    const long nwp = (long)nd_bias_offset(ND_CONV1, cin, cout);
     const long total = (long)P * gf + (cout + 3) / 4 * 4;
     hipLaunchKernelGGL(k_pack_wino_dev, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, T, kind, cin, cout, KB, w, bias, packed,
                        gf, nwp, P);

@@ -389,12 +389,7 @@ SsimPlan ssim_plan(int n, int c, int h, int w, char *base, bool with_grad = fals
     return p;
 }
 
-int upload_window() {
-    static bool done[64] = {false};   // __constant__ memory is per device
-    int dev = 0;
-    ND_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) ND_FAIL(ND_EINVAL, "ssim: device index %d", dev);
-    if (done[dev]) return ND_OK;
+int write_window() {
     float g[kWin];
     float s = 0.f;   // fp32 throughout, like torch's kernel / kernel.sum()
     for (int k = 0; k < kWin; ++k) {
@@ -404,8 +399,12 @@ int upload_window() {
     }
     for (int k = 0; k < kWin; ++k) g[k] /= s;
     ND_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_gauss), g, sizeof(g)));
-    done[dev] = true;
     return ND_OK;
+}
+int upload_window() {   // __constant__ memory is per device
+    int dev = 0;
+    ND_TRY(nd_device(&dev));
+    return nd_once_per_device(dev, write_window);
 }
 
 // score maps of `scales` pyramid levels -> plan.stats[scale][plane]

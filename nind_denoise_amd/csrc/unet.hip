@@ -167,7 +167,7 @@ extern "C" int nd_unet_pack_weights(int dtype, const float *const *tensors, int 
             continue;
         }
         if (l.bn.empty()) {
-            nd_pack_layer_f32(l.kind, l.cin, l.cout, w, b, blob + bl.off[i]);
+            nd_pack_layer(l.kind, l.cin, l.cout, ND_F32, w, b, blob + bl.off[i]);
             continue;
         }
         // fold eval-mode BatchNorm2d: y = (conv + b - mean) * gamma / sqrt(var + eps) + beta
@@ -180,7 +180,7 @@ extern "C" int nd_unet_pack_weights(int dtype, const float *const *tensors, int 
             for (int k = 0; k < l.cin * 9; ++k) wf[(size_t)co * l.cin * 9 + k] = w[(size_t)co * l.cin * 9 + k] * sc;
             bf[co] = (b[co] - rm[co]) * sc + be[co];
         }
-        nd_pack_layer_f32(l.kind, l.cin, l.cout, wf.data(), bf.data(), blob + bl.off[i]);
+        nd_pack_layer(l.kind, l.cin, l.cout, ND_F32, wf.data(), bf.data(), blob + bl.off[i]);
     }
     return ND_OK;
 }
@@ -220,18 +220,16 @@ extern "C" int nd_unet_forward(int dtype, const void *packed, const float *x, fl
         d.kind = l.kind;
         d.act = l.kind == ND_CONV3 ? ND_ACT_PRELU : ND_ACT_NONE;   // ReLU = PReLU with slope 0
         d.slope = 0.f;
-        d.slope_dev = nullptr;
         d.cin = l.cin;
         d.cout = l.cout;
         d.wpk = blob + bl.off[st.layer];
-        d.bias = d.wpk + (size_t)nd_mtiles(l.kind, l.cout) * nd_kblocks(l.cin) * nd_taps(l.kind) * 256;
+        d.bias = d.wpk + nd_bias_offset(l.kind, l.cin, l.cout);
         d.in = pl.buf[st.src];
         d.out = pl.buf[st.dst];
         d.out_plane0 = st.dst_plane0;
-        d.variant = -1;
         d.part = pl.split;
         d.part_bytes = kSplitScratchBytes;
-        ND_TRY(nd_launch_conv_f32(d, s));
+        ND_TRY(nd_launch_conv(d, s));
     }
     const float *fw = blob + bl.off[L.size() - 1];
     ND_TRY(nd_launch_final1x1(pl.buf[U4B], 64, fw, fw + 3 * 64, 0, y, h, w, s, 1));

@@ -394,14 +394,12 @@ extern "C" int nd_layer_forward(int kind, int act, float slope, int dtype, const
     d.kind = kind;
     d.act = act;
     d.slope = slope;
-    d.slope_dev = nullptr;
     d.cin = cin;
     d.cout = cout;
     d.wpk = (const float *)packed;
-    d.bias = d.wpk + (size_t)nd_mtiles(kind, cout) * nd_kblocks(cin, dtype) * nd_taps(kind) * 256;
+    d.bias = d.wpk + nd_bias_offset(kind, cin, cout, dtype);
     d.in = pl.in;
     d.out = pl.out;
-    d.out_plane0 = 0;
     d.variant = variant;
     d.part = pl.split;
     d.part_bytes = kSplitScratchBytes;
@@ -451,23 +449,18 @@ extern "C" int nd_layer_forward_winograd(int tile, int kind, int act, float slop
     d.kind = kind;
     d.act = act;
     d.slope = slope;
-    d.slope_dev = nullptr;
     d.cin = cin;
     d.cout = cout;
     d.wpk = (const float *)packed;
-    d.bias = nullptr;
     d.in = pl.in;
     d.out = pl.out;
-    d.out_plane0 = 0;
-    d.variant = -1;
     d.part = pl.split;
     d.part_bytes = kSplitScratchBytes;
     d.nosplit = (flags & ND_FLAG_NO_SPLITK) != 0;
+    if (tile & 1) d.bias = d.wpk + nd_bias_offset(kind, cin, cout, ND_F32, tile == 5 ? 4 : tile + 1);
     if (tile == 5) {
-        d.bias = d.wpk + (size_t)nd_mtiles(ND_CONV3, cout) * nd_kblocks(cin) * 3 * 6 * 256;
         ND_TRY(nd_launch_conv_w2d(d, s));
     } else if (tile & 1) {
-        d.bias = d.wpk + (size_t)nd_mtiles(ND_CONV3, cout) * nd_kblocks(cin) * 3 * (tile + 3) * 256;
         ND_TRY(nd_launch_conv_w1d(tile + 1, d, s));
     } else {
         ND_TRY(nd_launch_conv_wino(tile, d, (char *)ws + pl.bytes, ws_bytes - pl.bytes, s));
@@ -542,21 +535,18 @@ extern "C" int nd_conv_bench(int kind, int dtype, int batch, int cin, int cout, 
         // pseudo-random finite 16-bit patterns: fill as bf16/fp16 values in (-0.5, 0.5) through the fp32 generator + convert
         hipLaunchKernelGGL(k_fill_random16, dim3(2048), dim3(256), 0, s, (unsigned short *)ws, need / 2, 12345u, dtype);
         hipLaunchKernelGGL(k_fill_random16, dim3(1024), dim3(256), 0, s, (unsigned short *)wpk, wfloats * 2, 777u, dtype);
-        hipLaunchKernelGGL(k_fill_random, dim3(64), dim3(256), 0, s, wpk + (size_t)nd_mtiles(kind, cout) * nd_kblocks(cin, dtype) * nd_taps(kind) * 256,
-                           (size_t)nd_mtiles(kind, cout) * 32, 99u);
+        hipLaunchKernelGGL(k_fill_random, dim3(64), dim3(256), 0, s, wpk + nd_bias_offset(kind, cin, cout, dtype), (size_t)nd_mtiles(kind, cout) * 32, 99u);
     }
     ConvDesc d;
     d.kind = kind;
     d.act = ND_ACT_PRELU;
     d.slope = 0.2f;
-    d.slope_dev = nullptr;
     d.cin = cin;
     d.cout = cout;
     d.wpk = wpk;
-    d.bias = wpk + (size_t)nd_mtiles(kind, cout) * nd_kblocks(cin, dtype) * nd_taps(kind) * 256;
+    d.bias = wpk + nd_bias_offset(kind, cin, cout, dtype);
     d.in = pl.in;
     d.out = pl.out;
-    d.out_plane0 = 0;
     d.variant = variant;
     d.part = pl.split;
     d.part_bytes = kSplitScratchBytes;
@@ -601,20 +591,16 @@ extern "C" int nd_winograd_bench(int tile, int kind, int batch, int cin, int cou
     d.kind = kind;
     d.act = ND_ACT_PRELU;
     d.slope = 0.2f;
-    d.slope_dev = nullptr;
     d.cin = cin;
     d.cout = cout;
     d.wpk = wpk;
-    d.bias = nullptr;
     d.in = pl.in;
     d.out = pl.out;
-    d.out_plane0 = 0;
-    d.variant = -1;
     d.part = pl.split;
     d.part_bytes = kSplitScratchBytes;
     void *scratch = (char *)ws + pl.bytes;
     const size_t scratch_bytes = need - pl.bytes;
-    if (tile & 1) d.bias = d.wpk + (size_t)nd_mtiles(ND_CONV3, cout) * nd_kblocks(cin) * 3 * ((tile == 5 ? 3 : tile) + 3) * 256;
+    if (tile & 1) d.bias = d.wpk + nd_bias_offset(kind, cin, cout, ND_F32, tile == 5 ? 4 : tile + 1);
     auto run = [&]() {
         return tile == 5 ? nd_launch_conv_w2d(d, s) : ((tile & 1) ? nd_launch_conv_w1d(tile + 1, d, s) : nd_launch_conv_wino(tile, d, scratch, scratch_bytes, s));
     };

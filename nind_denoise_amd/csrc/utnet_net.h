@@ -254,7 +254,7 @@ inline Form step_form(const Step &st, int f, int dt, int flags, const Plan &pl, 
     if (train) return (train_w1 && train_w1[st.layer]) ? FORM_W1D4 : FORM_DIRECT;
     if (flags & ND_FLAG_DIRECT_CONV) return FORM_DIRECT;
     if (bl.w1off[st.layer]) {
-        if (!(flags & ND_FLAG_W1D_REGS) && nd_w2d_ok(pl.buf[st.src])) return FORM_W1D4;   // conv_w2d: any row width
+        if (nd_f43_w2d(pl.buf[st.src], lcout(l, f), false, flags)) return FORM_W1D4;   // conv_w2d: any row width
         if (nd_w1d_fits(kW1dTile, pl.buf[st.src])) return FORM_W1D4;
         if (nd_w1d_fits(2, pl.buf[st.src])) return FORM_W1D2;
         return FORM_DIRECT;
@@ -347,7 +347,6 @@ inline bool rois_supported(int f, int dt, int flags, const Plan &pl, const BlobL
             d.cout = lcout(l, f);
             d.in = pl.buf[kSteps[i].src];
             d.out = pl.buf[kSteps[i].dst];
-            d.variant = -1;
             d.roi_r0 = rois[i].r0;
             d.roi_c0 = rois[i].c0;
             d.roi_rows = rois[i].rows;
@@ -400,11 +399,10 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
         d.cin = lcin(l, f);
         d.cout = lcout(l, f);
         d.wpk = blob + bl.off[st.layer];
-        d.bias = d.wpk + (size_t)nd_mtiles(l.kind, d.cout) * nd_kblocks(d.cin, dt) * nd_taps(l.kind) * 256;
+        d.bias = d.wpk + nd_bias_offset(l.kind, d.cin, d.cout, dt);
         d.in = pl.buf[st.src];
         d.out = pl.buf[st.dst];
         d.out_plane0 = st.dst_plane0_mul * f / cpp;
-        d.variant = -1;
         d.part = pl.split;
         d.part_bytes = kSplitScratchBytes;
         d.nosplit = (flags & ND_FLAG_NO_SPLITK) != 0;
@@ -418,7 +416,7 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
         // MaxPool2d(2) fused into the producing layer's epilogue where its kernel can (conv_w2d, three-pass output transform):
         // the pool kernel re-read the whole skip tensor from HBM (2.4 % of the fp32 conv stack)
         const bool next_is_pool = this_step + 1 < kNumSteps && kSteps[this_step + 1].layer < 0;
-        const bool w2d = form == FORM_W1D4 && !pre && !(flags & ND_FLAG_W1D_REGS);
+        const bool w2d = form == FORM_W1D4 && nd_f43_w2d(d.in, d.cout, pre != nullptr, flags);
         if (next_is_pool && !pre && !(flags & ND_FLAG_UNFUSED_POOL)) {
             pool_view = pl.buf[kSteps[this_step + 1].dst];
             d.pool = &pool_view;
@@ -431,14 +429,8 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
             // narrow layer: 1-D Winograd along x inside the implicit-GEMM kernel; F(4,3), or F(2,3) on rows too wide for it
             const int T = form == FORM_W1D4 ? kW1dTile : 2;
             if (!pre) d.wpk = blob + (T == kW1dTile ? bl.w1off[st.layer] : bl.w1off2[st.layer]);
-            d.bias = d.wpk + (size_t)nd_mtiles(ND_CONV3, d.cout) * nd_kblocks(d.cin) * 3 * (T + 2) * 256;
-            // transform shared through LDS (conv_w2d.hip): inference always; training forward (it keeps the pre-activation copy, so its
-            // tiles are never split along K) where the layer has tiles for two rounds of workgroups -- else conv_w1d, which splits
-            const bool w2d_ok = T == 4 && !(flags & ND_FLAG_W1D_REGS) && nd_w2d_ok(d.in) && (!pre || nd_w2d_tiles(d.in, d.cout) >= 512);
-            if (w2d_ok)
-                ND_TRY(nd_launch_conv_w2d(d, s));
-            else
-                ND_TRY(nd_launch_conv_w1d(T, d, s));
+            d.bias = d.wpk + nd_bias_offset(d.kind, d.cin, d.cout, ND_F32, T);
+            ND_TRY(form == FORM_W1D4 ? nd_launch_conv_f43(d, flags, s) : nd_launch_conv_w1d(T, d, s));
             continue;
         }
         if (form == FORM_WINO3P) {

@@ -758,31 +758,18 @@ static int train_backward(TrainCtx &c, const float *params, float *grads, const 
         if (st.layer > 0) {
             ConvDesc d;
             d.kind = transposed_kind(l.kind);
-            d.act = ND_ACT_NONE;
-            d.slope = 1.f;
-            d.slope_dev = nullptr;
             d.cin = co;
             d.cout = ci;
             d.wpk = bblob + bb.off[st.layer];
-            d.bias = d.wpk + (size_t)nd_mtiles(d.kind, ci) * nd_kblocks(co) * nd_taps(d.kind) * 256;
+            d.bias = d.wpk + nd_bias_offset(d.kind, co, ci, ND_F32, c.bwd_w1[st.layer] ? kW1dTile : 0);
             d.in = go;
             d.in_plane0 = oplane0;
             d.out = t.g[st.src];
-            d.out_plane0 = 0;
-            d.variant = -1;
             d.part = t.fwd.split;
             d.part_bytes = kSplitScratchBytes;
             d.nosplit = (flags & ND_FLAG_NO_SPLITK) != 0;
-            if (c.bwd_w1[st.layer]) {
-                d.bias = d.wpk + (size_t)nd_mtiles(ND_CONV3, ci) * nd_kblocks(co) * 18 * 256;
-                // (a data gradient keeps no pre-activation copy: the inference form with the LDS-shared transform applies)
-                if (nd_w2d_ok(d.in) && !(flags & ND_FLAG_W1D_REGS))
-                    ND_TRY(nd_launch_conv_w2d(d, s));
-                else
-                    ND_TRY(nd_launch_conv_w1d(kW1dTile, d, s));
-            } else {
-                ND_TRY(nd_launch_conv(d, s));
-            }
+            // (a data gradient keeps no pre-activation copy: the F(4,3) form takes the inference path)
+            ND_TRY(c.bwd_w1[st.layer] ? nd_launch_conv_f43(d, flags, s) : nd_launch_conv(d, s));
         } else if (dx) {
             // the input image's gradient: first layer's data gradient + the adjoint of ReflectionPad2d(2), one kernel
             ND_TRY(nd_launch_input_grad(go, params + c.pl.off[tensor_index("convs1.0.weight")], H, W, dx, s));

@@ -475,12 +475,10 @@ int nd_launch_conv_wino(int T, const ConvDesc &d, void *scratch, size_t scratch_
         ND_FAIL(ND_EINVAL, "winograd: fp32 3x3 layers only");
     if (d.cin % 16 || d.cout % 4) ND_FAIL(ND_EINVAL, "winograd: Cin must be a multiple of 16, Cout of 4 (got %d, %d)", d.cin, d.cout);
     if (d.pre) ND_FAIL(ND_EINVAL, "winograd: inference only (no pre-activation copy)");
+    ND_TRY(nd_check_roi("winograd", d, d.in.Hb - 2, d.in.Wb - 2, T != 6 || d.pool, "a layer other than an unpooled F(6x6) one"));
     const bool roi = d.roi_rows > 0;
-    if (roi && (T != 6 || d.pool || d.roi_r0 < 0 || d.roi_c0 < 0 || d.roi_cols < 1 || d.roi_r0 + d.roi_rows > d.in.Hb - 2 || d.roi_c0 + d.roi_cols > d.in.Wb - 2))
-        ND_FAIL(ND_EINVAL, "winograd: region [%d,+%d) x [%d,+%d) outside the output (F(6x6), unpooled layers only)", d.roi_r0, d.roi_rows, d.roi_c0, d.roi_cols);
     const WinoGeo g = wino_geo(T, d.in, d.cin, d.cout, d.roi_rows, d.roi_cols);
-    if (d.out.Hb != d.in.Hb - 2 + 2 * d.out.pad || d.out.Wb != d.in.Wb - 2 + 2 * d.out.pad || d.out.B != d.in.B)
-        ND_FAIL(ND_EINVAL, "winograd: destination does not fit the result");
+    ND_TRY(nd_check_out("winograd", d, d.in.Hb - 2, d.in.Wb - 2, false));
     // a region is the same three passes on shifted base pointers (input view: rows [r0, r0 + rows + 2) of the bordered buffer)
     const long roi_in = roi ? (long)d.roi_r0 * d.in.Wb + d.roi_c0 : 0, roi_out = roi ? (long)d.roi_r0 * d.out.Wb + d.roi_c0 : 0;
     const int vHb = g.Hv + 2, vWb = g.Wv + 2;
@@ -508,26 +506,12 @@ int nd_launch_conv_wino(int T, const ConvDesc &d, void *scratch, size_t scratch_
 
     ConvDesc e;
     e.kind = ND_CONV1;
-    e.act = ND_ACT_NONE;
-    e.slope = 1.f;
-    e.slope_dev = nullptr;
     e.cin = d.cin;
     e.cout = d.cout;
     e.wpk = d.wpk;
-    e.bias = d.wpk + (size_t)nd_mtiles(ND_CONV1, d.cout) * nd_kblocks(d.cin) * 256;   // the zero bias of position 0
-    e.in.base = (float *)v;
-    e.in.planes = in_planes;
-    e.in.B = d.in.B;
-    e.in.Hb = g.TY;
-    e.in.Wb = g.TX;
-    e.in.pad = 0;
-    e.in.pstride = g.vnp;
-    e.in.dt = ND_F32;
-    e.out = e.in;
-    e.out.base = (float *)m;
-    e.out.planes = out_planes;
-    e.out.pstride = g.mnp;
-    e.out_plane0 = 0;
+    e.bias = d.wpk + nd_bias_offset(ND_CONV1, d.cin, d.cout);   // the zero bias of position 0
+    e.in = {(float *)v, in_planes, d.in.B, g.TY, g.TX, 0, g.vnp, ND_F32};
+    e.out = {(float *)m, out_planes, d.in.B, g.TY, g.TX, 0, g.mnp, ND_F32};
     e.variant = nd_conv_variant_gemm(d.cin, d.cout);
     e.part = d.part;
     e.part_bytes = d.part_bytes;
