@@ -65,13 +65,15 @@ typedef enum nd_flags {
                                  instead of the one that shares the transform through LDS (conv_w2d, the default)            */
     ND_FLAG_UNFUSED_POOL = 16, /* A/B switch: every MaxPool2d(2) as its own kernel (default: written from the producing layer's
                                  epilogue wherever its kernel can -- identical values)                                        */
+    ND_FLAG_TILE_ENCODER = 32, /* A/B switch: nd_utnet_denoise_frame runs every tile's whole encoder (default: the first two
+                                 levels once per band of tile rows, see nd_utnet_frame_plan)                                   */
     ND_FLAG_FULL_TILES = 8    /* nd_utnet_denoise_tiles / nd_utnet_profile_stack: compute every layer on the whole tile, as
                                  UtNet.forward does.  Default there: the last decoder levels compute only the pixels that the
                                  useful crop [pad, cs - pad) of a tile can reach (denoise_image.py:249-258 discards the rest of
                                  the network output before the canvas +=) -- same canvas, 19 % less work at cs 264 / ucs 200    */
 } nd_flags;
 
-int nd_version(void);   /* 104 = this header */
+int nd_version(void);   /* 105 = this header */
 const char *nd_last_error(void);
 
 /* ---------------------------------------------------------------- tile geometry (host, pure integer)
@@ -138,6 +140,28 @@ int nd_utnet_denoise_tiles(int funit, int act, int dtype, int flags, const void 
                            const float *img_chw, float *canvas_chw, int width, int height,
                            int cs, int ucs, int ol, int tile_begin, int tile_count, int batch,
                            void *workspace, size_t workspace_bytes, void *stream);
+
+/* The same loop for tiles [tile_begin, tile_begin+tile_count) of any length, in ascending launches of at most `batch` tiles
+ * (`workspace` as for nd_utnet_denoise_tiles with that batch).  fp32 storage in useful-region mode with a tile stride divisible
+ * by 4 (nd_utnet_frame_plan: D = 2): the first two encoder levels (convs1.0 ... the second pool) run once per band of tile rows
+ * on the band's window of the mirrored frame (valid 3x3 convolutions and 2x2 pools are translation-equivariant); each tile's
+ * skip tensors and pooled level-2 input are copied from the band, and the border lines its own ReflectionPad2d(2) reaches are
+ * recomputed from 16-pixel strips of its input.  Same canvas as the per-tile encoder up to fp32 re-association (<= 1e-5);
+ * bits do not depend on `batch` or the tile range with ND_FLAG_NO_SPLITK.  Every other case runs nd_utnet_denoise_tiles.
+ * frame_ws: nd_utnet_frame_workspace_bytes, zero-filled once (null / 0 when that is 0).  progress (optional) is called with
+ * (progress_ctx, launch index, first tile, tile count) before each launch is enqueued. */
+typedef void (*nd_progress_fn)(void *ctx, int n, int tile_begin, int tile_count);
+size_t nd_utnet_frame_workspace_bytes(int funit, int dtype, int flags, int width, int height, int cs, int ucs, int ol, int batch);
+int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, const void *packed_dev,
+                           const float *img_chw, float *canvas_chw, int width, int height,
+                           int cs, int ucs, int ol, int tile_begin, int tile_count, int batch,
+                           void *workspace, size_t workspace_bytes, void *frame_ws, size_t frame_ws_bytes, void *stream,
+                           nd_progress_fn progress, void *progress_ctx);
+/* Host-only query (no GPU call): the band plan of nd_utnet_denoise_frame.  out[8] = {D (shared encoder levels: 2 or 0),
+ * aligned levels (tile origins on whole pixels of level 0 .. aligned-1: 1 + the power of 2 in the stride, at most 4), tile rows
+ * per band, bands, stride, grid columns, grid rows, band input rows of a full band}.  A function of the frame geometry, the dtype
+ * and the flags only (batch enters only through the workspace size). */
+int nd_utnet_frame_plan(int funit, int dtype, int flags, int width, int height, int cs, int ucs, int ol, int *out);
 
 /* Profiling entry point for the roofline report: one pass of the conv stack (22 MFMA conv layers + 4 pools, the launches
  * between the input pack and the final 1x1) with a HIP event recorded on `stream` between launches.  Synchronises the stream.

@@ -14,7 +14,9 @@ DTYPE = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1, "f16": 2, 
 ACT = {"none": 0, "PReLU": 1, "ELU": 2, "Hardswish": 3}
 KIND = {"conv3": 0, "convT3": 1, "convT2s2": 2, "conv1": 3, "conv2s2": 4}
 # nd_flags (include/nind_hip.h): per-call arithmetic switches
-FLAG_NO_SPLITK, FLAG_DIRECT_CONV, FLAG_W1D_REGS, FLAG_FULL_TILES, FLAG_UNFUSED_POOL = 1, 2, 4, 8, 16
+FLAG_NO_SPLITK, FLAG_DIRECT_CONV, FLAG_W1D_REGS, FLAG_FULL_TILES, FLAG_UNFUSED_POOL, FLAG_TILE_ENCODER = 1, 2, 4, 8, 16, 32
+# nd_progress_fn: (ctx, launch index, first tile, tile count)
+PROGRESS_FN = ctypes.CFUNCTYPE(None, c_void_p, c_int, c_int, c_int)
 
 
 class StepProfile(ctypes.Structure):
@@ -67,6 +69,10 @@ _SIGNATURES = {
     "nd_utnet_profile_stack": (c_int, [c_int] * 4 + [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_int]),
     "nd_utnet_step_name": (c_char_p, [c_int]),
     "nd_utnet_useful_region": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int)]),
+    "nd_utnet_frame_workspace_bytes": (c_size_t, [c_int] * 9),
+    "nd_utnet_frame_plan": (c_int, [c_int] * 8 + [POINTER(c_int)]),
+    "nd_utnet_denoise_frame": (c_int, [c_int] * 4 + [c_void_p] * 3 + [c_int] * 8 + [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
+                                                                                    PROGRESS_FN, c_void_p]),
     "nd_layer_packed_bytes": (c_size_t, [c_int] * 4),
     "nd_layer_pack": (c_int, [c_int] * 4 + [c_void_p, c_void_p, c_void_p, c_size_t]),
     "nd_layer_workspace_bytes": (c_size_t, [c_int] * 7),

@@ -152,6 +152,120 @@ int nd_launch_gather_pack(const float *img, int W, int H, int cs, int ucs, int o
     return ND_OK;
 }
 
+// ------------------------------------------------------------------ shared encoder (fp32): band gather, strip gather, splice
+// Every gathered tile is the window of the symmetric-padded frame at its origin, so a band of tile rows is gathered as one image:
+// band pixel (v, u) = frame pixel (by0 + v, bx0 + u) under the same mirror.  The outer ring that no tile reaches unpadded (the
+// 2-pixel reflect border of the first and last tiles) only feeds lines the strips recompute: it is clamped into the frame.
+__global__ void k_gather_band(const float *__restrict__ img, TileGeo g, int by0, int bx0, f32x4 *__restrict__ dst, int Hb, int Wb) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    const int v = blockIdx.y;
+    if (u >= Wb) return;
+    int sx = mirror_sym(bx0 + u, g.W), sy = mirror_sym(by0 + v, g.H);
+    sx = sx < 0 ? 0 : (sx >= g.W ? g.W - 1 : sx);
+    sy = sy < 0 ? 0 : (sy >= g.H ? g.H - 1 : sy);
+    const size_t plane = (size_t)g.W * g.H;
+    const float *s = img + (size_t)sy * g.W + sx;
+    f32x4 o = {s[0], s[plane], s[2 * plane], 0.f};
+    dst[(size_t)v * Wb + u] = o;
+}
+
+int nd_launch_gather_band(const float *img, int W, int H, int cs, int ucs, int ol, int band_row0, const QpBuf &dst, hipStream_t s) {
+    TileGeo g;
+    ND_TRY(make_geo(W, H, cs, ucs, ol, &g));
+    if (dst.dt != ND_F32 || dst.pad != 0 || dst.B != 1 || (long)dst.Hb * dst.Wb > dst.pstride || band_row0 < 0 || band_row0 >= g.rows)
+        ND_FAIL(ND_EINVAL, "gather_band: bad destination / band row %d", band_row0);
+    dim3 grid((dst.Wb + 255) / 256, dst.Hb);
+    hipLaunchKernelGGL(k_gather_band, grid, dim3(256), 0, s, img, g, band_row0 * g.stride - g.pad - 2, -g.pad - 2, (f32x4 *)dst.base,
+                       dst.Hb, dst.Wb);
+    ND_HIP(hipGetLastError());
+    return ND_OK;
+}
+
+// The first-layer input (gather + ReflectionPad2d(2), as k_gather_pack) of two border strips per tile: image 2t = rows (vertical:
+// columns) [0, n) of tile t's (cs+4)^2 input, image 2t+1 = rows (columns) [cs+4-n, cs+4).
+__global__ void k_gather_strips(const float *__restrict__ img, TileGeo g, int tile_begin, int vertical, f32x4 *__restrict__ dst,
+                                int Hs, int Ws) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    const int v = blockIdx.y;
+    const int b = blockIdx.z;
+    if (u >= Ws) return;
+    const int i = tile_begin + (b >> 1), side = b & 1;
+    const int yi = i / g.cols, xi = i - yi * g.cols;
+    const int n = vertical ? Ws : Hs;
+    const int row = v + (!vertical && side ? g.cs + 4 - n : 0), col = u + (vertical && side ? g.cs + 4 - n : 0);
+    const int qx = reflect_nr(col - 2, g.cs), qy = reflect_nr(row - 2, g.cs);
+    const int sx = mirror_sym(xi * g.stride - g.pad + qx, g.W);
+    const int sy = mirror_sym(yi * g.stride - g.pad + qy, g.H);
+    const size_t plane = (size_t)g.W * g.H;
+    const float *s = img + (size_t)sy * g.W + sx;
+    f32x4 o = {s[0], s[plane], s[2 * plane], 0.f};
+    dst[((size_t)b * Hs + v) * Ws + u] = o;
+}
+
+int nd_launch_gather_strips(const float *img, int W, int H, int cs, int ucs, int ol, int tile_begin, int tile_count, bool vertical,
+                            const QpBuf &dst, hipStream_t s) {
+    TileGeo g;
+    ND_TRY(make_geo(W, H, cs, ucs, ol, &g));
+    const int n = vertical ? dst.Wb : dst.Hb, len = vertical ? dst.Hb : dst.Wb;
+    if (tile_begin < 0 || tile_count <= 0 || tile_begin + tile_count > g.cols * g.rows || dst.B != 2 * tile_count ||
+        dst.dt != ND_F32 || dst.pad != 0 || len != cs + 4 || n < 1 || n > cs + 4 || dst.used() > dst.pstride)
+        ND_FAIL(ND_EINVAL, "gather_strips: bad tile range [%d,+%d) or destination", tile_begin, tile_count);
+    dim3 grid((dst.Wb + 255) / 256, dst.Hb, dst.B);
+    hipLaunchKernelGGL(k_gather_strips, grid, dim3(256), 0, s, img, g, tile_begin, vertical ? 1 : 0, (f32x4 *)dst.base, dst.Hb, dst.Wb);
+    ND_HIP(hipGetLastError());
+    return ND_OK;
+}
+
+// dst image t, plane dst_p0 + p, interior pixel (r, c) of [r0, r1) x [c0, c1)  <-  src image img_mul * t + img_add, plane
+// src_p0 + p, interior pixel (yrel * step + r + oy, xi * step + c + ox), (yi, xi) = grid position of tile tile_begin + t,
+// yrel = yi - row0.  A band tensor: img_mul = 0, step = the tile stride at its level; a strip: step = 0.
+struct SpliceArgs {
+    const f32x4 *src;
+    f32x4 *dst;
+    long src_np, dst_np;
+    int src_Hb, src_Wb, src_pad, dst_Hb, dst_Wb, dst_pad;
+    int tile_begin, cols, row0, step, img_mul, img_add, oy, ox, r0, c0, rows, ccols, planes;
+};
+__global__ void k_splice(SpliceArgs a) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;   // pixel of the region, row-major (a region may be one column wide)
+    if (k >= a.rows * a.ccols) return;
+    const int r = a.r0 + k / a.ccols, c = a.c0 + k % a.ccols;
+    const int t = blockIdx.y / a.planes, p = blockIdx.y - t * a.planes;
+    const int i = a.tile_begin + t;
+    const int yi = i / a.cols, xi = i - yi * a.cols;
+    const int sy = (yi - a.row0) * a.step + r + a.oy + a.src_pad, sx = xi * a.step + c + a.ox + a.src_pad;
+    const long si = (long)p * a.src_np + ((long)(a.img_mul * t + a.img_add) * a.src_Hb + sy) * a.src_Wb + sx;
+    a.dst[(long)p * a.dst_np + ((long)t * a.dst_Hb + r + a.dst_pad) * a.dst_Wb + c + a.dst_pad] = a.src[si];
+}
+
+int nd_launch_splice(const QpBuf &src, int src_p0, const QpBuf &dst, int dst_p0, int planes, int tile_begin, int tile_count, int cols,
+                     int row0, int step, int img_mul, int img_add, int oy, int ox, int r0, int r1, int c0, int c1, hipStream_t s) {
+    const int sH = src.Hb - 2 * src.pad, sW = src.Wb - 2 * src.pad, dH = dst.Hb - 2 * dst.pad, dW = dst.Wb - 2 * dst.pad;
+    // the source pixels of the first / last tile row and of grid columns 0 / cols - 1 bound those of every tile (offsets are linear)
+    const int yf = tile_begin / cols - row0, yl = (tile_begin + tile_count - 1) / cols - row0;
+    const int xl = tile_count >= cols ? cols - 1 : ((tile_begin / cols == (tile_begin + tile_count - 1) / cols) ? (tile_begin + tile_count - 1) % cols : cols - 1);
+    const int xf = tile_count >= cols || tile_begin / cols != (tile_begin + tile_count - 1) / cols ? 0 : tile_begin % cols;
+    const bool ok = src.dt == ND_F32 && dst.dt == ND_F32 && tile_count > 0 && tile_count <= dst.B && planes > 0 && yf >= 0 &&
+                    src_p0 >= 0 && src_p0 + planes <= src.planes && dst_p0 >= 0 && dst_p0 + planes <= dst.planes &&
+                    r0 >= 0 && c0 >= 0 && r1 > r0 && c1 > c0 && r1 <= dH && c1 <= dW &&
+                    yf * step + r0 + oy >= 0 && yl * step + r1 - 1 + oy < sH && xf * step + c0 + ox >= 0 && xl * step + c1 - 1 + ox < sW &&
+                    img_add >= 0 && img_mul * (tile_count - 1) + img_add < src.B && (long)tile_count * planes <= 65535;
+    if (!ok) ND_FAIL(ND_EINVAL, "splice: region [%d,%d) x [%d,%d) of %d tiles x %d planes outside its source / destination", r0, r1, c0, c1,
+                     tile_count, planes);
+    SpliceArgs a;
+    a.src = (const f32x4 *)src.base + (long)src_p0 * src.np();
+    a.dst = (f32x4 *)dst.base + (long)dst_p0 * dst.np();
+    a.src_np = src.np(); a.dst_np = dst.np();
+    a.src_Hb = src.Hb; a.src_Wb = src.Wb; a.src_pad = src.pad;
+    a.dst_Hb = dst.Hb; a.dst_Wb = dst.Wb; a.dst_pad = dst.pad;
+    a.tile_begin = tile_begin; a.cols = cols; a.row0 = row0; a.step = step; a.img_mul = img_mul; a.img_add = img_add;
+    a.oy = oy; a.ox = ox; a.r0 = r0; a.c0 = c0; a.rows = r1 - r0; a.ccols = c1 - c0; a.planes = planes;
+    dim3 grid(((r1 - r0) * (c1 - c0) + 255) / 256, tile_count * planes);
+    hipLaunchKernelGGL(k_splice, grid, dim3(256), 0, s, a);
+    ND_HIP(hipGetLastError());
+    return ND_OK;
+}
+
 // ------------------------------------------------------------------ stitch (denoise_image.py:204-213, 249-267)
 // One thread per canvas pixel; contributions of the tiles [tile_begin, tile_begin+count) that cover it are added in
 // ascending tile index order on top of the current canvas value: the fp32 sum order of the reference's loop.

@@ -129,7 +129,7 @@ int nd_check_int32(const char *who, const QpBuf &in);
 int nd_check_roi(const char *who, const ConvDesc &d, int Hv, int Wv, bool refused, const char *why);
 // the arithmetic switches every flags-taking entry point accepts (include/nind_hip.h: nd_flags); unknown bits are an error
 static inline int nd_check_flags(int flags) {
-    if (flags & ~(ND_FLAG_NO_SPLITK | ND_FLAG_DIRECT_CONV | ND_FLAG_W1D_REGS | ND_FLAG_FULL_TILES | ND_FLAG_UNFUSED_POOL)) ND_FAIL(ND_EINVAL, "unknown flag bits 0x%x", flags);
+    if (flags & ~(ND_FLAG_NO_SPLITK | ND_FLAG_DIRECT_CONV | ND_FLAG_W1D_REGS | ND_FLAG_FULL_TILES | ND_FLAG_UNFUSED_POOL | ND_FLAG_TILE_ENCODER)) ND_FAIL(ND_EINVAL, "unknown flag bits 0x%x", flags);
     return ND_OK;
 }
 const char *nd_conv_variant_label(int v);
@@ -190,3 +190,12 @@ int nd_launch_final1x1_stitch(const QpBuf &src, int cin, const float *w, const f
                               hipStream_t s);
 int nd_launch_gather_pack(const float *img, int width, int height, int cs, int ucs, int ol, int tile_begin,
                           int tile_count, const QpBuf &dst, hipStream_t s);
+// shared encoder of the fused loop (fp32): band of tile rows from band_row0 as one first-layer input image (B = 1, no reflect
+// border); two border strips per tile (images 2t, 2t+1: top / bottom rows or, vertical, left / right columns of the tile's input);
+// per-tile copy of a window of a band or strip tensor into a tile buffer (see k_splice)
+int nd_launch_gather_band(const float *img, int width, int height, int cs, int ucs, int ol, int band_row0, const QpBuf &dst,
+                          hipStream_t s);
+int nd_launch_gather_strips(const float *img, int width, int height, int cs, int ucs, int ol, int tile_begin, int tile_count,
+                            bool vertical, const QpBuf &dst, hipStream_t s);
+int nd_launch_splice(const QpBuf &src, int src_p0, const QpBuf &dst, int dst_p0, int planes, int tile_begin, int tile_count, int cols,
+                     int row0, int step, int img_mul, int img_add, int oy, int ox, int r0, int r1, int c0, int c1, hipStream_t s);

@@ -180,6 +180,99 @@ extern "C" int nd_utnet_denoise_tiles(int funit, int act, int dtype, int flags, 
     return ND_OK;
 }
 
+// ------------------------------------------------------------------ frame loop with the shared encoder (utnet_net.h: frame_plan)
+extern "C" size_t nd_utnet_frame_workspace_bytes(int funit, int dtype, int flags, int width, int height, int cs, int ucs, int ol,
+                                                 int batch) {
+    FramePlan fp;
+    if (nd_check_flags(flags) != ND_OK || frame_plan(funit, dtype, flags, width, height, cs, ucs, ol, batch, &fp) != ND_OK) return 0;
+    return fp.bytes;
+}
+
+extern "C" int nd_utnet_frame_plan(int funit, int dtype, int flags, int width, int height, int cs, int ucs, int ol, int *out) {
+    ND_TRY(nd_check_flags(flags));
+    if (!out) ND_FAIL(ND_EINVAL, "nd_utnet_frame_plan: null output");
+    FramePlan fp;
+    ND_TRY(frame_plan(funit, dtype, flags, width, height, cs, ucs, ol, 1, &fp));
+    const int v[8] = {fp.D, fp.aligned, fp.R, fp.nbands, fp.S, fp.cols, fp.rows, fp.hx};
+    memcpy(out, v, sizeof(v));
+    return ND_OK;
+}
+
+extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, const void *packed, const float *img, float *canvas,
+                                      int width, int height, int cs, int ucs, int ol, int tile_begin, int tile_count, int batch,
+                                      void *ws, size_t ws_bytes, void *fws, size_t fws_bytes, void *stream, nd_progress_fn progress,
+                                      void *progress_ctx) {
+    ND_TRY(nd_check_flags(flags));
+    FramePlan fp;
+    ND_TRY(frame_plan(funit, dtype, flags, width, height, cs, ucs, ol, batch, &fp));
+    if (tile_begin < 0 || tile_count < 0 || tile_begin + tile_count > fp.cols * fp.rows)
+        ND_FAIL(ND_EINVAL, "nd_utnet_denoise_frame: tiles [%d,+%d) outside the grid of %d", tile_begin, tile_count, fp.cols * fp.rows);
+    const int end = tile_begin + tile_count;
+    Plan pl;
+    ND_TRY(forward_common(funit, act, dtype, packed, batch, batch, cs, cs, ws, ws_bytes, &pl));
+    const BlobLayout bl = blob_layout(funit, dtype);
+    Roi rois[kNumSteps];
+    const int crop = (cs - ucs) / 2;
+    if (fp.D && !(plan_rois(pl, crop, crop, rois) && rois_supported(funit, dtype, flags, pl, bl, rois))) fp.D = 0;
+    if (fp.D == 0) {   // every tile runs its whole encoder: launches of `batch` tiles from tile_begin
+        int n = 0;
+        for (int t0 = tile_begin; t0 < end; t0 += batch, ++n) {
+            const int cnt = end - t0 < batch ? end - t0 : batch;
+            if (progress) progress(progress_ctx, n, t0, cnt);
+            ND_TRY(nd_utnet_denoise_tiles(funit, act, dtype, flags, packed, img, canvas, width, height, cs, ucs, ol, t0, cnt, batch, ws,
+                                          ws_bytes, stream));
+        }
+        return ND_OK;
+    }
+    if (!img || !canvas) ND_FAIL(ND_EINVAL, "UtNet: null image");
+    if (!fws || fws_bytes < fp.bytes || ((uintptr_t)fws & 255))
+        ND_FAIL(ND_ENOMEM, "nd_utnet_denoise_frame: frame workspace %zu B given, %zu B needed (256-byte aligned)", fws_bytes, fp.bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const float *blob = (const float *)packed;
+    const float *fw = blob + bl.off[kNumLayers - 1];
+    char *const band_base = (char *)fws, *const sh_base = band_base + fp.band_bytes, *const sv_base = sh_base + fp.strip_bytes;
+    const int f4 = funit / 4, cols = fp.cols, S = fp.S;
+    int n = 0;
+    for (int b = tile_begin / (fp.R * cols); b < fp.nbands && b * fp.R * cols < end; ++b) {
+        const int row0 = b * fp.R, nrows = fp.rows - row0 < fp.R ? fp.rows - row0 : fp.R;
+        const int bt0 = tile_begin > row0 * cols ? tile_begin : row0 * cols, bt1 = end < (row0 + nrows) * cols ? end : (row0 + nrows) * cols;
+        // the band: its rows of tiles on the mirrored frame, steps [0, kSharedSteps) once
+        Plan bp = make_enc_plan(funit, band_hx(fp, nrows, cs), fp.wx, 1, fp.hx, fp.wx, 1, band_base, dtype);
+        bp.split = pl.split;
+        ND_TRY(nd_launch_gather_band(img, width, height, cs, ucs, ol, row0, bp.buf[X0], s));
+        ND_TRY(run_stack(funit, act, dtype, blob, bp, s, flags, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, kSharedSteps));
+        // its tiles in near-equal launches of at most `batch`
+        const int nt = bt1 - bt0, nl = (nt + batch - 1) / batch;
+        for (int j = 0; j < nl; ++j, ++n) {
+            const int t0 = bt0 + (int)((long)nt * j / nl), cnt = bt0 + (int)((long)nt * (j + 1) / nl) - t0;
+            if (progress) progress(progress_ctx, n, t0, cnt);
+            // border strips: images 2t / 2t + 1 = top / bottom rows (sh), left / right columns (sv) of tile t's input
+            Plan sh = make_enc_plan(funit, kStrip, cs + 4, 2 * cnt, kStrip, cs + 4, 2 * batch, sh_base, dtype);
+            Plan sv = make_enc_plan(funit, cs + 4, kStrip, 2 * cnt, cs + 4, kStrip, 2 * batch, sv_base, dtype);
+            sh.split = sv.split = pl.split;
+            ND_TRY(nd_launch_gather_strips(img, width, height, cs, ucs, ol, t0, cnt, false, sh.buf[X0], s));
+            ND_TRY(nd_launch_gather_strips(img, width, height, cs, ucs, ol, t0, cnt, true, sv.buf[X0], s));
+            ND_TRY(run_stack(funit, act, dtype, blob, sh, s, flags, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, kSharedSteps));
+            ND_TRY(run_stack(funit, act, dtype, blob, sv, s, flags, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, kSharedSteps));
+            // per tile: the skip halves over the window the decoder reads, P2 whole, then P2's border lines from the strips
+            const Plan tp = make_plan(funit, cs, cs, batch, cnt, (char *)ws, dtype);
+            ND_TRY(nd_launch_splice(bp.buf[CAT4], f4, tp.buf[CAT4], f4, f4, t0, cnt, cols, row0, S, 0, 0, 0, 0, fp.win4[0], fp.win4[1],
+                                    fp.win4[0], fp.win4[1], s));
+            ND_TRY(nd_launch_splice(bp.buf[CAT3], 2 * f4, tp.buf[CAT3], 2 * f4, 2 * f4, t0, cnt, cols, row0, S / 2, 0, 0, 0, 0, fp.win3[0],
+                                    fp.win3[1], fp.win3[0], fp.win3[1], s));
+            const int n2 = enc_extent(cs + 4, P2);
+            ND_TRY(nd_launch_splice(bp.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, row0, S / 4, 0, 0, 0, 0, 0, n2, 0, n2, s));
+            ND_TRY(nd_launch_splice(sh.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 0, 0, 0, 0, 1, 0, n2, s));
+            ND_TRY(nd_launch_splice(sh.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 1, 1 - n2, 0, n2 - 1, n2, 0, n2, s));
+            ND_TRY(nd_launch_splice(sv.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 0, 0, 0, 0, n2, 0, 1, s));
+            ND_TRY(nd_launch_splice(sv.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 1, 0, 1 - n2, 0, n2, n2 - 1, n2, s));
+            ND_TRY(run_stack(funit, act, dtype, blob, tp, s, flags, nullptr, nullptr, nullptr, nullptr, nullptr, rois, kSharedSteps, kNumSteps));
+            ND_TRY(nd_launch_final1x1_stitch(tp.buf[T4B], funit, fw, fw + 3 * funit, 2, canvas, width, height, cs, ucs, ol, t0, cnt, s));
+        }
+    }
+    return ND_OK;
+}
+
 // Profiling entry point (bench.py roofline leg): one forward of the conv stack with a HIP event between every launch on
 // `stream` (and around the GEMM launch of a three-pass Winograd layer).  Synchronises the stream.  26 entries, forward order:
 // 22 MFMA conv layers and 4 pools.  FLOP conventions: `flops` = algorithmic (torch FlopCounterMode, no

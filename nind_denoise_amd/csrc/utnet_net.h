@@ -368,13 +368,14 @@ inline bool rois_supported(int f, int dt, int flags, const Plan &pl, const BlobL
 // flags: nd_flags of the call (ND_FLAG_NO_SPLITK: every tile whole; ND_FLAG_DIRECT_CONV: no Winograd form on any layer)
 int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStream_t s, int flags = 0, hipEvent_t *ev = nullptr,
               const QpBuf *pre = nullptr, const float *slopes = nullptr, const unsigned char *train_w1 = nullptr,
-              hipEvent_t *ev_x = nullptr, const Roi *rois = nullptr) {
+              hipEvent_t *ev_x = nullptr, const Roi *rois = nullptr, int step_begin = 0, int step_end = kNumSteps) {
     const BlobLayout bl = blob_layout(f, dt, pre == nullptr, pre != nullptr);
     const int cpp = nd_cpp(dt);
-    int si = 0;
+    int si = step_begin;
     bool pool_done = false;   // the previous layer wrote the pooled tensor itself
     QpBuf pool_view;
-    for (const Step &st : kSteps) {
+    for (int k = step_begin; k < step_end; ++k) {
+        const Step &st = kSteps[k];
         if (ev) ND_HIP(hipEventRecord(ev[si], s));
         const int this_step = si++;
         if (st.layer < 0) {
@@ -415,7 +416,7 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
         }
         // MaxPool2d(2) fused into the producing layer's epilogue where its kernel can (conv_w2d, three-pass output transform):
         // the pool kernel re-read the whole skip tensor from HBM (2.4 % of the fp32 conv stack)
-        const bool next_is_pool = this_step + 1 < kNumSteps && kSteps[this_step + 1].layer < 0;
+        const bool next_is_pool = this_step + 1 < step_end && kSteps[this_step + 1].layer < 0;
         const bool w2d = form == FORM_W1D4 && nd_f43_w2d(d.in, d.cout, pre != nullptr, flags);
         if (next_is_pool && !pre && !(flags & ND_FLAG_UNFUSED_POOL)) {
             pool_view = pl.buf[kSteps[this_step + 1].dst];
@@ -458,6 +459,145 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
         ND_TRY(nd_launch_conv(d, s));
     }
     if (ev) ND_HIP(hipEventRecord(ev[si], s));
+    return ND_OK;
+}
+
+// ---------------------------------------------------------------- shared encoder of the fused denoise loop
+// Tiles lie on a grid of stride S = ucs - ol, and every gathered tile is the window of one symmetric-padded frame at its origin.
+// The encoder is a chain of valid 3x3 convolutions and 2x2 pools, so a tile's encoder tensors are windows of the same layers run
+// on a band of tile rows -- where the tile's origin falls on a whole pixel of the level (and a pool's 2x2 phase agrees) -- except
+// on the lines that its own ReflectionPad2d(2) reaches: rows / cols {0, 1, n-2, n-1} of the level-0 outputs, {0, n-1} below.
+// fp32 useful-region mode shares levels 0 and 1 (convs1.0 ... the second pool: the conv_w2d layers, 64 % of the encoder's time at
+// G24) when S % 4 == 0:
+//   * the band runs steps [0, kSharedSteps) once on its window of the mirrored frame;
+//   * the decoder reads neither the contaminated lines of CAT4 nor those of CAT3 (region plan) -- the tile's skip halves are copied
+//     from the band, only over the window the decoder reads;
+//   * P2 (the level-2 input, computed whole per tile) is copied from the band, and its contaminated rows / cols 0 and n-1 are
+//     recomputed exactly from kStrip-pixel strips of the tile's own input (a 16-row strip yields one P2 row through the 6 steps).
+// The deeper levels stay per tile: their exact border lines would need strips of 36 / 76 input rows.
+constexpr int kSharedSteps = 6;
+constexpr int kStrip = 16;
+constexpr double kBandBytes = 8.0 * (1 << 30);   // band tensors per launch of the shared steps (fixes the tile rows per band)
+
+// extent of encoder buffer b (X0 ... P2) for a first-layer input of extent x (X0 = x, valid convs -2, pools /2)
+inline int enc_extent(int x, int b) {
+    const int p1 = (x - 4) / 2;
+    switch (b) {
+        case X0: return x;
+        case A1: return x - 2;
+        case CAT4: return x - 4;
+        case P1: return p1;
+        case A2: return p1 - 2;
+        case CAT3: return p1 - 4;
+        default: return (p1 - 4) / 2;   // P2
+    }
+}
+// X0 ... P2 for B images of hx x wx first-layer input; planes sized for cap images of hcap x wcap (the plane stride does not move
+// when a band or a batch is smaller: plane 1 of X0 and the slack stay zero from the one fill of the workspace)
+Plan make_enc_plan(int f, int hx, int wx, int B, int hcap, int wcap, int cap, char *base, int dt) {
+    Plan p = {};
+    size_t off = 0;
+    auto add = [&](Buf id, int ch, int pad) {
+        QpBuf &q = p.buf[id];
+        q.planes = id == X0 ? 2 : (ch + nd_cpp(dt) - 1) / nd_cpp(dt);
+        q.dt = dt;
+        q.B = B;
+        q.Hb = enc_extent(hx, id) + 2 * pad;
+        q.Wb = enc_extent(wx, id) + 2 * pad;
+        q.pad = pad;
+        q.pstride = (long)cap * (enc_extent(hcap, id) + 2 * pad) * (enc_extent(wcap, id) + 2 * pad);
+        q.base = (float *)(base + off);
+        off += ((size_t)q.planes * q.pstride + nd_buf_slack(enc_extent(wcap, id) + 2 * pad)) * 16;
+        off = (off + 255) & ~(size_t)255;
+    };
+    add(X0, 8, 0);
+    add(A1, f, 0);
+    add(CAT4, 2 * f, 2);
+    add(P1, f, 0);
+    add(A2, 2 * f, 0);
+    add(CAT3, 4 * f, 2);
+    add(P2, 2 * f, 0);
+    p.split = nullptr;
+    p.wino = nullptr;
+    p.bytes = off;
+    return p;
+}
+
+struct FramePlan {
+    int D = 0;         // shared encoder levels (2, or 0: every tile runs its whole encoder)
+    int aligned = 0;   // levels on which every tile origin is a whole pixel: 1 + the power of 2 in S, at most 4
+    int S = 0, cols = 0, rows = 0, pad = 0;
+    int R = 0, nbands = 0;   // tile rows per band, bands
+    int hx = 0, wx = 0;      // first-layer input of a full band
+    int win4[2] = {0, 0}, win3[2] = {0, 0};   // [lo, hi) of the CAT4 / CAT3 skip pixels the decoder reads (both axes)
+    size_t band_bytes = 0, strip_bytes = 0, bytes = 0;
+};
+inline int band_hx(const FramePlan &fp, int nrows, int cs) { return (nrows - 1) * fp.S + cs + 4; }
+
+extern "C" int nd_tile_grid(int W, int H, int cs, int ucs, int ol, int *cols, int *rows, int *pad);
+
+// the band plan: a function of the frame geometry, the dtype and the flags (batch only sizes the strip buffers)
+int frame_plan(int f, int dt, int flags, int W, int H, int cs, int ucs, int ol, int batch, FramePlan *fp) {
+    *fp = FramePlan();
+    ND_TRY(check_funit(f, dt));
+    if (!valid_cs(cs)) ND_FAIL(ND_EINVAL, "frame plan: tile size %d", cs);
+    ND_TRY(nd_tile_grid(W, H, cs, ucs, ol, &fp->cols, &fp->rows, &fp->pad));
+    fp->S = ucs - ol;
+    fp->aligned = 1;
+    while (fp->aligned < 4 && fp->S % (1 << fp->aligned) == 0) ++fp->aligned;
+    // a tile origin must fall on a whole pixel of level 2 (the pooled input P2 is copied from the band), the arithmetic must be
+    // the fp32 F(4,3) layers this plan was built for, and the decoder must leave the contaminated skip lines unread
+    if (dt != ND_F32 || (flags & (ND_FLAG_FULL_TILES | ND_FLAG_TILE_ENCODER | ND_FLAG_DIRECT_CONV | ND_FLAG_W1D_REGS)) ||
+        fp->S % 4 || W < cs || H < cs || batch <= 0)
+        return ND_OK;
+    const Plan tp = make_plan(f, cs, cs, 1, 1, nullptr, dt);
+    const BlobLayout bl = blob_layout(f, dt);
+    Roi rois[kNumSteps];
+    const int crop = (cs - ucs) / 2;
+    if (!plan_rois(tp, crop, crop, rois)) return ND_OK;   // (the executor also checks that the kernels take them: rois_supported)
+    for (int i = 0; i < kNumSteps; ++i) {
+        const Step &st = kSteps[i];
+        if (st.layer < 0 || (st.src != CAT4 && st.src != CAT3) || kLayers[st.layer].kind != ND_CONVT3) continue;
+        const int n = enc_extent(cs + 4, st.src), edge = st.src == CAT4 ? 2 : 1;
+        if (rois[i].rows <= 0 || rois[i].r0 != rois[i].c0 || rois[i].rows != rois[i].cols) return ND_OK;
+        int *w = st.src == CAT4 ? fp->win4 : fp->win3;
+        w[0] = rois[i].r0 - 2 < 0 ? 0 : rois[i].r0 - 2;   // a transposed 3x3 layer reads input rows [lo - 2, hi) for output rows [lo, hi)
+        w[1] = rois[i].r0 + rois[i].rows > n ? n : rois[i].r0 + rois[i].rows;
+        if (w[0] < edge || w[1] > n - edge) return ND_OK;
+    }
+    if (fp->win4[1] <= fp->win4[0] || fp->win3[1] <= fp->win3[0]) return ND_OK;
+    // tile rows per band: as many as kBandBytes holds
+    fp->wx = (fp->cols - 1) * fp->S + cs + 4;
+    for (int R = fp->rows; R >= 1; --R) {
+        const int hx = band_hx(*fp, R, cs);
+        const size_t b = make_enc_plan(f, hx, fp->wx, 1, hx, fp->wx, 1, nullptr, dt).bytes;
+        if (b <= kBandBytes || R == 1) {
+            fp->R = R;
+            fp->hx = hx;
+            fp->band_bytes = b;
+            break;
+        }
+    }
+    // as few bands as that allows, of near-equal height (a short last band would repeat the band border for few tiles)
+    fp->nbands = (fp->rows + fp->R - 1) / fp->R;
+    fp->R = (fp->rows + fp->nbands - 1) / fp->nbands;
+    fp->hx = band_hx(*fp, fp->R, cs);
+    fp->band_bytes = make_enc_plan(f, fp->hx, fp->wx, 1, fp->hx, fp->wx, 1, nullptr, dt).bytes;
+    if ((long)fp->hx * fp->wx >= (1L << 26)) return ND_OK;   // (32-bit offsets of the conv kernels on a band image)
+    // every shared step of the band and of both strip shapes must run in conv_w2d (its pool epilogue included)
+    const Plan plans[3] = {make_enc_plan(f, fp->hx, fp->wx, 1, fp->hx, fp->wx, 1, nullptr, dt),
+                           make_enc_plan(f, kStrip, cs + 4, 2, kStrip, cs + 4, 2, nullptr, dt),
+                           make_enc_plan(f, cs + 4, kStrip, 2, cs + 4, kStrip, 2, nullptr, dt)};
+    for (const Plan &pp : plans)
+        for (int i = 0; i < kSharedSteps; ++i) {
+            const Step &st = kSteps[i];
+            if (st.layer < 0) continue;
+            if (step_form(st, f, dt, flags, pp, bl, false, nullptr) != FORM_W1D4 || !nd_f43_w2d(pp.buf[st.src], lcout(kLayers[st.layer], f), false, flags))
+                return ND_OK;
+        }
+    fp->strip_bytes = make_enc_plan(f, kStrip, cs + 4, 2 * batch, kStrip, cs + 4, 2 * batch, nullptr, dt).bytes;
+    fp->bytes = fp->band_bytes + 2 * fp->strip_bytes;
+    fp->D = 2;
     return ND_OK;
 }
 

@@ -122,11 +122,14 @@ class UtNet(nn.Module):
     #   useful_only = False -> the fused denoise loop computes whole tiles in every layer (as forward() always does) instead of
     #                          only what the useful centre of a tile depends on in the last decoder levels (same canvas)
     #   fused_pool = False -> A/B switch: every MaxPool2d(2) as its own kernel instead of from the producing layer's epilogue (same values)
+    #   share_encoder = False -> A/B switch: the fused frame loop runs every tile's whole encoder instead of the first two levels
+    #                            once per band of tile rows (fp32 useful-region mode; same canvas up to fp32 re-association)
     split_k = True
     winograd = True
     w1d_regs = False
     useful_only = True
     fused_pool = True
+    share_encoder = True
 
     def __init__(self, funit=64, activation='PReLU'):
         super().__init__()
@@ -180,7 +183,7 @@ class UtNet(nn.Module):
     def flags(self):
         return ((0 if self.split_k else _lib.FLAG_NO_SPLITK) | (0 if self.winograd else _lib.FLAG_DIRECT_CONV) |
                 (_lib.FLAG_W1D_REGS if self.w1d_regs else 0) | (0 if self.useful_only else _lib.FLAG_FULL_TILES) |
-                (0 if self.fused_pool else _lib.FLAG_UNFUSED_POOL))
+                (0 if self.fused_pool else _lib.FLAG_UNFUSED_POOL) | (0 if self.share_encoder else _lib.FLAG_TILE_ENCODER))
 
     # ------------------------------------------------------------------ weights
     def _weights_key(self, device):
@@ -239,6 +242,22 @@ class UtNet(nn.Module):
             ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
             _lib.check(lib.nd_utnet_workspace_init_hw(ws.data_ptr(), nbytes, self.funit, h, w, batch, self._dt,
                                                       _lib.stream_ptr(device)), "nd_utnet_workspace_init")
+            self._workspaces[key] = ws
+        return ws
+
+    def frame_workspace(self, width, height, cs, ucs, ol, batch, device):
+        """Band and strip buffers of the shared encoder for one frame geometry (nd_utnet_frame_workspace_bytes; zero-filled once,
+        then cached with the activation workspaces), or None where the frame loop runs every tile's whole encoder."""
+        lib = _lib.load()
+        nbytes = lib.nd_utnet_frame_workspace_bytes(self.funit, self._dt, self.flags, width, height, cs, ucs, ol, batch)
+        if nbytes == 0:
+            return None
+        key = (str(device), "frame", nbytes)
+        ws = self._workspaces.get(key)
+        if ws is None:
+            for k in [k for k in self._workspaces if k[1] == "frame"]:   # one frame workspace at a time
+                del self._workspaces[k]
+            ws = torch.zeros(nbytes, dtype=torch.uint8, device=device)
             self._workspaces[key] = ws
         return ws
 

@@ -2,9 +2,9 @@
 
 The frame stays in HBM as float32 CHW; tiles are gathered, denoised and stitched on the GPU in batches,
 in ascending tile index order (the reference's fp32 summation order), with no host synchronisation
-inside the loop.  For ``UtNet`` the three stages are fused by ``nd_utnet_denoise_tiles`` (no NCHW tile
-batch is ever materialised); any other callable model goes through ``nd_tile_gather`` -> model ->
-``nd_stitch_add``.
+inside the loop.  For ``UtNet`` the three stages are fused by ``nd_utnet_denoise_frame`` (no NCHW tile
+batch is ever materialised; in fp32 the first two encoder levels run once per band of tile rows); any
+other callable model goes through ``nd_tile_gather`` -> model -> ``nd_stitch_add``.
 """
 import torch
 
@@ -54,24 +54,27 @@ def denoise_frame(model, img, cs, ucs, ol, batch=16, tile_range=None, canvas=Non
     if canvas is None:
         canvas = torch.zeros_like(img)
     lib = _lib.load()
-    fused = isinstance(model, UtNet)
     with torch.cuda.device(img.device):
-        if fused:
-            batch = max(1, min(batch, end - begin)) if end > begin else 1
+        if isinstance(model, UtNet):
+            if end <= begin:
+                return canvas
+            # one call for the whole range: the library walks it band by band (nd_utnet_denoise_frame), in launches of <= batch
+            batch = max(1, min(batch, end - begin))
             blob = model.packed_weights(img.device)
             ws = model.workspace(cs, batch, img.device)
-            stream = _lib.stream_ptr(img.device)
+            fws = model.frame_workspace(width, height, cs, ucs, ol, batch, img.device)
+            cb = _lib.PROGRESS_FN(lambda _ctx, n, t0, cnt: progress(n, t0, cnt)) if progress is not None else _lib.PROGRESS_FN()
+            _lib.check(lib.nd_utnet_denoise_frame(model.funit, _lib.ACT[model.activation], _lib.DTYPE[model.compute_dtype], model.flags,
+                                                  blob.data_ptr(), img.data_ptr(), canvas.data_ptr(), width, height, cs, ucs, ol,
+                                                  begin, end - begin, batch, ws.data_ptr(), ws.numel(),
+                                                  fws.data_ptr() if fws is not None else None, fws.numel() if fws is not None else 0,
+                                                  _lib.stream_ptr(img.device), cb, None), "nd_utnet_denoise_frame")
+            return canvas
         for n, t0 in enumerate(range(begin, end, batch)):
             cnt = min(batch, end - t0)
             if progress is not None:
                 progress(n, t0, cnt)
-            if fused:
-                _lib.check(lib.nd_utnet_denoise_tiles(model.funit, _lib.ACT[model.activation], _lib.DTYPE[model.compute_dtype],
-                                                      model.flags, blob.data_ptr(), img.data_ptr(), canvas.data_ptr(), width, height,
-                                                      cs, ucs, ol, t0, cnt, batch, ws.data_ptr(), ws.numel(), stream),
-                           "nd_utnet_denoise_tiles")
-            else:
-                x = gather_tiles(img, cs, ucs, ol, t0, cnt)
-                y = model(x)
-                stitch_tiles(canvas, y, cs, ucs, ol, t0)
+            x = gather_tiles(img, cs, ucs, ol, t0, cnt)
+            y = model(x)
+            stitch_tiles(canvas, y, cs, ucs, ol, t0)
     return canvas
