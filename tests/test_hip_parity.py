@@ -21,6 +21,21 @@ ABS_TOL = 1e-3
 REL_TOL = 1e-3
 
 
+def _shared_encoder_tests():
+    import importlib.util
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "test_shared_encoder.py")
+    spec = importlib.util.spec_from_file_location("_shared_encoder_bars", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+# weights whose deep levels reach the output (synth gain; at 1.0 an error below level 1 moves the output by < 2e-8) and the fp32 bar
+# of a whole UtNet(64) tile against float64 there, relative to max(1, max|ref|): defined and gated in test_shared_encoder.py
+_SE = _shared_encoder_tests()
+VISIBLE_GAIN, BAR_NET64 = _SE.VISIBLE_GAIN, _SE.BAR_NET64
+
+
 @pytest.fixture(scope="module")
 def dev():
     if not torch.cuda.is_available():
@@ -459,12 +474,27 @@ def test_utnet_f64_winograd_tile_remainders(dev):
     net = UtNet()
     net.load_state_dict(sd)
     net = net.eval().to(dev)
-    for (h, w), B in (((120, 120), 3), ((136, 136), 1), ((152, 152), 5), ((200, 200), 2), ((152, 104), 2), ((104, 216), 1)):
+    shapes = (((120, 120), 3), ((136, 136), 1), ((152, 152), 5), ((200, 200), 2), ((152, 104), 2), ((104, 216), 1))
+    for (h, w), B in shapes:
         x = torch.rand(B, 3, h, w, generator=torch.Generator().manual_seed(h + w))
         with torch.no_grad():
             ref = onet.utnet_forward(sd, x)
         err = assert_close(net(x.to(dev)), ref, f"f64 {h}x{w} batch {B}")
         assert err <= 2e-6 * max(1.0, ref.abs().max().item()), (h, w, err)     # measured ~1e-7: the fp32 path, not just the 1e-3 bar
+    # the same shapes at visible weights, against float64
+    sd = synth.make_utnet_state_dict(funit=64, seed=7, gain=VISIBLE_GAIN)
+    net.load_state_dict(sd)
+    sd64 = {k: v.double() for k, v in sd.items()}
+    errs = []
+    for (h, w), B in shapes:
+        x = torch.rand(B, 3, h, w, generator=torch.Generator().manual_seed(h + w))
+        with torch.no_grad():
+            ref = onet.utnet_forward(sd64, x.double())
+        y = net(x.to(dev)).double().cpu()
+        assert torch.isfinite(y).all()
+        errs.append((y - ref).abs().max().item() / max(1.0, ref.abs().max().item()))
+    print(f"UtNet(64) gain {VISIBLE_GAIN} Winograd remainders vs float64: " + ", ".join(f"{s[0][0]}x{s[0][1]} {e:.2e}" for s, e in zip(shapes, errs)))
+    assert max(errs) <= BAR_NET64, errs
 
 
 def test_device_packed_weights_equal_host_packed(dev):
@@ -734,6 +764,9 @@ def test_cli_debug_crop_dumps(dev, tmp_path, monkeypatch):
     assert os.path.isfile(str(tmp_path / "b.tiff") + "dbg_inclborders.tif")
 
 
+WIDE_PSNR_VISIBLE = {"f16": 74.0, "bf16": 56.0}    # 16-bit storage at VISIBLE_GAIN vs float64 (measured 77.5 / 59.7 dB)
+
+
 @pytest.mark.parametrize("cs", [504, 520])
 def test_utnet_f64_wide_tiles_vs_oracle(dev, cs):
     # the shipped default tile (cs=504, denoise_image.py:41) and BASELINE config 4's cs=520: rows too wide for three
@@ -755,6 +788,21 @@ def test_utnet_f64_wide_tiles_vs_oracle(dev, cs):
         mse = ((y - ref) ** 2).mean().item()
         psnr = 10 * np.log10((ref.max() - ref.min()).item() ** 2 / max(mse, 1e-30))
         print(f"UtNet(64) cs={cs} {dtype}: PSNR {psnr:.1f} dB, max abs err {(y - ref).abs().max().item():.3e}")
+        assert torch.isfinite(y).all() and psnr >= min_psnr, (dtype, cs, psnr)
+    net.set_compute_dtype("f32")
+    # visible weights against float64: fp32 within BAR_NET64, 16-bit storage by PSNR (peak = the reference's range)
+    sd = synth.make_utnet_state_dict(funit=64, seed=123, gain=VISIBLE_GAIN)
+    net.load_state_dict(sd)
+    with torch.no_grad():
+        ref = onet.utnet_forward({k: v.double() for k, v in sd.items()}, x.double())
+    y = net(x.to(dev)).double().cpu()
+    err = (y - ref).abs().max().item() / max(1.0, ref.abs().max().item())
+    print(f"UtNet(64) gain {VISIBLE_GAIN} cs={cs} fp32 vs float64: {err:.2e}")
+    assert torch.isfinite(y).all() and err <= BAR_NET64, err
+    for dtype, min_psnr in (("f16", WIDE_PSNR_VISIBLE["f16"]), ("bf16", WIDE_PSNR_VISIBLE["bf16"])):
+        y = net.set_compute_dtype(dtype)(x.to(dev)).double().cpu()
+        psnr = 10 * np.log10((ref.max() - ref.min()).item() ** 2 / max(((y - ref) ** 2).mean().item(), 1e-30))
+        print(f"UtNet(64) gain {VISIBLE_GAIN} cs={cs} {dtype}: PSNR {psnr:.1f} dB vs float64")
         assert torch.isfinite(y).all() and psnr >= min_psnr, (dtype, cs, psnr)
     net.set_compute_dtype("f32")
 
