@@ -73,7 +73,7 @@ typedef enum nd_flags {
                                  the network output before the canvas +=) -- same canvas, 19 % less work at cs 264 / ucs 200    */
 } nd_flags;
 
-int nd_version(void);   /* 105 = this header */
+int nd_version(void);   /* 106 = this header */
 const char *nd_last_error(void);
 
 /* ---------------------------------------------------------------- tile geometry (host, pure integer)
@@ -109,17 +109,15 @@ size_t nd_utnet_packed_bytes(int funit, int dtype);
 int nd_utnet_pack_weights(int funit, int dtype, const float *const *tensors, int n_tensors,
                           void *packed_host, size_t packed_bytes);
 
-/* Workspace for one (cs, batch) geometry: activations in the quad-planar layout, zero borders included.
- * nd_utnet_workspace_init must run once on a workspace before its first forward with that geometry. */
 /* The same blob built in HBM from tensors that already live there (fp32 storage only): device-side packers; the Winograd
  * weight transforms are evaluated in fp32 instead of double (packed values agree to ~1e-7 relative).  Stream-ordered. */
 int nd_utnet_pack_weights_device(int funit, int dtype, const float *const *dev_tensors, int n_tensors, void *packed_dev,
                                  size_t packed_bytes, void *stream);
-size_t nd_utnet_workspace_bytes(int funit, int cs, int batch, int dtype);
-int nd_utnet_workspace_init(void *workspace, size_t workspace_bytes, int funit, int cs, int batch, int dtype,
-                            void *stream);
 
-/* Non-square inputs (the --whole_image branch, denoise_image.py:110-128): h and w must each be of the form 16k+56. */
+/* UtNet.forward (UtNet.py:97-109): x_nchw [batch,3,h,w] -> y_nchw [batch,3,h,w], both float32 in HBM; h and w are each of the
+ * form 16k+56 (h = w = cs for the tiles of the denoise loop; the --whole_image branch, denoise_image.py:110-128, passes a whole
+ * image).  The workspace holds the activations of one (h, w, batch) geometry in the quad-planar layout, zero borders included;
+ * nd_utnet_workspace_init_hw must run once on it before its first forward with that geometry. */
 size_t nd_utnet_workspace_bytes_hw(int funit, int h, int w, int batch, int dtype);
 int nd_utnet_workspace_init_hw(void *workspace, size_t workspace_bytes, int funit, int h, int w, int batch, int dtype,
                                void *stream);
@@ -127,14 +125,9 @@ int nd_utnet_forward_hw(int funit, int act, int dtype, int flags, const void *pa
                         const float *x_nchw, float *y_nchw, int batch, int h, int w,
                         void *workspace, size_t workspace_bytes, void *stream);
 
-/* UtNet.forward (UtNet.py:97-109): x_nchw [batch,3,cs,cs] -> y_nchw [batch,3,cs,cs], both float32 in HBM. */
-int nd_utnet_forward(int funit, int act, int dtype, int flags, const void *packed_dev,
-                     const float *x_nchw, float *y_nchw, int batch, int cs,
-                     void *workspace, size_t workspace_bytes, void *stream);
-
 /* The whole hot loop of denoise_image.py:240-267 for tiles [tile_begin, tile_begin+tile_count) of one frame,
  * device resident: gather(+mirror) -> UtNet -> useful crop -> seamless edges -> canvas +=.
- * tile_count <= batch of the workspace.  Equivalent to nd_tile_gather + nd_utnet_forward + nd_stitch_add
+ * tile_count <= batch of the workspace.  Equivalent to nd_tile_gather + nd_utnet_forward_hw + nd_stitch_add
  * without materialising the NCHW tile batch. */
 int nd_utnet_denoise_tiles(int funit, int act, int dtype, int flags, const void *packed_dev,
                            const float *img_chw, float *canvas_chw, int width, int height,
@@ -181,7 +174,7 @@ typedef struct nd_step_profile {
     double xform_bytes_out;
 } nd_step_profile;
 /* crop: margin of the useful tile centre the caller will keep ((cs - ucs) / 2 of the denoise loop; 0: the whole output, as
- * nd_utnet_forward computes it) -- the stack then runs exactly as inside nd_utnet_denoise_tiles with the same flags */
+ * nd_utnet_forward_hw computes it) -- the stack then runs exactly as inside nd_utnet_denoise_tiles with the same flags */
 int nd_utnet_profile_stack(int funit, int act, int dtype, int flags, const void *packed_dev, int batch, int cs, int crop,
                            void *workspace, size_t workspace_bytes, void *stream, nd_step_profile *steps, int max_steps);
 const char *nd_utnet_step_name(int i);
@@ -230,65 +223,51 @@ size_t nd_layer_wgrad_workspace_bytes(int kind, int batch, int cin, int cout, in
 int nd_layer_wgrad(int kind, const float *x_nchw, const float *dy_nchw, int batch, int cin, int h, int w, int cout,
                    float *dw, float *db, void *workspace, size_t workspace_bytes, void *stream);
 
-/* UtNet training step (BASELINE config 5; nn_train.py:308-380, nn_common.py:198-255), PReLU networks, fp32.
- * Parameters and gradients are flat float buffers in state-dict order (nd_utnet_tensor_name / nd_utnet_param_range):
- * one buffer for the data-parallel all-reduce and for the optimizer.  nd_utnet_train_step = device-side weight
- * packing + forward + loss + backward:
+/* UtNet training step (BASELINE config 5; nn_train.py:308-380, nn_common.py:198-255), fp32, on crops of h x w pixels (each
+ * side 16k+56, e.g. 136 / 184).  Parameters and gradients are flat float buffers in state-dict order (nd_utnet_tensor_name /
+ * nd_utnet_param_range): one buffer for the data-parallel all-reduce and for the optimizer.  x, target, y_out, gy, dx:
+ * [batch,3,h,w] NCHW fp32 in HBM.  The workspace holds one (h, w, batch) geometry; nd_utnet_train_workspace_init_hw zero-fills
+ * it once before its first use.  blobs: nd_utnet_train_blob_bytes of packed weights.
+ *
+ * nd_utnet_train_step_hw = device-side weight packing + forward + loss + backward of a PReLU network:
  *     loss = w_l1 * mean|g - t| + w_mse * mean (g - t)^2 + w_ssim * mean_n(1 - SSIM_n(g, t))
  *            + w_msssim * mean_n(1 - MS-SSIM_n(g, t)),        g = clip(net(x), 0, 1), t = target   (nn_common.py:198-241;
- *     the SSIM terms as in nd_ssim_loss_grad; MS-SSIM needs cs >= 161, so it cannot be used on 136-pixel crops)
- * x, target, y_out: [batch,3,cs,cs] NCHW fp32 in HBM (cs = 16k+56, e.g. 136 / 184); loss_out: one float in HBM.
- * loss_cs: the criteria see the centre crop of loss_cs x loss_cs pixels of output and target (pt_ops.pt_crop_batch,
- * nn_train.py:319-323; --loss_cs); the gradient is zero outside it.  0 or cs: the whole output.
+ *     the SSIM terms as in nd_ssim_loss_grad; MS-SSIM needs a loss crop of at least 161 pixels)
+ * loss_out: one float in HBM.  loss_cs > 0: the criteria see the centre loss_cs x loss_cs crop at y0 = (h - loss_cs) / 2,
+ * x0 = (w - loss_cs) / 2 of output and target (pt_ops.pt_crop_batch, nn_train.py:319-323; --loss_cs), and the gradient is zero
+ * outside it; 0: the whole output.
+ *
+ * The two halves of the step for torch.autograd, so that the reference's own training statements
+ * (nn_common.py:198-218: `self.model(noisy_batch).clip(0,1)`, `loss.backward()`) run unchanged on the module:
+ * nd_utnet_train_forward_hw = device-side weight packing + forward with the pre-activations kept in `workspace`;
+ * nd_utnet_train_backward_hw = the whole backward from gy = d loss / d output.  grads (nullable) = the flat parameter
+ * gradients -- null skips every parameter-gradient launch and bucket event (a frozen network costs forward + data gradients
+ * only); dx_nchw (nullable) = d loss / d x, the first layer's data gradient through the ReflectionPad2d(2) of the input; at
+ * least one of the two.  act: ND_ACT_PRELU | ND_ACT_ELU | ND_ACT_HARDSWISH (networks/UtNet.py:17-26; tensors of the parameter
+ * layout that the activation does not have -- PReLU slopes -- are ignored and their gradients left untouched).  `workspace`
+ * and `blobs` carry the forward's state to the backward call: nothing else may use them in between.
+ *
  * nd_adam_step = torch.optim.Adam(lr, betas, eps, amsgrad) on the flat buffers (nn_common.py:185). */
 size_t nd_utnet_param_count(int funit);
 int nd_utnet_param_range(int funit, int tensor_idx, size_t *offset, size_t *count);
 size_t nd_utnet_train_blob_bytes(int funit);
-size_t nd_utnet_train_workspace_bytes(int funit, int cs, int batch);
-int nd_utnet_train_workspace_init(void *workspace, size_t workspace_bytes, int funit, int cs, int batch, void *stream);
-int nd_utnet_train_step(int funit, int flags, const float *params, float *grads, void *blobs, const float *x_nchw,
-                        const float *target_nchw, float *y_out_nchw, float w_l1, float w_mse, float w_ssim, float w_msssim,
-                        float *loss_out, int batch, int cs, int loss_cs, void *workspace, size_t workspace_bytes, void *stream);
-/* The two halves of the step for torch.autograd, so that the reference's own training statements
- * (nn_common.py:198-218: `self.model(noisy_batch).clip(0,1)`, `loss.backward()`) run unchanged on the module:
- * nd_utnet_train_forward = device-side weight packing + forward with the pre-activations kept in `workspace`;
- * nd_utnet_train_backward = the whole backward from gy = d loss / d output [batch,3,cs,cs] into the flat gradient buffer.
- * act: ND_ACT_PRELU | ND_ACT_ELU | ND_ACT_HARDSWISH (networks/UtNet.py:17-26; tensors of the parameter layout that the
- * activation does not have -- PReLU slopes -- are ignored and their gradients left untouched).  `workspace` and `blobs`
- * carry the forward's state to the backward call: nothing else may use them in between.  These square-crop forms produce
- * the parameter gradients only. */
-int nd_utnet_train_forward(int funit, int act, int flags, const float *params, void *blobs, const float *x_nchw, float *y_out_nchw,
-                           int batch, int cs, void *workspace, size_t workspace_bytes, void *stream);
-int nd_utnet_train_backward(int funit, int act, int flags, const float *params, float *grads, void *blobs, const float *gy_nchw,
-                            int batch, int cs, void *workspace, size_t workspace_bytes, void *stream, void *const *bucket_events,
-                            int n_events);
-/* The same on h x w crops (each side 16k+56; with h = w = cs the square entry points above are these, bit for bit).
- * nd_utnet_train_backward_hw: grads (nullable) = the flat parameter gradients -- null skips every parameter-gradient launch
- * and bucket event (a frozen network costs forward + data gradients only); dx_nchw (nullable) = d loss / d x [batch,3,h,w],
- * the first layer's data gradient through the ReflectionPad2d(2) of the input; at least one of the two.
- * nd_utnet_train_step_hw: nd_utnet_train_step_ev on h x w crops, bucket_events nullable; loss_cs > 0 crops an
- * loss_cs x loss_cs square at y0 = (h - loss_cs) / 2, x0 = (w - loss_cs) / 2 (pt_ops.pt_crop_batch), 0 = the whole output. */
 size_t nd_utnet_train_workspace_bytes_hw(int funit, int h, int w, int batch);
 int nd_utnet_train_workspace_init_hw(void *workspace, size_t workspace_bytes, int funit, int h, int w, int batch, void *stream);
+int nd_utnet_train_step_hw(int funit, int flags, const float *params, float *grads, void *blobs, const float *x_nchw,
+                           const float *target_nchw, float *y_out_nchw, float w_l1, float w_mse, float w_ssim, float w_msssim,
+                           float *loss_out, int batch, int h, int w, int loss_cs, void *workspace, size_t workspace_bytes,
+                           void *stream, void *const *bucket_events, int n_events);
 int nd_utnet_train_forward_hw(int funit, int act, int flags, const float *params, void *blobs, const float *x_nchw,
                               float *y_out_nchw, int batch, int h, int w, void *workspace, size_t workspace_bytes, void *stream);
 int nd_utnet_train_backward_hw(int funit, int act, int flags, const float *params, float *grads, void *blobs, const float *gy_nchw,
                                float *dx_nchw, int batch, int h, int w, void *workspace, size_t workspace_bytes, void *stream,
                                void *const *bucket_events, int n_events);
-int nd_utnet_train_step_hw(int funit, int flags, const float *params, float *grads, void *blobs, const float *x_nchw,
-                           const float *target_nchw, float *y_out_nchw, float w_l1, float w_mse, float w_ssim, float w_msssim,
-                           float *loss_out, int batch, int h, int w, int loss_cs, void *workspace, size_t workspace_bytes,
-                           void *stream, void *const *bucket_events, int n_events);
 /* Data-parallel training that overlaps the gradient reduction with the backward pass (BASELINE configs[4]): the flat gradient
  * buffer is cut into nd_utnet_grad_buckets = 9 contiguous ranges, one per decoder / encoder level, numbered in the order the
- * backward pass completes them; bucket_events[k] (hipEvent_t, nullable array) is recorded on `stream` when bucket k is final,
- * so a reducer on another stream can all-reduce it under the backward of the shallower levels.  nd_utnet_train_step_ev = the
- * fused step with those events. */
+ * backward pass completes them.  bucket_events of nd_utnet_train_step_hw / nd_utnet_train_backward_hw: null, or n_events = 9
+ * hipEvent_t; bucket_events[k] is recorded on `stream` when bucket k is final, so a reducer on another stream can all-reduce it
+ * under the backward of the shallower levels. */
 int nd_utnet_grad_buckets(int funit, size_t *offsets, size_t *counts, int max);
-int nd_utnet_train_step_ev(int funit, int flags, const float *params, float *grads, void *blobs, const float *x_nchw,
-                           const float *target_nchw, float *y_out_nchw, float w_l1, float w_mse, float w_ssim, float w_msssim,
-                           float *loss_out, int batch, int cs, int loss_cs, void *workspace, size_t workspace_bytes, void *stream,
-                           void *const *bucket_events, int n_events);
 int nd_adam_step(float *params, const float *grads, float *m, float *v, float *vmax, size_t n, float lr, float beta1,
                  float beta2, float eps, int step, int amsgrad, void *stream);
 

@@ -51,12 +51,9 @@ _SIGNATURES = {
     "nd_utnet_packed_bytes": (c_size_t, [c_int, c_int]),
     "nd_utnet_pack_weights": (c_int, [c_int, c_int, POINTER(c_void_p), c_int, c_void_p, c_size_t]),
     "nd_utnet_pack_weights_device": (c_int, [c_int, c_int, POINTER(c_void_p), c_int, c_void_p, c_size_t, c_void_p]),
-    "nd_utnet_workspace_bytes": (c_size_t, [c_int] * 4),
-    "nd_utnet_workspace_init": (c_int, [c_void_p, c_size_t] + [c_int] * 4 + [c_void_p]),
     "nd_utnet_workspace_bytes_hw": (c_size_t, [c_int] * 5),
     "nd_utnet_workspace_init_hw": (c_int, [c_void_p, c_size_t] + [c_int] * 5 + [c_void_p]),
     "nd_utnet_forward_hw": (c_int, [c_int] * 4 + [c_void_p] * 3 + [c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "nd_utnet_forward": (c_int, [c_int] * 4 + [c_void_p] * 3 + [c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "nd_utnet_denoise_tiles": (c_int, [c_int] * 4 + [c_void_p] * 3 + [c_int] * 8 + [c_void_p, c_size_t, c_void_p]),
     "nd_unet_num_tensors": (c_int, []),
     "nd_unet_tensor_name": (c_char_p, [c_int]),
@@ -89,17 +86,7 @@ _SIGNATURES = {
     "nd_utnet_param_count": (c_size_t, [c_int]),
     "nd_utnet_param_range": (c_int, [c_int, c_int, POINTER(c_size_t), POINTER(c_size_t)]),
     "nd_utnet_train_blob_bytes": (c_size_t, [c_int]),
-    "nd_utnet_train_workspace_bytes": (c_size_t, [c_int] * 3),
-    "nd_utnet_train_workspace_init": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
-    "nd_utnet_train_step": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
-                                    c_float, c_float, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "nd_utnet_train_forward": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
-    "nd_utnet_train_backward": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t,
-                                        c_void_p, POINTER(c_void_p), c_int]),
     "nd_utnet_grad_buckets": (c_int, [c_int, POINTER(c_size_t), POINTER(c_size_t), c_int]),
-    "nd_utnet_train_step_ev": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
-                                       c_float, c_float, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, POINTER(c_void_p),
-                                       c_int]),
     "nd_utnet_train_workspace_bytes_hw": (c_size_t, [c_int] * 4),
     "nd_utnet_train_workspace_init_hw": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_void_p]),
     "nd_utnet_train_forward_hw": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,

@@ -103,15 +103,7 @@ extern "C" size_t nd_utnet_workspace_bytes_hw(int funit, int h, int w, int batch
     if (check_net(funit, h, w, batch, dtype) != ND_OK) return 0;
     return make_plan(funit, h, w, batch, batch, nullptr, dtype).bytes;
 }
-extern "C" size_t nd_utnet_workspace_bytes(int funit, int cs, int batch, int dtype) {
-    return nd_utnet_workspace_bytes_hw(funit, cs, cs, batch, dtype);
-}
 
-extern "C" int nd_utnet_workspace_init_hw(void *ws, size_t ws_bytes, int funit, int h, int w, int batch, int dtype,
-                                          void *stream);
-extern "C" int nd_utnet_workspace_init(void *ws, size_t ws_bytes, int funit, int cs, int batch, int dtype, void *stream) {
-    return nd_utnet_workspace_init_hw(ws, ws_bytes, funit, cs, cs, batch, dtype, stream);
-}
 extern "C" int nd_utnet_workspace_init_hw(void *ws, size_t ws_bytes, int funit, int h, int w, int batch, int dtype,
                                           void *stream) {
     ND_TRY(check_net(funit, h, w, batch, dtype));
@@ -135,12 +127,6 @@ static int forward_common(int funit, int act, int dtype, const void *packed, int
 }
 
 extern "C" int nd_utnet_forward_hw(int funit, int act, int dtype, int flags, const void *packed, const float *x, float *y,
-                                   int batch, int h, int w, void *ws, size_t ws_bytes, void *stream);
-extern "C" int nd_utnet_forward(int funit, int act, int dtype, int flags, const void *packed, const float *x, float *y,
-                                int batch, int cs, void *ws, size_t ws_bytes, void *stream) {
-    return nd_utnet_forward_hw(funit, act, dtype, flags, packed, x, y, batch, cs, cs, ws, ws_bytes, stream);
-}
-extern "C" int nd_utnet_forward_hw(int funit, int act, int dtype, int flags, const void *packed, const float *x, float *y,
                                    int batch, int h, int w, void *ws, size_t ws_bytes, void *stream) {
     ND_TRY(nd_check_flags(flags));
     Plan pl;
@@ -149,7 +135,9 @@ extern "C" int nd_utnet_forward_hw(int funit, int act, int dtype, int flags, con
     hipStream_t s = (hipStream_t)stream;
     const float *blob = (const float *)packed;
     ND_TRY(nd_launch_reflect_pack(x, batch, h, w, pl.buf[X0], s));
-    ND_TRY(run_stack(funit, act, dtype, blob, pl, s, flags));
+    StackOpts o;
+    o.flags = flags;
+    ND_TRY(run_stack(funit, act, dtype, blob, pl, s, o));
     const BlobLayout bl = blob_layout(funit, dtype);
     const float *fw = blob + bl.off[kNumLayers - 1];
     ND_TRY(nd_launch_final1x1(pl.buf[T4B], funit, fw, fw + 3 * funit, 2, y, h, w, s));
@@ -170,10 +158,11 @@ extern "C" int nd_utnet_denoise_tiles(int funit, int act, int dtype, int flags, 
     // only the useful centre [pad, cs - pad) of a tile reaches the canvas (k_final1x1_stitch reads nothing else): the last decoder
     // levels compute just what that centre depends on
     Roi rois[kNumSteps];
-    const Roi *use = nullptr;
+    StackOpts o;
+    o.flags = flags;
     const int crop = (cs - ucs) / 2;
-    if (!(flags & ND_FLAG_FULL_TILES) && plan_rois(pl, crop, crop, rois) && rois_supported(funit, dtype, flags, pl, bl, rois)) use = rois;
-    ND_TRY(run_stack(funit, act, dtype, blob, pl, s, flags, nullptr, nullptr, nullptr, nullptr, nullptr, use));
+    if (!(flags & ND_FLAG_FULL_TILES) && plan_rois(pl, crop, crop, rois) && rois_supported(funit, dtype, flags, pl, bl, rois)) o.rois = rois;
+    ND_TRY(run_stack(funit, act, dtype, blob, pl, s, o));
     const float *fw = blob + bl.off[kNumLayers - 1];
     ND_TRY(nd_launch_final1x1_stitch(pl.buf[T4B], funit, fw, fw + 3 * funit, 2, canvas, width, height, cs, ucs, ol,
                                      tile_begin, tile_count, s));
@@ -232,6 +221,10 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
     const float *fw = blob + bl.off[kNumLayers - 1];
     char *const band_base = (char *)fws, *const sh_base = band_base + fp.band_bytes, *const sv_base = sh_base + fp.strip_bytes;
     const int f4 = funit / 4, cols = fp.cols, S = fp.S;
+    StackOpts enc, dec;   // the shared steps of a band / strip batch; the rest of a tile's stack, on the useful regions
+    enc.flags = dec.flags = flags;
+    enc.step_end = dec.step_begin = kSharedSteps;
+    dec.rois = rois;
     int n = 0;
     for (int b = tile_begin / (fp.R * cols); b < fp.nbands && b * fp.R * cols < end; ++b) {
         const int row0 = b * fp.R, nrows = fp.rows - row0 < fp.R ? fp.rows - row0 : fp.R;
@@ -240,7 +233,7 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
         Plan bp = make_enc_plan(funit, band_hx(fp, nrows, cs), fp.wx, 1, fp.hx, fp.wx, 1, band_base, dtype);
         bp.split = pl.split;
         ND_TRY(nd_launch_gather_band(img, width, height, cs, ucs, ol, row0, bp.buf[X0], s));
-        ND_TRY(run_stack(funit, act, dtype, blob, bp, s, flags, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, kSharedSteps));
+        ND_TRY(run_stack(funit, act, dtype, blob, bp, s, enc));
         // its tiles in near-equal launches of at most `batch`
         const int nt = bt1 - bt0, nl = (nt + batch - 1) / batch;
         for (int j = 0; j < nl; ++j, ++n) {
@@ -252,8 +245,8 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
             sh.split = sv.split = pl.split;
             ND_TRY(nd_launch_gather_strips(img, width, height, cs, ucs, ol, t0, cnt, false, sh.buf[X0], s));
             ND_TRY(nd_launch_gather_strips(img, width, height, cs, ucs, ol, t0, cnt, true, sv.buf[X0], s));
-            ND_TRY(run_stack(funit, act, dtype, blob, sh, s, flags, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, kSharedSteps));
-            ND_TRY(run_stack(funit, act, dtype, blob, sv, s, flags, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, kSharedSteps));
+            ND_TRY(run_stack(funit, act, dtype, blob, sh, s, enc));
+            ND_TRY(run_stack(funit, act, dtype, blob, sv, s, enc));
             // per tile: the skip halves over the window the decoder reads, P2 whole, then P2's border lines from the strips
             const Plan tp = make_plan(funit, cs, cs, batch, cnt, (char *)ws, dtype);
             ND_TRY(nd_launch_splice(bp.buf[CAT4], f4, tp.buf[CAT4], f4, f4, t0, cnt, cols, row0, S, 0, 0, 0, 0, fp.win4[0], fp.win4[1],
@@ -266,12 +259,26 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
             ND_TRY(nd_launch_splice(sh.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 1, 1 - n2, 0, n2 - 1, n2, 0, n2, s));
             ND_TRY(nd_launch_splice(sv.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 0, 0, 0, 0, n2, 0, 1, s));
             ND_TRY(nd_launch_splice(sv.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 1, 0, 1 - n2, 0, n2, n2 - 1, n2, s));
-            ND_TRY(run_stack(funit, act, dtype, blob, tp, s, flags, nullptr, nullptr, nullptr, nullptr, nullptr, rois, kSharedSteps, kNumSteps));
+            ND_TRY(run_stack(funit, act, dtype, blob, tp, s, dec));
             ND_TRY(nd_launch_final1x1_stitch(tp.buf[T4B], funit, fw, fw + 3 * funit, 2, canvas, width, height, cs, ucs, ol, t0, cnt, s));
         }
     }
     return ND_OK;
 }
+
+namespace {
+// N HIP events, destroyed with the object on every exit path
+template <int N>
+struct Events {
+    hipEvent_t ev[N];
+    int n = 0;
+    int create() {
+        for (; n < N; ++n) ND_HIP(hipEventCreate(&ev[n]));
+        return ND_OK;
+    }
+    ~Events() { for (int i = 0; i < n; ++i) (void)hipEventDestroy(ev[i]); }
+};
+}  // namespace
 
 // Profiling entry point (bench.py roofline leg): one forward of the conv stack with a HIP event between every launch on
 // `stream` (and around the GEMM launch of a three-pass Winograd layer).  Synchronises the stream.  26 entries, forward order:
@@ -285,19 +292,17 @@ extern "C" int nd_utnet_profile_stack(int funit, int act, int dtype, int flags, 
     if (max_steps < kNumSteps || !steps) ND_FAIL(ND_EINVAL, "nd_utnet_profile_stack: need room for %d steps", kNumSteps);
     if (crop < 0 || 2 * crop >= cs) ND_FAIL(ND_EINVAL, "nd_utnet_profile_stack: crop %d", crop);
     hipStream_t s = (hipStream_t)stream;
-    // every argument is validated above: from here on the events are destroyed on every exit path
-    struct Events {
-        hipEvent_t ev[kNumSteps + 1 + 2 * kNumSteps];
-        int n = 0;
-        ~Events() { for (int i = 0; i < n; ++i) (void)hipEventDestroy(ev[i]); }
-    } evs;
-    for (; evs.n < kNumSteps + 1 + 2 * kNumSteps; ++evs.n) ND_HIP(hipEventCreate(&evs.ev[evs.n]));
+    Events<kNumSteps + 1 + 2 * kNumSteps> evs;
+    ND_TRY(evs.create());
     hipEvent_t *const ev = evs.ev, *const evx = evs.ev + kNumSteps + 1;
     const BlobLayout bl = blob_layout(funit, dtype);
     Roi rois[kNumSteps];
-    const Roi *use = nullptr;
-    if (!(flags & ND_FLAG_FULL_TILES) && plan_rois(pl, crop, crop, rois) && rois_supported(funit, dtype, flags, pl, bl, rois)) use = rois;
-    int rc = run_stack(funit, act, dtype, (const float *)packed, pl, s, flags, ev, nullptr, nullptr, nullptr, evx, use);
+    StackOpts opts;
+    opts.flags = flags;
+    opts.ev = ev;
+    opts.ev_x = evx;
+    if (!(flags & ND_FLAG_FULL_TILES) && plan_rois(pl, crop, crop, rois) && rois_supported(funit, dtype, flags, pl, bl, rois)) opts.rois = rois;
+    int rc = run_stack(funit, act, dtype, (const float *)packed, pl, s, opts);
     if (rc == ND_OK) {
         hipError_t e = hipStreamSynchronize(s);
         if (e != hipSuccess) {
@@ -314,16 +319,16 @@ extern "C" int nd_utnet_profile_stack(int funit, int act, int dtype, int flags, 
             break;
         }
         const Step &st = kSteps[i];
-        const Form form = step_form(st, funit, dtype, flags, pl, bl, false, nullptr);
+        const Form form = step_form(st, funit, dtype, flags, pl, bl);
         o.form = (int)form;
         o.kind = st.layer >= 0 ? kLayers[st.layer].kind : -1;
         const QpBuf &in = pl.buf[st.src], &out = pl.buf[st.dst];
         const double B = batch, esz = 16.0 / nd_cpp(dtype);      // bytes per stored channel value
         double hin = in.Hb - 2 * in.pad, win = in.Wb - 2 * in.pad;
-        if (use && use[i].rows > 0) {   // the layer ran on a region: count what it computed
+        if (opts.rois && opts.rois[i].rows > 0) {   // the layer ran on a region: count what it computed
             const bool t3 = kLayers[st.layer].kind == ND_CONVT3;
-            hin = use[i].rows - (t3 ? 2 : 0);   // (a transposed 3x3 layer's region is on its output grid = input + 2)
-            win = use[i].cols - (t3 ? 2 : 0);
+            hin = opts.rois[i].rows - (t3 ? 2 : 0);   // (a transposed 3x3 layer's region is on its output grid = input + 2)
+            win = opts.rois[i].cols - (t3 ? 2 : 0);
         }
         if (st.layer < 0) {
             const double c = st.dst_plane0_mul * funit;
@@ -361,9 +366,9 @@ extern "C" int nd_utnet_profile_stack(int funit, int act, int dtype, int flags, 
                 o.ms_xform_out = c;
             }
             QpBuf v = in;
-            if (use && use[i].rows > 0) {   // the passes ran on a view of rows + 2 x cols + 2 bordered input pixels
-                v.Hb = use[i].rows + 2;
-                v.Wb = use[i].cols + 2;
+            if (opts.rois && opts.rois[i].rows > 0) {   // the passes ran on a view of rows + 2 x cols + 2 bordered input pixels
+                v.Hb = opts.rois[i].rows + 2;
+                v.Wb = opts.rois[i].cols + 2;
             }
             nd_wino_xform_bytes(kWinoTile, v, (int)ci, (int)co, &o.xform_bytes_in, &o.xform_bytes_out);
         }
@@ -462,6 +467,62 @@ LayerPlan layer_plan(int kind, int B, int cin, int cout, int h, int w, char *bas
     p.bytes = off;
     return p;
 }
+
+// the kernel family of a single-layer call: the direct implicit GEMM, or the Winograd form named by a tile code (include/nind_hip.h):
+// 1 | 3 = 1-D F(2,3) | F(4,3) along x in conv_w1d, 5 = the same F(4,3) through conv_w2d, 2 | 4 | 6 = three-pass F(T x T, 3 x 3)
+enum LayerFamily { LF_NONE, LF_DIRECT, LF_W1D, LF_W2D, LF_WINO3P };
+struct LayerForm {
+    LayerFamily fam;
+    int T;   // Winograd output tile (0: direct)
+};
+constexpr LayerForm kDirect = {LF_DIRECT, 0};
+LayerForm wino_form(int tile) {
+    if (tile < 1 || tile > 6) return {LF_NONE, 0};
+    if (tile == 5) return {LF_W2D, 4};
+    return (tile & 1) ? LayerForm{LF_W1D, tile + 1} : LayerForm{LF_WINO3P, tile};
+}
+size_t wino_packed_floats(const LayerForm &fm, int cin, int cout) {
+    return fm.fam == LF_WINO3P ? nd_wino_packed_floats(fm.T, cin, cout) : nd_w1d_packed_floats(fm.T, cin, cout);
+}
+
+// the launch of a layer in form fm on the buffers of its plan, weights at wpk (a three-pass blob carries no bias of its own)
+ConvDesc layer_desc(const LayerForm &fm, int kind, int cin, int cout, int dt, const float *wpk, const LayerPlan &pl) {
+    ConvDesc d;
+    d.kind = kind;
+    d.cin = cin;
+    d.cout = cout;
+    d.wpk = wpk;
+    if (fm.fam != LF_WINO3P) d.bias = wpk + nd_bias_offset(kind, cin, cout, dt, fm.T);
+    d.in = pl.in;
+    d.out = pl.out;
+    d.part = pl.split;
+    d.part_bytes = kSplitScratchBytes;
+    return d;
+}
+int launch_form(const LayerForm &fm, const ConvDesc &d, void *scratch, size_t scratch_bytes, hipStream_t s) {
+    switch (fm.fam) {
+        case LF_W1D: return nd_launch_conv_w1d(fm.T, d, s);
+        case LF_W2D: return nd_launch_conv_w2d(d, s);
+        case LF_WINO3P: return nd_launch_conv_wino(fm.T, d, scratch, scratch_bytes, s);
+        default: return nd_launch_conv(d, s);
+    }
+}
+
+// one layer on NCHW tensors, its arguments checked: zero the layer plan's buffers (not the Winograd scratch behind them),
+// NCHW -> quad-planar, the layer in form fm, quad-planar -> NCHW
+int layer_forward(const LayerForm &fm, int kind, int act, float slope, int dt, const void *packed, const float *x, int batch,
+                  int cin, int h, int w, int cout, float *y, void *ws, size_t ws_bytes, int variant, int flags, hipStream_t s) {
+    const LayerPlan pl = layer_plan(kind, batch, cin, cout, h, w, (char *)ws, dt);
+    ND_HIP(hipMemsetAsync(ws, 0, pl.bytes, s));
+    ND_TRY(nd_launch_nchw_to_qp(x, cin, pl.in, 0, s));
+    ConvDesc d = layer_desc(fm, kind, cin, cout, dt, (const float *)packed, pl);
+    d.act = act;
+    d.slope = slope;
+    d.variant = variant;
+    d.nosplit = (flags & ND_FLAG_NO_SPLITK) != 0;
+    ND_TRY(launch_form(fm, d, (char *)ws + pl.bytes, ws_bytes - pl.bytes, s));
+    return nd_launch_qp_to_nchw(pl.out, 0, y, cout, s);
+}
 }  // namespace
 
 extern "C" size_t nd_layer_workspace_bytes(int kind, int batch, int cin, int cout, int h, int w, int dtype) {
@@ -479,53 +540,32 @@ extern "C" int nd_layer_forward(int kind, int act, float slope, int dtype, const
     if (!need) ND_FAIL(ND_EINVAL, "nd_layer_forward: bad shape");
     if (!ws || ws_bytes < need) ND_FAIL(ND_ENOMEM, "nd_layer_forward: workspace %zu B given, %zu B needed", ws_bytes, need);
     if (cout % nd_cpp(dtype)) ND_FAIL(ND_EINVAL, "nd_layer_forward: cout must be a multiple of %d", nd_cpp(dtype));
-    hipStream_t s = (hipStream_t)stream;
-    LayerPlan pl = layer_plan(kind, batch, cin, cout, h, w, (char *)ws, dtype);
-    ND_HIP(hipMemsetAsync(ws, 0, need, s));
-    ND_TRY(nd_launch_nchw_to_qp(x, cin, pl.in, 0, s));
-    ConvDesc d;
-    d.kind = kind;
-    d.act = act;
-    d.slope = slope;
-    d.cin = cin;
-    d.cout = cout;
-    d.wpk = (const float *)packed;
-    d.bias = d.wpk + nd_bias_offset(kind, cin, cout, dtype);
-    d.in = pl.in;
-    d.out = pl.out;
-    d.variant = variant;
-    d.part = pl.split;
-    d.part_bytes = kSplitScratchBytes;
-    d.nosplit = (flags & ND_FLAG_NO_SPLITK) != 0;
-    ND_TRY(nd_launch_conv(d, s));
-    ND_TRY(nd_launch_qp_to_nchw(pl.out, 0, y, cout, s));
-    return ND_OK;
+    return layer_forward(kDirect, kind, act, slope, dtype, packed, x, batch, cin, h, w, cout, y, ws, ws_bytes, variant, flags,
+                         (hipStream_t)stream);
 }
 
-// Winograd form of a 3x3 layer (tile = 2 | 4): same interface as nd_layer_forward with a blob from nd_winograd_pack
-// (tile = 1 | 3: the 1-D F(2,3) | F(4,3) form fused into the implicit-GEMM kernel, conv_w1d.hip)
-static bool wino_tile_ok(int tile) { return tile >= 1 && tile <= 6; }   // 5: the F(4,3) form of tile 3 through conv_w2d; 6: three-pass F(6x6,3x3)
+// Winograd form of a 3x3 layer (tile code: wino_form): same interface as nd_layer_forward with a blob from nd_winograd_pack
 extern "C" size_t nd_winograd_packed_bytes(int tile, int cin, int cout) {
-    if (!wino_tile_ok(tile) || cin <= 0 || cout <= 0) return 0;
-    if (tile == 5) tile = 3;
-    return ((tile & 1) ? nd_w1d_packed_floats(tile + 1, cin, cout) : nd_wino_packed_floats(tile, cin, cout)) * sizeof(float);
+    const LayerForm fm = wino_form(tile);
+    if (fm.fam == LF_NONE || cin <= 0 || cout <= 0) return 0;
+    return wino_packed_floats(fm, cin, cout) * sizeof(float);
 }
 extern "C" int nd_winograd_pack(int tile, int kind, int cin, int cout, const float *w, const float *bias, void *packed,
                                 size_t packed_bytes) {
     const size_t need = nd_winograd_packed_bytes(tile, cin, cout);
     if (!need) ND_FAIL(ND_EINVAL, "nd_winograd_pack: bad shape");
     if (!packed || packed_bytes < need) ND_FAIL(ND_ENOMEM, "nd_winograd_pack: %zu B given, %zu B needed", packed_bytes, need);
-    if (tile == 5) tile = 3;
-    if (tile & 1) return nd_w1d_pack(tile + 1, kind, cin, cout, w, bias, (float *)packed);
-    return nd_wino_pack(tile, kind, cin, cout, w, bias, (float *)packed);
+    const LayerForm fm = wino_form(tile);
+    if (fm.fam == LF_WINO3P) return nd_wino_pack(fm.T, kind, cin, cout, w, bias, (float *)packed);
+    return nd_w1d_pack(fm.T, kind, cin, cout, w, bias, (float *)packed);
 }
 extern "C" size_t nd_layer_winograd_workspace_bytes(int tile, int kind, int batch, int cin, int cout, int h, int w) {
-    if (!wino_tile_ok(tile) || (kind != ND_CONV3 && kind != ND_CONVT3)) return 0;
+    const LayerForm fm = wino_form(tile);
+    if (fm.fam == LF_NONE || (kind != ND_CONV3 && kind != ND_CONVT3)) return 0;
     const size_t base = nd_layer_workspace_bytes(kind, batch, cin, cout, h, w, ND_F32);
-    if (!base) return 0;
-    if (tile & 1) return base;
+    if (!base || fm.fam != LF_WINO3P) return base;
     const LayerPlan pl = layer_plan(kind, batch, cin, cout, h, w, nullptr, ND_F32);
-    return base + nd_wino_scratch_bytes(tile, pl.in, cin, cout);
+    return base + nd_wino_scratch_bytes(fm.T, pl.in, cin, cout);
 }
 extern "C" int nd_layer_forward_winograd(int tile, int kind, int act, float slope, const void *packed, const float *x, int batch,
                                          int cin, int h, int w, int cout, float *y, void *ws, size_t ws_bytes, int flags,
@@ -534,32 +574,8 @@ extern "C" int nd_layer_forward_winograd(int tile, int kind, int act, float slop
     const size_t need = nd_layer_winograd_workspace_bytes(tile, kind, batch, cin, cout, h, w);
     if (!need) ND_FAIL(ND_EINVAL, "nd_layer_forward_winograd: bad shape / kind / tile");
     if (!ws || ws_bytes < need) ND_FAIL(ND_ENOMEM, "nd_layer_forward_winograd: workspace %zu B given, %zu B needed", ws_bytes, need);
-    hipStream_t s = (hipStream_t)stream;
-    LayerPlan pl = layer_plan(kind, batch, cin, cout, h, w, (char *)ws, ND_F32);
-    ND_HIP(hipMemsetAsync(ws, 0, pl.bytes, s));
-    ND_TRY(nd_launch_nchw_to_qp(x, cin, pl.in, 0, s));
-    ConvDesc d;
-    d.kind = kind;
-    d.act = act;
-    d.slope = slope;
-    d.cin = cin;
-    d.cout = cout;
-    d.wpk = (const float *)packed;
-    d.in = pl.in;
-    d.out = pl.out;
-    d.part = pl.split;
-    d.part_bytes = kSplitScratchBytes;
-    d.nosplit = (flags & ND_FLAG_NO_SPLITK) != 0;
-    if (tile & 1) d.bias = d.wpk + nd_bias_offset(kind, cin, cout, ND_F32, tile == 5 ? 4 : tile + 1);
-    if (tile == 5) {
-        ND_TRY(nd_launch_conv_w2d(d, s));
-    } else if (tile & 1) {
-        ND_TRY(nd_launch_conv_w1d(tile + 1, d, s));
-    } else {
-        ND_TRY(nd_launch_conv_wino(tile, d, (char *)ws + pl.bytes, ws_bytes - pl.bytes, s));
-    }
-    ND_TRY(nd_launch_qp_to_nchw(pl.out, 0, y, cout, s));
-    return ND_OK;
+    return layer_forward(wino_form(tile), kind, act, slope, ND_F32, packed, x, batch, cin, h, w, cout, y, ws, ws_bytes, -1, flags,
+                         (hipStream_t)stream);
 }
 
 extern "C" int nd_maxpool2_forward(const float *x, int batch, int c, int h, int w, float *y, void *ws, size_t ws_bytes,
@@ -611,108 +627,79 @@ __global__ void k_fill_random16(unsigned short *p, size_t n, unsigned seed, int 
     }
 }
 
+namespace {
+// the operands of a micro-benchmark: `bytes` of layer buffers from ws and wfloats of packed weights, pseudo-random (16-bit
+// storage: finite bf16 / fp16 patterns in (-0.5, 0.5) through the fp32 generator + convert, and an fp32 bias)
+void fill_random(void *ws, size_t bytes, float *wpk, size_t wfloats, int dt, int kind, int cin, int cout, hipStream_t s) {
+    if (dt == ND_F32) {
+        hipLaunchKernelGGL(k_fill_random, dim3(2048), dim3(256), 0, s, (float *)ws, bytes / 4, 12345u);
+        hipLaunchKernelGGL(k_fill_random, dim3(1024), dim3(256), 0, s, wpk, wfloats, 777u);
+        return;
+    }
+    hipLaunchKernelGGL(k_fill_random16, dim3(2048), dim3(256), 0, s, (unsigned short *)ws, bytes / 2, 12345u, dt);
+    hipLaunchKernelGGL(k_fill_random16, dim3(1024), dim3(256), 0, s, (unsigned short *)wpk, wfloats * 2, 777u, dt);
+    hipLaunchKernelGGL(k_fill_random, dim3(64), dim3(256), 0, s, wpk + nd_bias_offset(kind, cin, cout, dt), (size_t)nd_mtiles(kind, cout) * 32, 99u);
+}
+
+// one warm-up launch of d in form fm (it also validates the variant), then the mean duration of `iters` launches between two
+// events on s.  Synchronises.
+int time_form(const char *what, const LayerForm &fm, const ConvDesc &d, void *scratch, size_t scratch_bytes, int iters,
+              hipStream_t s, float *mean_ms) {
+    ND_TRY(launch_form(fm, d, scratch, scratch_bytes, s));
+    Events<2> ev;
+    ND_TRY(ev.create());
+    ND_HIP(hipEventRecord(ev.ev[0], s));
+    int rc = ND_OK;
+    for (int i = 0; i < iters && rc == ND_OK; ++i) rc = launch_form(fm, d, scratch, scratch_bytes, s);
+    (void)hipEventRecord(ev.ev[1], s);
+    if (hipStreamSynchronize(s) != hipSuccess && rc == ND_OK) {
+        nd_set_error("%s: stream failed", what);
+        rc = ND_EHIP;
+    }
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, ev.ev[0], ev.ev[1]);
+    if (mean_ms) *mean_ms = ms / (iters > 0 ? iters : 1);
+    return rc;
+}
+}  // namespace
+
 extern "C" int nd_conv_bench(int kind, int dtype, int batch, int cin, int cout, int h, int w, int variant, int iters, void *ws,
                              size_t ws_bytes, void *stream, float *mean_ms) {
     const size_t need = nd_layer_workspace_bytes(kind, batch, cin, cout, h, w, dtype);
-    const size_t wfloats = need ? nd_packed_floats(kind, cin, cout, dtype) : 0;
     if (!need) ND_FAIL(ND_EINVAL, "nd_conv_bench: bad shape");
+    const size_t wfloats = nd_packed_floats(kind, cin, cout, dtype);
     const size_t total = need + ((wfloats * 4 + 255) & ~(size_t)255);
     if (!ws || ws_bytes < total) ND_FAIL(ND_ENOMEM, "nd_conv_bench: workspace %zu B given, %zu B needed", ws_bytes, total);
     hipStream_t s = (hipStream_t)stream;
     LayerPlan pl = layer_plan(kind, batch, cin, cout, h, w, (char *)ws, dtype);
     float *wpk = (float *)((char *)ws + need);
-    if (dtype == ND_F32) {
-        hipLaunchKernelGGL(k_fill_random, dim3(2048), dim3(256), 0, s, (float *)ws, need / 4, 12345u);
-        hipLaunchKernelGGL(k_fill_random, dim3(1024), dim3(256), 0, s, wpk, wfloats, 777u);
-    } else {
-        // pseudo-random finite 16-bit patterns: fill as bf16/fp16 values in (-0.5, 0.5) through the fp32 generator + convert
-        hipLaunchKernelGGL(k_fill_random16, dim3(2048), dim3(256), 0, s, (unsigned short *)ws, need / 2, 12345u, dtype);
-        hipLaunchKernelGGL(k_fill_random16, dim3(1024), dim3(256), 0, s, (unsigned short *)wpk, wfloats * 2, 777u, dtype);
-        hipLaunchKernelGGL(k_fill_random, dim3(64), dim3(256), 0, s, wpk + nd_bias_offset(kind, cin, cout, dtype), (size_t)nd_mtiles(kind, cout) * 32, 99u);
-    }
-    ConvDesc d;
-    d.kind = kind;
+    fill_random(ws, need, wpk, wfloats, dtype, kind, cin, cout, s);
+    ConvDesc d = layer_desc(kDirect, kind, cin, cout, dtype, wpk, pl);
     d.act = ND_ACT_PRELU;
     d.slope = 0.2f;
-    d.cin = cin;
-    d.cout = cout;
-    d.wpk = wpk;
-    d.bias = wpk + nd_bias_offset(kind, cin, cout, dtype);
-    d.in = pl.in;
-    d.out = pl.out;
     d.variant = variant;
-    d.part = pl.split;
-    d.part_bytes = kSplitScratchBytes;
-    ND_TRY(nd_launch_conv(d, s));  // warm-up (also validates the variant)
-    hipEvent_t e0, e1;
-    ND_HIP(hipEventCreate(&e0));
-    ND_HIP(hipEventCreate(&e1));
-    ND_HIP(hipEventRecord(e0, s));
-    int rc = ND_OK;
-    for (int i = 0; i < iters && rc == ND_OK; ++i) rc = nd_launch_conv(d, s);
-    (void)hipEventRecord(e1, s);
-    if (hipStreamSynchronize(s) != hipSuccess && rc == ND_OK) {
-        nd_set_error("nd_conv_bench: stream failed");
-        rc = ND_EHIP;
-    }
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (mean_ms) *mean_ms = ms / (iters > 0 ? iters : 1);
-    return rc;
+    return time_form("nd_conv_bench", kDirect, d, nullptr, 0, iters, s, mean_ms);
 }
 
 extern "C" int nd_num_conv_variants(void) { return nd_conv_variant_count(); }
 extern "C" const char *nd_conv_variant_name(int v) { return nd_conv_variant_label(v); }
 
-// Same measurement for the Winograd form (tile = 2 | 4) of a 3x3 layer: the three passes per iteration.
+// Same measurement for the Winograd form (tile code: wino_form) of a 3x3 layer: all its passes per iteration.
 // workspace: nd_layer_winograd_workspace_bytes + nd_winograd_packed_bytes + 256 B
 extern "C" int nd_winograd_bench(int tile, int kind, int batch, int cin, int cout, int h, int w, int iters, void *ws,
                                  size_t ws_bytes, void *stream, float *mean_ms) {
     const size_t need = nd_layer_winograd_workspace_bytes(tile, kind, batch, cin, cout, h, w);
     if (!need) ND_FAIL(ND_EINVAL, "nd_winograd_bench: bad shape / kind / tile");
-    const size_t wfloats = (tile & 1) ? nd_w1d_packed_floats(tile == 5 ? 4 : tile + 1, cin, cout) : nd_wino_packed_floats(tile, cin, cout);
+    const LayerForm fm = wino_form(tile);
+    const size_t wfloats = wino_packed_floats(fm, cin, cout);
     const size_t total = ((need + 255) & ~(size_t)255) + wfloats * 4;
     if (!ws || ws_bytes < total) ND_FAIL(ND_ENOMEM, "nd_winograd_bench: workspace %zu B given, %zu B needed", ws_bytes, total);
     hipStream_t s = (hipStream_t)stream;
     LayerPlan pl = layer_plan(kind, batch, cin, cout, h, w, (char *)ws, ND_F32);
     float *wpk = (float *)((char *)ws + ((need + 255) & ~(size_t)255));
-    hipLaunchKernelGGL(k_fill_random, dim3(2048), dim3(256), 0, s, (float *)ws, pl.bytes / 4, 12345u);
-    hipLaunchKernelGGL(k_fill_random, dim3(1024), dim3(256), 0, s, wpk, wfloats, 777u);
-    ConvDesc d;
-    d.kind = kind;
+    fill_random(ws, pl.bytes, wpk, wfloats, ND_F32, kind, cin, cout, s);
+    ConvDesc d = layer_desc(fm, kind, cin, cout, ND_F32, wpk, pl);
     d.act = ND_ACT_PRELU;
     d.slope = 0.2f;
-    d.cin = cin;
-    d.cout = cout;
-    d.wpk = wpk;
-    d.in = pl.in;
-    d.out = pl.out;
-    d.part = pl.split;
-    d.part_bytes = kSplitScratchBytes;
-    void *scratch = (char *)ws + pl.bytes;
-    const size_t scratch_bytes = need - pl.bytes;
-    if (tile & 1) d.bias = d.wpk + nd_bias_offset(kind, cin, cout, ND_F32, tile == 5 ? 4 : tile + 1);
-    auto run = [&]() {
-        return tile == 5 ? nd_launch_conv_w2d(d, s) : ((tile & 1) ? nd_launch_conv_w1d(tile + 1, d, s) : nd_launch_conv_wino(tile, d, scratch, scratch_bytes, s));
-    };
-    ND_TRY(run());
-    hipEvent_t e0, e1;
-    ND_HIP(hipEventCreate(&e0));
-    ND_HIP(hipEventCreate(&e1));
-    ND_HIP(hipEventRecord(e0, s));
-    int rc = ND_OK;
-    for (int i = 0; i < iters && rc == ND_OK; ++i) rc = run();
-    (void)hipEventRecord(e1, s);
-    if (hipStreamSynchronize(s) != hipSuccess && rc == ND_OK) {
-        nd_set_error("nd_winograd_bench: stream failed");
-        rc = ND_EHIP;
-    }
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (mean_ms) *mean_ms = ms / (iters > 0 ? iters : 1);
-    return rc;
+    return time_form("nd_winograd_bench", fm, d, (char *)ws + pl.bytes, need - pl.bytes, iters, s, mean_ms);
 }

@@ -95,14 +95,14 @@ struct BlobLayout {
     size_t total;
 };
 // train: the layout of the training step's forward blob -- every 3x3 region can hold either the direct or the fused 1-D
-// Winograd packing (the step picks per layer), no separate Winograd regions
+// Winograd packing (the step picks per layer), no separate Winograd regions; else the inference blob with its Winograd regions
 inline size_t layer_floats(const LayerSpec &l, int f, int dt, bool train) {
     const size_t direct = nd_packed_floats(l.kind, lcin(l, f), lcout(l, f), dt);
     if (!train || dt != ND_F32 || (l.kind != ND_CONV3 && l.kind != ND_CONVT3)) return direct;
     const size_t w1 = nd_w1d_packed_floats(kW1dTile, lcin(l, f), lcout(l, f));
     return w1 > direct ? w1 : direct;
 }
-BlobLayout blob_layout(int f, int dt, bool with_wino = true, bool train = false) {
+BlobLayout blob_layout(int f, int dt, bool train = false) {
     BlobLayout b;
     size_t o = kHeaderFloats;
     for (int i = 0; i < kNumLayers; ++i) {
@@ -115,13 +115,13 @@ BlobLayout blob_layout(int f, int dt, bool with_wino = true, bool train = false)
     }
     for (int i = 0; i < kNumLayers; ++i) {
         b.woff[i] = 0;
-        if (with_wino && wino_layer(kLayers[i], f, dt)) {
+        if (!train && wino_layer(kLayers[i], f, dt)) {
             b.woff[i] = o;
             o += (nd_wino_packed_floats(kWinoTile, lcin(kLayers[i], f), lcout(kLayers[i], f)) + 63) / 64 * 64;
         }
         b.w1off[i] = b.w1off2[i] = 0;
         const LayerSpec &l = kLayers[i];
-        if (with_wino && dt == ND_F32 && (l.kind == ND_CONV3 || l.kind == ND_CONVT3) && !b.woff[i]) {
+        if (!train && dt == ND_F32 && (l.kind == ND_CONV3 || l.kind == ND_CONVT3) && !b.woff[i]) {
             b.w1off[i] = o;
             o += (nd_w1d_packed_floats(kW1dTile, lcin(l, f), lcout(l, f)) + 63) / 64 * 64;
             b.w1off2[i] = o;
@@ -244,14 +244,15 @@ Plan make_plan(int f, int ch_, int cw_, int cap, int nimg, char *base, int dt) {
     return p;
 }
 
-// which kernel family runs step `st` of the stack (pl = the plan of the call: the fused 1-D form needs the row's LDS images to fit)
+// which kernel family runs step `st` of the stack (pl = the plan of the call: the fused 1-D form needs the row's LDS images to fit;
+// train_w1: null for inference, else the training forward's per-layer choice, 1 = fused 1-D Winograd)
 enum Form { FORM_POOL = -1, FORM_DIRECT = 0, FORM_W1D4 = 1, FORM_W1D2 = 2, FORM_WINO3P = 3 };
-inline Form step_form(const Step &st, int f, int dt, int flags, const Plan &pl, const BlobLayout &bl, bool train,
-                      const unsigned char *train_w1) {
+inline Form step_form(const Step &st, int f, int dt, int flags, const Plan &pl, const BlobLayout &bl,
+                      const unsigned char *train_w1 = nullptr) {
     if (st.layer < 0) return FORM_POOL;
     const LayerSpec &l = kLayers[st.layer];
     if (l.kind != ND_CONV3 && l.kind != ND_CONVT3) return FORM_DIRECT;
-    if (train) return (train_w1 && train_w1[st.layer]) ? FORM_W1D4 : FORM_DIRECT;
+    if (train_w1) return train_w1[st.layer] ? FORM_W1D4 : FORM_DIRECT;
     if (flags & ND_FLAG_DIRECT_CONV) return FORM_DIRECT;
     if (bl.w1off[st.layer]) {
         if (nd_f43_w2d(pl.buf[st.src], lcout(l, f), false, flags)) return FORM_W1D4;   // conv_w2d: any row width
@@ -336,7 +337,7 @@ inline bool plan_rois(const Plan &pl, int crop_h, int crop_w, Roi *roi) {
 inline bool rois_supported(int f, int dt, int flags, const Plan &pl, const BlobLayout &bl, const Roi *rois) {
     for (int i = 0; i < kNumSteps; ++i) {
         if (rois[i].rows <= 0) continue;
-        const Form form = step_form(kSteps[i], f, dt, flags, pl, bl, false, nullptr);
+        const Form form = step_form(kSteps[i], f, dt, flags, pl, bl);
         if (form == FORM_DIRECT) {
             // conv_qp walks linear pixel ranges: a region much narrower than its buffer may not fit any stage image -- then no
             // layer is restricted (a whole-tile layer needs whole-tile producers)
@@ -361,22 +362,29 @@ inline bool rois_supported(int f, int dt, int flags, const Plan &pl, const BlobL
     return true;
 }
 
-// ev (optional): kNumSteps+1 events, ev[i] recorded before step i, ev[kNumSteps] after the last one;
-// ev_x (optional, with ev): 2 events per step, recorded after the input transform and after the GEMMs of a three-pass layer
-// pre (optional, training): kNumSlopes compact buffers that receive acc + bias of every activated layer
-// train_w1 (training forward, with pre): per layer, 1 = the layer's blob region holds the fused 1-D Winograd packing
-// flags: nd_flags of the call (ND_FLAG_NO_SPLITK: every tile whole; ND_FLAG_DIRECT_CONV: no Winograd form on any layer)
-int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStream_t s, int flags = 0, hipEvent_t *ev = nullptr,
-              const QpBuf *pre = nullptr, const float *slopes = nullptr, const unsigned char *train_w1 = nullptr,
-              hipEvent_t *ev_x = nullptr, const Roi *rois = nullptr, int step_begin = 0, int step_end = kNumSteps) {
-    const BlobLayout bl = blob_layout(f, dt, pre == nullptr, pre != nullptr);
+// what one run_stack call does besides the whole inference stack: a call site sets only the members that differ
+struct StackOpts {
+    int flags = 0;                     // nd_flags of the call (ND_FLAG_NO_SPLITK: every tile whole; ND_FLAG_DIRECT_CONV: no Winograd form)
+    const Roi *rois = nullptr;         // per step: the region the layer computes (plan_rois; rows 0: the whole layer)
+    int step_begin = 0, step_end = kNumSteps;   // the steps [step_begin, step_end) of kSteps
+    hipEvent_t *ev = nullptr;          // profiling: kNumSteps+1 events, ev[i] recorded before step i, ev[kNumSteps] after the last one
+    hipEvent_t *ev_x = nullptr;        // profiling, with ev: 2 events per step, recorded after the input transform and after the
+                                       // GEMMs of a three-pass layer
+    // training forward (both set): the blob of blob_layout(f, dt, true)
+    const QpBuf *pre = nullptr;                // kNumSlopes compact buffers that receive acc + bias of every activated layer
+    const unsigned char *train_w1 = nullptr;   // per layer, 1 = the layer's blob region holds the fused 1-D Winograd packing
+};
+int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStream_t s, const StackOpts &o) {
+    const QpBuf *const pre = o.pre;
+    const int flags = o.flags, step_begin = o.step_begin, step_end = o.step_end;
+    const BlobLayout bl = blob_layout(f, dt, pre != nullptr);
     const int cpp = nd_cpp(dt);
     int si = step_begin;
     bool pool_done = false;   // the previous layer wrote the pooled tensor itself
     QpBuf pool_view;
     for (int k = step_begin; k < step_end; ++k) {
         const Step &st = kSteps[k];
-        if (ev) ND_HIP(hipEventRecord(ev[si], s));
+        if (o.ev) ND_HIP(hipEventRecord(o.ev[si], s));
         const int this_step = si++;
         if (st.layer < 0) {
             if (pool_done) {
@@ -392,7 +400,7 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
         d.kind = l.kind;
         d.act = l.prelu >= 0 ? act : ND_ACT_NONE;
         d.slope = 0.25f;
-        d.slope_dev = (l.prelu >= 0 && act == ND_ACT_PRELU) ? (slopes ? slopes + l.prelu : blob + l.prelu) : nullptr;
+        d.slope_dev = (l.prelu >= 0 && act == ND_ACT_PRELU) ? blob + l.prelu : nullptr;
         if (pre && l.prelu >= 0) {
             d.pre = pre[l.prelu].base;
             d.pre_plane = pre[l.prelu].np();
@@ -407,12 +415,12 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
         d.part = pl.split;
         d.part_bytes = kSplitScratchBytes;
         d.nosplit = (flags & ND_FLAG_NO_SPLITK) != 0;
-        const Form form = step_form(st, f, dt, flags, pl, bl, pre != nullptr, train_w1);
-        if (rois && rois[this_step].rows > 0) {
-            d.roi_r0 = rois[this_step].r0;
-            d.roi_c0 = rois[this_step].c0;
-            d.roi_rows = rois[this_step].rows;
-            d.roi_cols = rois[this_step].cols;
+        const Form form = step_form(st, f, dt, flags, pl, bl, o.train_w1);
+        if (o.rois && o.rois[this_step].rows > 0) {
+            d.roi_r0 = o.rois[this_step].r0;
+            d.roi_c0 = o.rois[this_step].c0;
+            d.roi_rows = o.rois[this_step].rows;
+            d.roi_cols = o.rois[this_step].cols;
         }
         // MaxPool2d(2) fused into the producing layer's epilogue where its kernel can (conv_w2d, three-pass output transform):
         // the pool kernel re-read the whole skip tensor from HBM (2.4 % of the fp32 conv stack)
@@ -452,13 +460,13 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
                     c.pool = &pv;
                 }
                 // (profiling: the split of a layer's time into its passes is recorded for a single-chunk layer only)
-                ND_TRY(nd_launch_conv_wino(kWinoTile, c, pl.wino, pl.wino_bytes, s, (ev_x && nimg <= kWinoChunk) ? ev_x + 2 * this_step : nullptr));
+                ND_TRY(nd_launch_conv_wino(kWinoTile, c, pl.wino, pl.wino_bytes, s, (o.ev_x && nimg <= kWinoChunk) ? o.ev_x + 2 * this_step : nullptr));
             }
             continue;
         }
         ND_TRY(nd_launch_conv(d, s));
     }
-    if (ev) ND_HIP(hipEventRecord(ev[si], s));
+    if (o.ev) ND_HIP(hipEventRecord(o.ev[si], s));
     return ND_OK;
 }
 
@@ -592,7 +600,7 @@ int frame_plan(int f, int dt, int flags, int W, int H, int cs, int ucs, int ol, 
         for (int i = 0; i < kSharedSteps; ++i) {
             const Step &st = kSteps[i];
             if (st.layer < 0) continue;
-            if (step_form(st, f, dt, flags, pp, bl, false, nullptr) != FORM_W1D4 || !nd_f43_w2d(pp.buf[st.src], lcout(kLayers[st.layer], f), false, flags))
+            if (step_form(st, f, dt, flags, pp, bl) != FORM_W1D4 || !nd_f43_w2d(pp.buf[st.src], lcout(kLayers[st.layer], f), false, flags))
                 return ND_OK;
         }
     fp->strip_bytes = make_enc_plan(f, kStrip, cs + 4, 2 * batch, kStrip, cs + 4, 2 * batch, nullptr, dt).bytes;

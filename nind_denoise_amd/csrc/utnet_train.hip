@@ -540,14 +540,11 @@ extern "C" int nd_utnet_param_range(int funit, int tensor_idx, size_t *offset, s
 }
 extern "C" size_t nd_utnet_train_blob_bytes(int funit) {
     if (funit < 8 || funit % 8) return 0;
-    return (blob_layout(funit, ND_F32, false, true).total + bwd_blob_layout(funit).total) * sizeof(float);
+    return (blob_layout(funit, ND_F32, true).total + bwd_blob_layout(funit).total) * sizeof(float);
 }
 extern "C" size_t nd_utnet_train_workspace_bytes_hw(int funit, int h, int w, int batch) {
     if (check_train(funit, h, w, batch) != ND_OK) return 0;
     return make_train_plan(funit, h, w, batch, nullptr).bytes;
-}
-extern "C" size_t nd_utnet_train_workspace_bytes(int funit, int cs, int batch) {
-    return nd_utnet_train_workspace_bytes_hw(funit, cs, cs, batch);
 }
 extern "C" int nd_utnet_train_workspace_init_hw(void *ws, size_t ws_bytes, int funit, int h, int w, int batch, void *stream) {
     ND_TRY(check_train(funit, h, w, batch));
@@ -556,12 +553,9 @@ extern "C" int nd_utnet_train_workspace_init_hw(void *ws, size_t ws_bytes, int f
     ND_HIP(hipMemsetAsync(ws, 0, need, (hipStream_t)stream));   // zero borders of activations AND gradients, slack
     return ND_OK;
 }
-extern "C" int nd_utnet_train_workspace_init(void *ws, size_t ws_bytes, int funit, int cs, int batch, void *stream) {
-    return nd_utnet_train_workspace_init_hw(ws, ws_bytes, funit, cs, cs, batch, stream);
-}
 
 // ---- the step in two halves: (1) weight packing + forward with the pre-activations kept, (2) backward from d loss / d output.
-// nd_utnet_train_step runs both with the loss between them; nd_utnet_train_forward / nd_utnet_train_backward expose the halves
+// nd_utnet_train_step_hw runs both with the loss between them; nd_utnet_train_forward_hw / nd_utnet_train_backward_hw expose the halves
 // to torch.autograd (networks/UtNet.py: model(x).clip(0, 1), loss.backward() of nn_common.py:198-218 then work unchanged).
 struct TrainCtx {
     int f, B, H, W, flags, act;
@@ -591,7 +585,7 @@ static int train_ctx(TrainCtx &c, int funit, int flags, int act, const float *pa
     if (ws_bytes < c.t.bytes) ND_FAIL(ND_ENOMEM, "UtNet training workspace: %zu B given, %zu B needed", ws_bytes, c.t.bytes);
     c.s = (hipStream_t)stream;
     c.pl = param_layout(funit);
-    c.bl = blob_layout(funit, ND_F32, false, true);
+    c.bl = blob_layout(funit, ND_F32, true);
     // 3x3 layers whose rows fit its LDS images run the fused 1-D Winograd kernel, forward and data gradient (else the direct one)
     memset(c.fwd_w1, 0, sizeof(c.fwd_w1));
     memset(c.bwd_w1, 0, sizeof(c.bwd_w1));
@@ -649,7 +643,11 @@ static int train_forward(TrainCtx &c, const float *params, const float *x, float
         for (int k = 0; k < kNumSlopes; ++k)
             ND_HIP(hipMemcpyAsync(fblob + k, c.slopes[k], sizeof(float), hipMemcpyDeviceToDevice, s));
     ND_TRY(nd_launch_reflect_pack(x, B, H, W, c.t.fwd.buf[X0], s));
-    ND_TRY(run_stack(f, c.act, ND_F32, fblob, c.t.fwd, s, c.flags, nullptr, c.t.pre, nullptr, c.fwd_w1));
+    StackOpts o;
+    o.flags = c.flags;
+    o.pre = c.t.pre;
+    o.train_w1 = c.fwd_w1;
+    ND_TRY(run_stack(f, c.act, ND_F32, fblob, c.t.fwd, s, o));
     const float *fw = fblob + bl.off[kNumLayers - 1];
     ND_TRY(nd_launch_final1x1(c.t.fwd.buf[T4B], f, fw, fw + 3 * f, 2, y_out, H, W, s));
     return ND_OK;
@@ -787,11 +785,14 @@ static int train_backward(TrainCtx &c, const float *params, float *grads, const 
 //   loss = w_l1 * mean|g - target| + w_mse * mean (g - target)^2 + w_ssim * mean_n(1 - SSIM_n(g, target))
 //          + w_msssim * mean_n(1 - MS-SSIM_n(g, target)),      g = clip(y, 0, 1)          (nn_common.py:198-199, 226-241)
 // and the backward pass.  params / grads: flat fp32 buffers in state-dict order (nd_utnet_param_range);
-// x, target, y_out: [batch,3,h,w] NCHW fp32; loss_out: one float in HBM; blobs: nd_utnet_train_blob_bytes scratch.
-static int train_step_impl(int funit, int flags, const float *params, float *grads, void *blobs, const float *x,
-                           const float *target, float *y_out, float w_l1, float w_mse, float w_ssim, float w_msssim,
-                           float *loss_out, int batch, int h, int w, int loss_cs, void *ws, size_t ws_bytes, void *stream,
-                           void *const *bucket_ev) {
+// x, target, y_out: [batch,3,h,w] NCHW fp32 (each side 16k+56); loss_out: one float in HBM; blobs: nd_utnet_train_blob_bytes
+// scratch.  bucket_events (nullable, else nd_utnet_grad_buckets of them): bucket_events[k] (hipEvent_t) is recorded on `stream` as soon as
+// every gradient of bucket k is final -- a data-parallel run overlaps the gradient reduction with the backward pass.
+extern "C" int nd_utnet_train_step_hw(int funit, int flags, const float *params, float *grads, void *blobs, const float *x,
+                                      const float *target, float *y_out, float w_l1, float w_mse, float w_ssim, float w_msssim,
+                                      float *loss_out, int batch, int h, int w, int loss_cs, void *ws, size_t ws_bytes, void *stream,
+                                      void *const *bucket_events, int n_events) {
+    if (bucket_events && n_events != kNumBuckets) ND_FAIL(ND_EINVAL, "train step: %d bucket events expected", kNumBuckets);
     // the criteria see the centre loss_cs x loss_cs crop (nn_train.py:319-323, pt_ops.pt_crop_batch), or the whole output
     const int Lh = loss_cs > 0 ? loss_cs : h, Lw = loss_cs > 0 ? loss_cs : w, L = Lh < Lw ? Lh : Lw;
     if (Lh > h || Lw > w) ND_FAIL(ND_EINVAL, "UtNet training: loss_cs=%d exceeds the crop size %dx%d", loss_cs, h, w);
@@ -839,32 +840,7 @@ static int train_step_impl(int funit, int flags, const float *params, float *gra
         ND_HIP(hipGetLastError());
     }
 
-    return train_backward(c, params, grads, t.gy, nullptr, bucket_ev);
-}
-extern "C" int nd_utnet_train_step(int funit, int flags, const float *params, float *grads, void *blobs, const float *x,
-                                   const float *target, float *y_out, float w_l1, float w_mse, float w_ssim, float w_msssim,
-                                   float *loss_out, int batch, int cs, int loss_cs, void *ws, size_t ws_bytes, void *stream) {
-    return train_step_impl(funit, flags, params, grads, blobs, x, target, y_out, w_l1, w_mse, w_ssim, w_msssim, loss_out, batch, cs,
-                           cs, loss_cs, ws, ws_bytes, stream, nullptr);
-}
-// The same step for a data-parallel run that overlaps the gradient reduction with the backward pass: bucket_events[k]
-// (hipEvent_t, nd_utnet_grad_buckets of them) is recorded on `stream` as soon as every gradient of bucket k is final.
-extern "C" int nd_utnet_train_step_ev(int funit, int flags, const float *params, float *grads, void *blobs, const float *x,
-                                      const float *target, float *y_out, float w_l1, float w_mse, float w_ssim, float w_msssim,
-                                      float *loss_out, int batch, int cs, int loss_cs, void *ws, size_t ws_bytes, void *stream,
-                                      void *const *bucket_events, int n_events) {
-    if (!bucket_events || n_events != kNumBuckets) ND_FAIL(ND_EINVAL, "train step: %d bucket events expected", kNumBuckets);
-    return train_step_impl(funit, flags, params, grads, blobs, x, target, y_out, w_l1, w_mse, w_ssim, w_msssim, loss_out, batch, cs,
-                           cs, loss_cs, ws, ws_bytes, stream, bucket_events);
-}
-// The step on h x w crops (each side 16k+56); bucket_events nullable (else nd_utnet_grad_buckets of them)
-extern "C" int nd_utnet_train_step_hw(int funit, int flags, const float *params, float *grads, void *blobs, const float *x,
-                                      const float *target, float *y_out, float w_l1, float w_mse, float w_ssim, float w_msssim,
-                                      float *loss_out, int batch, int h, int w, int loss_cs, void *ws, size_t ws_bytes, void *stream,
-                                      void *const *bucket_events, int n_events) {
-    if (bucket_events && n_events != kNumBuckets) ND_FAIL(ND_EINVAL, "train step: %d bucket events expected", kNumBuckets);
-    return train_step_impl(funit, flags, params, grads, blobs, x, target, y_out, w_l1, w_mse, w_ssim, w_msssim, loss_out, batch, h,
-                           w, loss_cs, ws, ws_bytes, stream, bucket_events);
+    return train_backward(c, params, grads, t.gy, nullptr, bucket_events);
 }
 // Buckets of the flat gradient buffer in the order the backward pass completes them (one per decoder / encoder level):
 // offsets / counts in floats.  Returns the number of buckets (9); fills at most `max` entries.
@@ -906,17 +882,6 @@ extern "C" int nd_utnet_train_backward_hw(int funit, int act, int flags, const f
     TrainCtx c;
     ND_TRY(train_ctx(c, funit, flags, act, params, blobs, batch, h, w, ws, ws_bytes, stream));
     return train_backward(c, params, grads, gy, dx, bucket_events);
-}
-extern "C" int nd_utnet_train_forward(int funit, int act, int flags, const float *params, void *blobs, const float *x, float *y_out,
-                                      int batch, int cs, void *ws, size_t ws_bytes, void *stream) {
-    return nd_utnet_train_forward_hw(funit, act, flags, params, blobs, x, y_out, batch, cs, cs, ws, ws_bytes, stream);
-}
-extern "C" int nd_utnet_train_backward(int funit, int act, int flags, const float *params, float *grads, void *blobs, const float *gy,
-                                       int batch, int cs, void *ws, size_t ws_bytes, void *stream, void *const *bucket_events,
-                                       int n_events) {
-    if (!grads || !gy) ND_FAIL(ND_EINVAL, "train backward: null pointer");
-    return nd_utnet_train_backward_hw(funit, act, flags, params, grads, blobs, gy, nullptr, batch, cs, cs, ws, ws_bytes, stream,
-                                      bucket_events, n_events);
 }
 
 // torch.optim.Adam(params, lr, betas=(b1,b2), eps, amsgrad) on flat buffers; step = 1, 2, ...

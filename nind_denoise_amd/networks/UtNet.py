@@ -3,9 +3,9 @@
 
 The torch layers created here are parameter CONTAINERS only (they give the module the reference's
 state-dict layout, initialisation and ``load_state_dict`` behaviour); ``forward`` never calls them.
-It repacks the weights once into MFMA fragment order, keeps the packed blob and a per-(cs, batch)
+It repacks the weights once into MFMA fragment order, keeps the packed blob and a per-(h, w, batch)
 activation workspace resident in HBM, and enqueues the whole conv stack on the current stream
-through ``nd_utnet_forward``.  There is no CPU path: a CPU tensor raises.
+through ``nd_utnet_forward_hw``.  There is no CPU path: a CPU tensor raises.
 """
 import ctypes
 
@@ -241,7 +241,7 @@ class UtNet(nn.Module):
                 self._workspaces.pop(next(iter(self._workspaces)))
             ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
             _lib.check(lib.nd_utnet_workspace_init_hw(ws.data_ptr(), nbytes, self.funit, h, w, batch, self._dt,
-                                                      _lib.stream_ptr(device)), "nd_utnet_workspace_init")
+                                                      _lib.stream_ptr(device)), "nd_utnet_workspace_init_hw")
             self._workspaces[key] = ws
         return ws
 
@@ -293,7 +293,7 @@ class UtNet(nn.Module):
             y = torch.empty_like(x)
             _lib.check(lib.nd_utnet_forward_hw(self.funit, _lib.ACT[self.activation], self._dt, self.flags, blob.data_ptr(),
                                                x.data_ptr(), y.data_ptr(), batch, h, w, ws.data_ptr(), ws.numel(),
-                                               _lib.stream_ptr(x.device)), "nd_utnet_forward")
+                                               _lib.stream_ptr(x.device)), "nd_utnet_forward_hw")
         return y
 
     def _train_state(self, device):

@@ -1009,7 +1009,7 @@ def test_reference_style_main_loop_with_dataloader(dev, whole_k):
     assert (fused_roi - fused).abs().max().item() <= 2e-6 * max(1.0, fused.abs().max().item())
 
 
-def test_api_error_paths(dev):
+def test_api_error_paths_hw_forward(dev):
     lib = _lib.load()
     from nind_denoise_amd import pipeline
     img = torch.zeros(3, 300, 300, device=dev)
@@ -1021,19 +1021,19 @@ def test_api_error_paths(dev):
     ws = torch.empty(1 << 20, dtype=torch.uint8, device=dev)
     blob = torch.zeros(1 << 10, device=dev)
     x = torch.zeros(1, 3, 104, 104, device=dev)
-    rc = lib.nd_utnet_forward(16, 1, 0, 0, blob.data_ptr(), x.data_ptr(), x.data_ptr(), 1, 104, ws.data_ptr(), ws.numel(),
-                              _lib.stream_ptr(dev))
+    rc = lib.nd_utnet_forward_hw(16, 1, 0, 0, blob.data_ptr(), x.data_ptr(), x.data_ptr(), 1, 104, 104, ws.data_ptr(),
+                                 ws.numel(), _lib.stream_ptr(dev))
     assert rc == -2 and b"workspace" in lib.nd_last_error()      # ND_ENOMEM: workspace too small, nothing launched
-    rc = lib.nd_utnet_forward(12, 1, 0, 0, blob.data_ptr(), x.data_ptr(), x.data_ptr(), 1, 104, ws.data_ptr(), ws.numel(),
-                              _lib.stream_ptr(dev))
+    rc = lib.nd_utnet_forward_hw(12, 1, 0, 0, blob.data_ptr(), x.data_ptr(), x.data_ptr(), 1, 104, 104, ws.data_ptr(),
+                                 ws.numel(), _lib.stream_ptr(dev))
     assert rc == -1                                              # funit not a multiple of 8
-    rc = lib.nd_utnet_forward(16, 7, 0, 0, blob.data_ptr(), x.data_ptr(), x.data_ptr(), 1, 104, ws.data_ptr(), ws.numel(),
-                              _lib.stream_ptr(dev))
+    rc = lib.nd_utnet_forward_hw(16, 7, 0, 0, blob.data_ptr(), x.data_ptr(), x.data_ptr(), 1, 104, 104, ws.data_ptr(),
+                                 ws.numel(), _lib.stream_ptr(dev))
     assert rc == -1                                              # unknown activation
-    rc = lib.nd_utnet_forward(16, 1, 0, 64, blob.data_ptr(), x.data_ptr(), x.data_ptr(), 1, 104, ws.data_ptr(), ws.numel(),
-                              _lib.stream_ptr(dev))
+    rc = lib.nd_utnet_forward_hw(16, 1, 0, 64, blob.data_ptr(), x.data_ptr(), x.data_ptr(), 1, 104, 104, ws.data_ptr(),
+                                 ws.numel(), _lib.stream_ptr(dev))
     assert rc == -1 and b"flag" in lib.nd_last_error()           # unknown flag bit
-    assert lib.nd_utnet_workspace_bytes(16, 104, 1, 1) > 0 and lib.nd_utnet_workspace_bytes(8, 104, 1, 1) == 0   # bf16 needs funit%16
+    assert lib.nd_utnet_workspace_bytes_hw(16, 104, 104, 1, 1) > 0 and lib.nd_utnet_workspace_bytes_hw(8, 104, 104, 1, 1) == 0   # bf16 needs funit%16
     torch.cuda.synchronize()
 
 
@@ -1290,7 +1290,7 @@ def _ddp_worker(port, outq):
 
 def test_bucketed_gradient_reduce_over_rccl(dev):
     """BASELINE configs[4] building block: the training step records one event per level bucket while the backward pass runs
-    (nd_utnet_train_step_ev) and the reducer all-reduces each bucket behind its event on a side stream (RCCL, world size 1 here:
+    (nd_utnet_train_step_hw) and the reducer all-reduces each bucket behind its event on a side stream (RCCL, world size 1 here:
     the transport and the event / stream ordering run, the sum is over one rank): two updates give the same parameters and
     gradients as without the reducer, bit for bit."""
     import socket
@@ -1494,7 +1494,7 @@ def test_bench_frame_g24_fp32_launch_shapes_vs_oracle(dev):
     """bench.py's timed configuration (BASELINE configs[1], G24): one 6000x4000 frame, UtNet(64) fp32, cs=264, 256 tiles per
     conv-stack launch -- three-pass Winograd over a 256-tile chunk, split-K tail planning at that size, long plane offsets
     (256 x 178 MB of activations) -- and the frame's last launch of 252 tiles (1276 = 4 x 256 + 252) in the 256-tile workspace.
-    The fused loop bench.py times == gather -> nd_utnet_forward -> stitch of the same five launches; sampled tiles of the first
+    The fused loop bench.py times == gather -> nd_utnet_forward_hw -> stitch of the same five launches; sampled tiles of the first
     and the last launch (first / last of the launch, some past index 128) against the oracle."""
     from nind_denoise_amd import pipeline
     from nind_denoise_amd.networks.UtNet import UtNet

@@ -140,12 +140,12 @@ def test_utnet_module_has_reference_state_dict_layout(golden_dir):
         net(torch.zeros(1, 3, 104, 104))  # CPU tensor: no fallback
 
 
-def test_utnet_pack_whole_net_and_sizes():
+def test_utnet_flops_and_hw_workspace_sizes():
     lib = _lib.load()
     assert lib.nd_utnet_flops(64, 264) == 84_830_297_600.0
     assert lib.nd_utnet_flops(64, 256) == 0.0
-    assert lib.nd_utnet_workspace_bytes(64, 256, 1, 0) == 0
-    assert lib.nd_utnet_workspace_bytes(64, 264, 4, 0) > 4 * 150e6
+    assert lib.nd_utnet_workspace_bytes_hw(64, 256, 256, 1, 0) == 0
+    assert lib.nd_utnet_workspace_bytes_hw(64, 264, 264, 4, 0) > 4 * 150e6
     from nind_denoise_amd.networks.UtNet import UtNet, nearest_valid_cs, valid_cs
     assert [nearest_valid_cs(c) for c in (128, 256, 512, 50)] == [136, 264, 520, 104]
     assert valid_cs(264) and valid_cs(504) and not valid_cs(256)

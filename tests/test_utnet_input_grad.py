@@ -24,16 +24,14 @@ BAND = 3      # rows / columns 0 .. 2 and H-3 .. H-1: every pixel the reflection
 
 # ---------------------------------------------------------------------------- CPU: the C ABI's new entry points
 
-def test_version_and_hw_workspace_sizes():
+def test_abi_version_and_hw_train_workspace_sizes():
     lib = _lib.load()
-    assert lib.nd_version() >= 104
+    assert lib.nd_version() >= 106
     assert lib.nd_utnet_train_workspace_bytes_hw(8, 104, 152, 2) > 0
     assert lib.nd_utnet_train_workspace_bytes_hw(8, 104, 100, 2) == 0       # 100 is not 16k+56
     assert lib.nd_utnet_train_workspace_bytes_hw(8, 110, 104, 2) == 0
     assert lib.nd_utnet_train_workspace_bytes_hw(12, 104, 104, 2) == 0      # funit % 8 != 0
     assert lib.nd_utnet_train_workspace_bytes_hw(8, 104, 104, 0) == 0
-    for funit, cs, b in ((8, 104, 2), (16, 136, 3), (64, 136, 30)):
-        assert lib.nd_utnet_train_workspace_bytes_hw(funit, cs, cs, b) == lib.nd_utnet_train_workspace_bytes(funit, cs, b)
 
 
 # ---------------------------------------------------------------------------- GPU
@@ -233,61 +231,36 @@ def _flat_params(lib, sd, funit, dev):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("flags", [0, _lib.FLAG_NO_SPLITK])
-def test_square_entry_points_equal_hw_forms(dev, flags):
-    """The square ABI is the H x W one with h = w: same outputs, losses and gradients, bit for bit.  And the backward's
-    input gradient does not depend on whether the parameter gradients were requested with it."""
+def test_backward_param_and_input_grads_independent(dev, flags):
+    """The backward's parameter gradients and input gradient do not depend on whether the other one was requested: bit for
+    bit, and a backward without parameter gradients writes none."""
     lib = _lib.load()
     funit, B, cs = 8, 2, 104
     sd = synth.make_utnet_state_dict(funit=funit, seed=31, gain=1.8)
     params = _flat_params(lib, sd, funit, dev)
-    x, t = (a.to(dev) for a in _data(B, cs, cs, 3))
-    nbytes = lib.nd_utnet_train_workspace_bytes(funit, cs, B)
-    assert nbytes == lib.nd_utnet_train_workspace_bytes_hw(funit, cs, cs, B)
+    x = _data(B, cs, cs, 3)[0].to(dev)
+    nbytes = lib.nd_utnet_train_workspace_bytes_hw(funit, cs, cs, B)
     blobs = torch.empty(lib.nd_utnet_train_blob_bytes(funit), dtype=torch.uint8, device=dev)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     s = _lib.stream_ptr(dev)
     _lib.check(lib.nd_utnet_train_workspace_init_hw(ws.data_ptr(), nbytes, funit, cs, cs, B, s))
     act = _lib.ACT["PReLU"]
-
-    def step(hw):
-        y, loss, grads = torch.empty_like(x), torch.zeros(1, device=dev), torch.zeros_like(params)
-        common = (funit, flags, params.data_ptr(), grads.data_ptr(), blobs.data_ptr(), x.data_ptr(), t.data_ptr(), y.data_ptr(),
-                  0.3, 0.7, 0.0, 0.0, loss.data_ptr(), B)
-        if hw:
-            _lib.check(lib.nd_utnet_train_step_hw(*common, cs, cs, 88, ws.data_ptr(), nbytes, s, None, 0))
-        else:
-            _lib.check(lib.nd_utnet_train_step(*common, cs, 88, ws.data_ptr(), nbytes, s))
-        torch.cuda.synchronize()
-        return y, loss, grads
-
-    for a, b in zip(step(False), step(True)):
-        assert torch.equal(a, b)
-
     gy = (torch.rand(B, 3, cs, cs, generator=torch.Generator().manual_seed(4)) - 0.5).to(dev)
 
-    def halves(hw, with_grads=True, with_dx=False):
-        y, grads = torch.empty_like(x), torch.zeros_like(params)
-        dx = torch.zeros_like(x)
-        if hw:
-            _lib.check(lib.nd_utnet_train_forward_hw(funit, act, flags, params.data_ptr(), blobs.data_ptr(), x.data_ptr(),
-                                                     y.data_ptr(), B, cs, cs, ws.data_ptr(), nbytes, s))
-            _lib.check(lib.nd_utnet_train_backward_hw(funit, act, flags, params.data_ptr(), grads.data_ptr() if with_grads else None,
-                                                      blobs.data_ptr(), gy.data_ptr(), dx.data_ptr() if with_dx else None, B, cs,
-                                                      cs, ws.data_ptr(), nbytes, s, None, 0))
-        else:
-            _lib.check(lib.nd_utnet_train_forward(funit, act, flags, params.data_ptr(), blobs.data_ptr(), x.data_ptr(),
-                                                  y.data_ptr(), B, cs, ws.data_ptr(), nbytes, s))
-            _lib.check(lib.nd_utnet_train_backward(funit, act, flags, params.data_ptr(), grads.data_ptr(), blobs.data_ptr(),
-                                                   gy.data_ptr(), B, cs, ws.data_ptr(), nbytes, s, None, 0))
+    def halves(with_grads, with_dx):
+        y, grads, dx = torch.empty_like(x), torch.zeros_like(params), torch.zeros_like(x)
+        _lib.check(lib.nd_utnet_train_forward_hw(funit, act, flags, params.data_ptr(), blobs.data_ptr(), x.data_ptr(),
+                                                 y.data_ptr(), B, cs, cs, ws.data_ptr(), nbytes, s))
+        _lib.check(lib.nd_utnet_train_backward_hw(funit, act, flags, params.data_ptr(), grads.data_ptr() if with_grads else None,
+                                                  blobs.data_ptr(), gy.data_ptr(), dx.data_ptr() if with_dx else None, B, cs,
+                                                  cs, ws.data_ptr(), nbytes, s, None, 0))
         torch.cuda.synchronize()
-        return y, grads, dx
+        return grads, dx
 
-    old, new = halves(False), halves(True)
-    assert torch.equal(old[0], new[0]) and torch.equal(old[1], new[1])
-    both, dx_only = halves(True, True, True), halves(True, False, True)
-    assert torch.equal(both[1], old[1])                     # asking for dx leaves the parameter gradients alone
-    assert torch.equal(both[2], dx_only[2]) and both[2].abs().max().item() > 0
-    assert not dx_only[1].any()                              # grads = NULL: nothing written to a parameter gradient
+    grads_only, both, dx_only = halves(True, False), halves(True, True), halves(False, True)
+    assert torch.equal(both[0], grads_only[0])              # asking for dx leaves the parameter gradients alone
+    assert torch.equal(both[1], dx_only[1]) and both[1].abs().max().item() > 0
+    assert not dx_only[0].any()                              # grads = NULL: nothing written to a parameter gradient
     with pytest.raises(ValueError):                          # a backward asked for nothing
         _lib.check(lib.nd_utnet_train_backward_hw(funit, act, flags, params.data_ptr(), None, blobs.data_ptr(), gy.data_ptr(),
                                                   None, B, cs, cs, ws.data_ptr(), nbytes, s, None, 0))
