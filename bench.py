@@ -3,6 +3,12 @@
 
     python bench.py --gpus N --steps K --warmup W            (N > 1: this process spawns the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (also fine: ranks from the env)
+    python bench.py --gpus N --steps K --warmup W --full     (the headline figure and every other leg, see below)
+
+A plain run sets up, warms up, times the K steps, writes `--dump-outputs` and prints the headline line -- nothing else.
+`--full` adds the legs that measure or check beyond the headline figure, after the timed steps: the roofline profile, the
+whole-tile comparison, the host-to-host rate, the CPU baseline with the parity check, the other single-GPU configurations
+(N = 1), and the compute-only shard time and the replicas rate (N > 1).  The `--no-*` switches drop single legs of a `--full` run.
 
 A "step" is one 6000x4000 frame through the device-resident crop -> UtNet -> stitch loop (BASELINE.json configs[1],
 geometry "G24" of SURVEY.md section 8: cs=264 is the valid tile size nearest to the named 256, which the reference
@@ -15,21 +21,21 @@ rank packs them into MFMA fragment order on its own device), and per frame sends
 receives + adds the canvas rows it wrote (RCCL point-to-point over xGMI).  The stream of frames is software-pipelined
 (nind_denoise_amd/dist.py: ShardedFrameStream): the scatter of frame n+1 and the gather of frame n-1 run on a side stream under
 the compute of frame n.  Total work per step is fixed as N grows -> "scaling": "strong"; `value` = megapixels of the frames that
-left rank 0 / max-over-ranks time.  The same line carries, under `frame_shard`, the rate of N independent REPLICAS (one whole
+left rank 0 / max-over-ranks time.  A `--full` line carries, under `frame_shard`, the rate of N independent REPLICAS (one whole
 frame per rank per step, no data-path traffic) -- labelled as such, not the metric.
 `--frames F` times BASELINE configs[2]'s shape instead (a step = F frames dealt round-robin to the ranks, no per-frame exchange);
 `--frame-per-rank` makes the replicas mode the timed one.
 
 The timed loop is the product's default: every tile's whole cs x cs crop goes in, every layer runs, and the layers of the last
 decoder levels compute only the outputs that the tile's useful centre (what the stitch keeps) depends on; `--whole-tiles` times
-the loop with whole-tile layers instead, and the default run reports that rate and the difference of the two canvases under
+the loop with whole-tile layers instead, and a `--full` run reports that rate and the difference of the two canvases under
 `whole_tiles`.
 
 `--dump-outputs DIR` writes, right after the timed steps, the canvas the last timed step stitched (DIR/canvas.npy; a fixed seeded
 sample of it above 64 MB).  The frames and weights are seeded, so the same arguments give the same inputs on every run, and the
 dumps of two builds compare value for value.
 
-One JSON line on rank 0:
+One JSON line on rank 0; with `--full` it also carries (among others)
   roofline      the dominant kernel by time (conv_w2d, the fused 1-D Winograd 3x3 kernel on the fp32 path): MFMA-EXECUTED
                 FLOP / HIP-event time on the launch stream / MFMA peak (<= 1 by construction); the algorithmic
                 (direct-convolution) rate is reported beside it, and `families` prices every kernel family against its own
@@ -109,7 +115,11 @@ def parse():
     ap.add_argument("--tile-shard", action="store_true", help="(the default for N > 1; kept for older command lines)")
     ap.add_argument("--frame-per-rank", action="store_true",
                     help="N > 1: time N independent replicas (one whole frame per rank per step, no exchange) instead of the tile-sharded stream")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the bf16 G24 / fp16 G61 / fp32 G24d legs of the default single-GPU run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs beyond the headline figure (roofline, whole-tile leg, host-to-host "
+                         "leg, CPU baseline + parity, other configurations; N > 1: compute-only shard time, replicas); the --no-* "
+                         "switches below drop single legs of such a run")
+    ap.add_argument("--no-other-configs", action="store_true", help="skip the bf16 G24 / fp16 G61 / fp32 G24d legs of a --full single-GPU run")
     ap.add_argument("--cpu-sample-tiles", type=int, default=0,
                     help="0: sized for ~10 s of CPU work per mode; -1: the WHOLE frame, un-extrapolated (minutes: for a kept record)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="torch CPU threads of the baseline leg (0: all the cgroup allows, max 64)")
@@ -577,10 +587,13 @@ def main():
 
     mode = "single" if world == 1 and args.frames == 0 else ("frames" if args.frames > 0 else ("replicas" if args.frame_per_rank else "tile-stream"))
     lo, hi = geo.shard(rank, world) if mode == "tile-stream" else (0, total)
-    # a few distinct synthetic frames resident in HBM are cycled (the arithmetic does not depend on the pixel values)
+    # a few distinct synthetic frames resident in HBM are cycled (the arithmetic does not depend on the pixel values); the
+    # single-GPU loop times the first one alone
     if rank == 0 or mode in ("frames", "replicas"):
         frame_np = synth.make_frame(W, H, seed=24)
-        pool = [torch.from_numpy(frame_np).to(dev)] + [torch.from_numpy(synth.make_frame(W, H, seed=s_)).to(dev) for s_ in (25, 26)]
+        pool = [torch.from_numpy(frame_np).to(dev)]
+        if mode != "single":
+            pool += [torch.from_numpy(synth.make_frame(W, H, seed=s_)).to(dev) for s_ in (25, 26)]
     else:
         pool = []
     canvas = torch.zeros((3, H, W), dtype=torch.float32, device=dev)
@@ -641,7 +654,7 @@ def main():
 
     dt = max_over_ranks(dt)
     extra = {}
-    if mode == "tile-stream":
+    if args.full and mode == "tile-stream":
         # compute-only time of this rank's shard (no exchange): what a step would cost if the exchange were free
         compute(pool[0] if rank == 0 else stream.frames[0], stream.canvas[0], lo, hi)
         torch.cuda.synchronize()
@@ -730,14 +743,14 @@ def main():
 
     flop_frame = net.flops_per_tile(cs) * total
     out["end_to_end_algorithmic_tflops"] = round(flop_frame * frames_per_step * args.steps / dt / 1e12, 3)
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # (N > 1: rank 0 profiles the conv stack at the launch size of its own tile shard)
         b = min(args.batch, hi - lo)
         steps = conv_stack_profile(net, cs, b, dev, crop=(cs - ucs) // 2)
         log("conv stack profile done")
         out["roofline"] = roofline_report(steps, args.dtype, cs, b, args.funit)
         out["config"]["computed_flop_per_frame"] = sum(s_["flop"] for s_ in steps) / b * total   # conv stack, regions counted as computed
-    if mode == "single" and not args.whole_tiles and not args.no_whole_leg:
+    if args.full and mode == "single" and not args.whole_tiles and not args.no_whole_leg:
         # the same frame with every layer on whole tiles (what UtNet.forward computes): its rate, and the two canvases compared
         cv_roi = canvas.clone()
         net.useful_only = False
@@ -751,7 +764,7 @@ def main():
         net.useful_only = True
         del cv_roi
         log(f"whole-tile leg: {out['whole_tiles']['value']} MP/s, canvases differ by {diff:.2e}")
-    if not args.no_host_leg and mode == "single":
+    if args.full and not args.no_host_leg and mode == "single":
         # SURVEY.md 8(d)'s end-to-end definition: decoded fp32 frame in pinned host memory -> stitched frame in host memory,
         # through the resident engine (H2D / compute / D2H overlapped over a ring of 3 slots).  Reported beside `value`.
         from nind_denoise_amd.serve import FrameEngine
@@ -772,7 +785,7 @@ def main():
         del eng
         log("host-to-host leg done")
     threads = args.cpu_threads or min(host_cores(), 64)
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         n = args.cpu_sample_tiles or max(8, min(200, threads * 6))   # ~10 s of CPU work per mode at ~0.1 s/tile
         ids = list(range(total)) if n < 0 else sample_runs(total, n, run=8)
         n = len(ids)
@@ -798,7 +811,7 @@ def main():
                         "-- stitched into a zero canvas, against the oracle's stitched canvas of the cpu_baseline tiles, on the pixels only those tiles touch")
         out["parity"] = par_
         log(f"parity on {n} tiles ({par_['canvas_values_compared']} canvas values): max abs {par_['max_abs']:.3e}")
-    if mode == "single" and not args.no_other_configs and args.dtype == "f32" and (W, H, cs, ucs, ol) == (6000, 4000, 264, 200, 64):
+    if args.full and mode == "single" and not args.no_other_configs and args.dtype == "f32" and (W, H, cs, ucs, ol) == (6000, 4000, 264, 200, 64):
         del pool, canvas
         net._workspaces.clear()
         torch.cuda.empty_cache()

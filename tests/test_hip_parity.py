@@ -1729,15 +1729,15 @@ def test_pipelined_frame_stream_with_hip_compute(dev, world):
 
 
 def test_bench_n2_rehearsal_line(dev, tmp_path):
-    """`bench.py --gpus 2` end to end on the one-GPU box (ND_BENCH_REHEARSAL=1: both ranks on GPU 0, messages over gloo): the launcher
-    spawns the ranks, the default N > 1 mode is the pipelined tile-shard stream, the parameters are broadcast from rank 0, rank 0
-    prints ONE JSON line that names the partition and carries the pipeline / replicas keys."""
+    """`bench.py --gpus 2 --full` end to end on a one-GPU machine (ND_BENCH_REHEARSAL=1: both ranks on GPU 0, messages over gloo): the
+    launcher spawns the ranks, the default N > 1 mode is the pipelined tile-shard stream, the parameters are broadcast from rank 0,
+    rank 0 prints ONE JSON line that names the partition and carries the pipeline / replicas keys."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, ND_BENCH_REHEARSAL="1")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--width", "1500",
-                        "--height", "1100", "--funit", "16", "--batch", "32", "--no-roofline", "--dump-outputs", str(tmp_path / "dump")],
+                        "--height", "1100", "--funit", "16", "--batch", "32", "--full", "--no-roofline", "--dump-outputs", str(tmp_path / "dump")],
                        env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -1780,6 +1780,28 @@ def test_bench_dump_outputs_is_the_timed_canvas(dev, tmp_path):
     net = net.eval().to(dev)
     want = pipeline.denoise_frame(net, torch.from_numpy(synth.make_frame(1500, 1100, seed=24)).to(dev), 264, 200, 64, batch=32)
     assert got.dtype == np.float32 and np.array_equal(got, want.cpu().numpy())
+
+
+def test_bench_plain_line_and_full_legs(dev):
+    """`bench.py` without --full times its steps and prints the headline line, with none of the other legs; --full on the same
+    arguments adds the roofline, whole-tile, host-to-host and CPU baseline legs, and the timed path meets its parity bar there."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--width", "1500",
+           "--height", "1100", "--funit", "16", "--batch", "32"]
+    lines = []
+    for extra in ([], ["--full", "--cpu-sample-tiles", "16"]):
+        r = subprocess.run(cmd + extra, cwd=root, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    plain, full = lines
+    for d in lines:
+        assert d["steps"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    legs = {"roofline", "whole_tiles", "host_to_host", "cpu_baseline", "parity", "other_configs", "pipeline", "frame_shard"}
+    assert not legs & plain.keys() and "computed_flop_per_frame" not in plain["config"], sorted(plain)
+    assert {"roofline", "whole_tiles", "host_to_host", "cpu_baseline", "parity"} <= full.keys(), sorted(full)
+    assert full["parity"]["ok"] and full["parity"]["tiles"] == 16, full["parity"]
 
 
 # ---------------------------------------------------------------------------- fixtures executed by the reference itself
