@@ -218,13 +218,17 @@ int nd_launch_gather_strips(const float *img, int W, int H, int cs, int ucs, int
 
 // dst image t, plane dst_p0 + p, interior pixel (r, c) of [r0, r1) x [c0, c1)  <-  src image img_mul * t + img_add, plane
 // src_p0 + p, interior pixel (yrel * step + r + oy, xi * step + c + ox), (yi, xi) = grid position of tile tile_begin + t,
-// yrel = yi - row0.  A band tensor: img_mul = 0, step = the tile stride at its level; a strip: step = 0.
+// yrel = yi - row0.  A band tensor: img_mul = 0, step = the tile stride at its level; a strip: step = 0.  band_rows > 0: the source
+// holds bands of band_rows tile rows in two slots, slot_elems apart -- a tile reads band yi / band_rows in slot (band & 1), row0 =
+// the band's first tile row (a launch may cross a band seam).
 struct SpliceArgs {
     const f32x4 *src;
     f32x4 *dst;
     long src_np, dst_np;
     int src_Hb, src_Wb, src_pad, dst_Hb, dst_Wb, dst_pad;
     int tile_begin, cols, row0, step, img_mul, img_add, oy, ox, r0, c0, rows, ccols, planes;
+    int band_rows;
+    long slot_elems;
 };
 __global__ void k_splice(SpliceArgs a) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;   // pixel of the region, row-major (a region may be one column wide)
@@ -233,23 +237,28 @@ __global__ void k_splice(SpliceArgs a) {
     const int t = blockIdx.y / a.planes, p = blockIdx.y - t * a.planes;
     const int i = a.tile_begin + t;
     const int yi = i / a.cols, xi = i - yi * a.cols;
-    const int sy = (yi - a.row0) * a.step + r + a.oy + a.src_pad, sx = xi * a.step + c + a.ox + a.src_pad;
-    const long si = (long)p * a.src_np + ((long)(a.img_mul * t + a.img_add) * a.src_Hb + sy) * a.src_Wb + sx;
+    const int band = a.band_rows > 0 ? yi / a.band_rows : 0, row0 = a.band_rows > 0 ? band * a.band_rows : a.row0;
+    const int sy = (yi - row0) * a.step + r + a.oy + a.src_pad, sx = xi * a.step + c + a.ox + a.src_pad;
+    const long si = (long)p * a.src_np + (band & 1) * a.slot_elems + ((long)(a.img_mul * t + a.img_add) * a.src_Hb + sy) * a.src_Wb + sx;
     a.dst[(long)p * a.dst_np + ((long)t * a.dst_Hb + r + a.dst_pad) * a.dst_Wb + c + a.dst_pad] = a.src[si];
 }
 
 int nd_launch_splice(const QpBuf &src, int src_p0, const QpBuf &dst, int dst_p0, int planes, int tile_begin, int tile_count, int cols,
-                     int row0, int step, int img_mul, int img_add, int oy, int ox, int r0, int r1, int c0, int c1, hipStream_t s) {
+                     int row0, int step, int img_mul, int img_add, int oy, int ox, int r0, int r1, int c0, int c1, hipStream_t s,
+                     int band_rows, long slot_elems) {
     const int sH = src.Hb - 2 * src.pad, sW = src.Wb - 2 * src.pad, dH = dst.Hb - 2 * dst.pad, dW = dst.Wb - 2 * dst.pad;
-    // the source pixels of the first / last tile row and of grid columns 0 / cols - 1 bound those of every tile (offsets are linear)
-    const int yf = tile_begin / cols - row0, yl = (tile_begin + tile_count - 1) / cols - row0;
-    const int xl = tile_count >= cols ? cols - 1 : ((tile_begin / cols == (tile_begin + tile_count - 1) / cols) ? (tile_begin + tile_count - 1) % cols : cols - 1);
-    const int xf = tile_count >= cols || tile_begin / cols != (tile_begin + tile_count - 1) / cols ? 0 : tile_begin % cols;
-    const bool ok = src.dt == ND_F32 && dst.dt == ND_F32 && tile_count > 0 && tile_count <= dst.B && planes > 0 && yf >= 0 &&
-                    src_p0 >= 0 && src_p0 + planes <= src.planes && dst_p0 >= 0 && dst_p0 + planes <= dst.planes &&
-                    r0 >= 0 && c0 >= 0 && r1 > r0 && c1 > c0 && r1 <= dH && c1 <= dW &&
-                    yf * step + r0 + oy >= 0 && yl * step + r1 - 1 + oy < sH && xf * step + c0 + ox >= 0 && xl * step + c1 - 1 + ox < sW &&
-                    img_add >= 0 && img_mul * (tile_count - 1) + img_add < src.B && (long)tile_count * planes <= 65535;
+    bool ok = src.dt == ND_F32 && dst.dt == ND_F32 && tile_begin >= 0 && cols > 0 && tile_count > 0 && tile_count <= dst.B && planes > 0 &&
+              src_p0 >= 0 && src_p0 + planes <= src.planes && dst_p0 >= 0 && dst_p0 + planes <= dst.planes &&
+              r0 >= 0 && c0 >= 0 && r1 > r0 && c1 > c0 && r1 <= dH && c1 <= dW && band_rows >= 0 &&
+              (band_rows == 0 || (slot_elems >= 0 && img_mul == 0 && img_add == 0)) &&
+              img_add >= 0 && img_mul * (tile_count - 1) + img_add < src.B && (long)tile_count * planes <= 65535;
+    // the source window of every tile of the launch (a launch has at most a few hundred tiles)
+    for (int t = 0; t < tile_count && ok; ++t) {
+        const int yi = (tile_begin + t) / cols, xi = (tile_begin + t) % cols;
+        const int yrel = yi - (band_rows > 0 ? yi / band_rows * band_rows : row0);
+        if (band_rows > 0 && (yi / band_rows & 1)) ok = slot_elems >= (long)src.Hb * src.Wb && slot_elems + (long)src.Hb * src.Wb <= src.np();
+        ok = ok && yrel >= 0 && yrel * step + r0 + oy >= 0 && yrel * step + r1 - 1 + oy < sH && xi * step + c0 + ox >= 0 && xi * step + c1 - 1 + ox < sW;
+    }
     if (!ok) ND_FAIL(ND_EINVAL, "splice: region [%d,%d) x [%d,%d) of %d tiles x %d planes outside its source / destination", r0, r1, c0, c1,
                      tile_count, planes);
     SpliceArgs a;
@@ -260,8 +269,40 @@ int nd_launch_splice(const QpBuf &src, int src_p0, const QpBuf &dst, int dst_p0,
     a.dst_Hb = dst.Hb; a.dst_Wb = dst.Wb; a.dst_pad = dst.pad;
     a.tile_begin = tile_begin; a.cols = cols; a.row0 = row0; a.step = step; a.img_mul = img_mul; a.img_add = img_add;
     a.oy = oy; a.ox = ox; a.r0 = r0; a.c0 = c0; a.rows = r1 - r0; a.ccols = c1 - c0; a.planes = planes;
+    a.band_rows = band_rows; a.slot_elems = slot_elems;
     dim3 grid(((r1 - r0) * (c1 - c0) + 255) / 256, tile_count * planes);
     hipLaunchKernelGGL(k_splice, grid, dim3(256), 0, s, a);
+    ND_HIP(hipGetLastError());
+    return ND_OK;
+}
+
+// The conv kernels that read a skip half in place (ConvDesc::in2) take the tile's place in the band plane from a table in HBM: the
+// division by `cols` and the band bookkeeping stay out of them.  One thread per tile of the launch.
+__host__ __device__ static inline long skip_origin(int i, int cols, int band_rows, int step, int Wb, int dpad, long slot_elems) {
+    const int yi = i / cols, xi = i - yi * cols, band = yi / band_rows;
+    return (band & 1) * slot_elems + (long)((yi - band * band_rows) * step + dpad) * Wb + xi * step + dpad;
+}
+__global__ void k_skip_origins(int tile_begin, int tile_count, int cols, int band_rows, int step, int Wb, int dpad, long slot_elems,
+                               int *__restrict__ table) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= tile_count) return;
+    table[t] = (int)skip_origin(tile_begin + t, cols, band_rows, step, Wb, dpad, slot_elems);
+}
+
+int nd_launch_skip_origins(const QpBuf &src, int dst_pad, int tile_begin, int tile_count, int cols, int band_rows, int step, long slot_elems,
+                           int *table, long *origin_max, hipStream_t s) {
+    const int dpad = src.pad - dst_pad;
+    if (!table || tile_begin < 0 || tile_count <= 0 || cols <= 0 || band_rows <= 0 || step < 0 || dpad < 0 || slot_elems < 0 || src.B != 1)
+        ND_FAIL(ND_EINVAL, "skip_origins: bad tile range [%d,+%d) / %d rows per band", tile_begin, tile_count, band_rows);
+    long omax = 0;
+    for (int t = 0; t < tile_count; ++t) {
+        const long o = skip_origin(tile_begin + t, cols, band_rows, step, src.Wb, dpad, slot_elems);
+        omax = o > omax ? o : omax;
+    }
+    if (omax >= (1L << 31)) ND_FAIL(ND_EINVAL, "skip_origins: origin %ld exceeds 32 bits", omax);
+    if (origin_max) *origin_max = omax;
+    hipLaunchKernelGGL(k_skip_origins, dim3((tile_count + 255) / 256), dim3(256), 0, s, tile_begin, tile_count, cols, band_rows, step, src.Wb,
+                       dpad, slot_elems, table);
     ND_HIP(hipGetLastError());
     return ND_OK;
 }

@@ -123,6 +123,12 @@ struct ConvParams {
     // in band -- so that a 2x2 pooling block is four consecutive pixels of an N tile, i.e. four adjacent lanes of one accumulator
     int band2;
     FastDiv fd_2Wv;   // divider by 2 * Wv
+    // conv_w2d.hip, second input source (ConvDesc::in2; null: none): K blocks [kb2, KB) read plane 2 * (kb - kb2) + half of in2, where
+    // the bordered pixel (y, x) of image t is element origin2[t] + y * Wb2 + x
+    const f32x4 *in2;
+    long in2_plane;
+    const int *origin2;
+    int kb2, Wb2;
 };
 
 static inline void nd_conv_fastdivs(ConvParams &p) {

@@ -79,7 +79,9 @@ __device__ __forceinline__ unsigned long long stamp() {
 // decoded strip: image, first output row, first output column
 struct Strip { int img, y0, x0; bool ok; };
 
-template <int DBG>   // ablation bits for timing experiments (tools/w2d_ablate.sh); 0 = the production kernel
+// DBG: ablation bits for timing experiments (tools/w2d_ablate.sh); 0 = the production kernel.  SRC2: the layer has a second input
+// source (ConvParams::in2) -- an instantiation of its own, so that the kernel every other layer runs keeps its registers
+template <int DBG, bool SRC2 = false>
 __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
@@ -139,6 +141,7 @@ __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
     // stamps).  One half of the waves (p.dbg bit 0: which) loads and transforms the pixels (pass A: 4 x 64 = 256
     // of the 320 lane-transforms, pass B: the other 64 on one more wave), three waves issue the 36 weight pieces by LDS-DMA.
     int f_id = vb, f_c = 0, f_end = 0, f_stage = 0, issued = 0;
+    int f_nb = 0;   // SRC2: the fill tile's N tile
     const float *f_w;
     // Roles (tools/w2d_roles.sh tried twelve assignments: all within 3 % of each other): waves 4..7 load + transform the pixels
     // (pass A), wave 0 pass B; waves 0..3 issue the weight DMA, 9 contiguous pieces each.
@@ -164,6 +167,7 @@ __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
         f_end = it.c1;
         const int nb = (int)fdiv((unsigned)it.tile, p.fd_ntm), mb = it.tile - nb * p.n_tiles_m;
         f_w = p.wpk + (size_t)mb * kMTB * p.KB * kTaps * 256;     // wave-uniform: the lane's 16 bytes are added as a 32-bit offset
+        if constexpr (SRC2) f_nb = nb;
 #pragma unroll
         for (int ps = 0; ps < 2; ++ps)
             if (ps == 0 ? xfA : xfB) {
@@ -173,7 +177,20 @@ __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
                 x_keep[ps] = left + 2 < 6 ? left + 2 : 6;
             }
     };
+    // SRC2: a tile's K blocks switch to the second source at p.kb2.  The lane's offset is recomputed there (once per tile, or when a
+    // split-K item starts behind the switch) instead of held twice.  (This instantiation is never pooled and keeps no pre-activation
+    // copy -- the launcher refuses both -- which is what leaves it registers to spare: with those paths compiled in it spilled)
+    auto set_fill_src2 = [&]() {
+        const int nb = f_nb;
+#pragma unroll
+        for (int ps = 0; ps < 2; ++ps)
+            if (ps == 0 ? xfA : xfB) {
+                const Strip st = strip_of(nb, x_s[ps]);
+                x_off[ps] = 16u * ((unsigned)x_h[ps] * (unsigned)p.in2_plane + (unsigned)p.origin2[st.img] + (unsigned)(st.y0 + x_i[ps]) * p.Wb2 + st.x0);
+            }
+    };
     set_fill_tile(f_id);
+    if constexpr (SRC2) if (f_c >= p.kb2) set_fill_src2();
     f32x4 dn[2][6];
 #pragma unroll
     for (int ps = 0; ps < 2; ++ps)
@@ -186,7 +203,9 @@ __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
     // priority -- DESIGN.md section 4.)
     auto fill_loads = [&]() {
         if (issued >= nsteps || (DBG & 8)) return;
-        const char *kbase = (const char *)(p.in + (size_t)(2 * f_c) * p.in_plane);   // scalar; x_off is a 32-bit BYTE offset
+        const bool s2 = SRC2 && f_c >= p.kb2;   // wave-uniform: the K block comes from the second source (a split-K chunk may straddle the switch)
+        const char *kbase = s2 ? (const char *)(p.in2 + (size_t)(2 * (f_c - p.kb2)) * p.in2_plane)
+                               : (const char *)(p.in + (size_t)(2 * f_c) * p.in_plane);   // scalar; x_off is a 32-bit BYTE offset
         if (xfA) {
 #pragma unroll
             for (int k = 0; k < 6; ++k) dn[0][k] = *(const f32x4 *)(kbase + x_off[0] + 16 * k);
@@ -241,7 +260,12 @@ __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
         f_stage ^= 1;
         if (++f_c == f_end) {
             f_id += nwg;
-            if (f_id < nitems) set_fill_tile(f_id);
+            if (f_id < nitems) {
+                set_fill_tile(f_id);
+                if constexpr (SRC2) if (f_c >= p.kb2) set_fill_src2();   // (a split-K item that starts behind the switch)
+            }
+        } else if constexpr (SRC2) {
+            if (f_c == p.kb2) set_fill_src2();
         }
     };
 
@@ -306,7 +330,7 @@ __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
         // row e_row, pooled pixel e_px & 1 of the strip the lane already decoded (strips start on rows = 0 mod 8, pixels = 0 mod 4)
         const int pp_i = (e_px & ~3) + 2 * (e_px & 1);              // scratch column of the 2x2 block's first pixel
         const int pxp = (st.x0 >> 1) + (e_px & 1), pyp = (st.y0 >> 1) + e_row;
-        const bool okP = p.pool && !(lane & 2) && st.ok && 2 * pxp + 1 < p.wpx && 2 * pyp + 1 < p.Hv;
+        const bool okP = !SRC2 && p.pool && !(lane & 2) && st.ok && 2 * pxp + 1 < p.wpx && 2 * pyp + 1 < p.Hv;
         const unsigned offP = (unsigned)((st.img * p.pool_P + (pyp + p.pool_pad) * p.pool_W + pxp + p.pool_pad) * 16);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -341,7 +365,7 @@ __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
                     yy[i][2 * pr + 1] = y[i][1];
                 }
             }
-            if (p.pre) {   // training forward: acc + bias for the activation's backward pass, compact planes [C/4][B][Hv][wpx]
+            if (!SRC2 && p.pre) {   // training forward: acc + bias for the activation's backward pass, compact planes [C/4][B][Hv][wpx]
                 const Strip so = strip_of(nb, sl);
                 const int yo = so.y0 + rr, m4 = (q0 + 2 * g + h) * 4, left = p.wpx - so.x0;
                 if (so.ok && yo < p.Hv && m4 < p.M) {
@@ -378,7 +402,7 @@ __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
                 const f32x4 va = *((const f32x4 *)scratch + e_row * 16 + e_px);
                 const f32x4 vb2 = *((const f32x4 *)scratch + (e_row + 4) * 16 + e_px);
                 f32x4 vp = va;
-                if (p.pool) {   // wave-uniform
+                if (!SRC2 && p.pool) {   // wave-uniform
                     const f32x4 *blk = (const f32x4 *)scratch + (2 * e_row) * 16 + pp_i;
                     const f32x4 p00 = blk[0], p01 = blk[1], p10 = blk[16], p11 = blk[17];
 #pragma unroll
@@ -553,7 +577,11 @@ int nd_launch_conv_w2d(const ConvDesc &d, hipStream_t stream) {
     const int Hv = roi ? d.roi_rows : Hfull, Wpx = roi ? d.roi_cols : Wfull, Wg = (Wpx + 3) / 4, NB = (Hv + kR - 1) / kR;
     if (d.pre && (roi || d.pool)) ND_FAIL(ND_EINVAL, "w2d: a pre-activation copy goes with whole, unpooled layers only");
     if (d.cout % 4) ND_FAIL(ND_EINVAL, "w2d: cout must be a multiple of 4");
-    ND_TRY(nd_check_in_planes("w2d", d, KB));
+    ND_TRY(nd_check_in_planes("w2d", d, KB, true));
+    const bool src2 = d.in2.base != nullptr;
+    if (src2 && (d.pool || d.pre)) ND_FAIL(ND_EINVAL, "w2d: a layer with a second input source is neither pooled nor keeps a pre-activation copy");
+    // (a strip of the last band / group reads kR + 2 rows x 6 pixels from its first pixel, valid or not: see below)
+    if (src2) ND_TRY(nd_check_in2("w2d", d, KB, (long)(d.roi_r0 + (NB - 1) * kR + kRI - 1) * d.in2.Wb + d.roi_c0 + 4 * (Wg - 1) + 6));
     ND_TRY(nd_check_out("w2d", d, Hfull, Wfull, false));
     // a lane's float4 index inside a K block's two-plane window is 32 bits; strips of the last band / group read up to 9 rows + 5
     // pixels past the last valid pixel (the buffers carry that slack)
@@ -562,10 +590,11 @@ int nd_launch_conv_w2d(const ConvDesc &d, hipStream_t stream) {
 
     int dev = 0, ncus = 0;
     ND_TRY(nd_device(&dev, &ncus));
-    void (*fn)(ConvParams) = conv_w2d<0>;
+    void (*fn)(ConvParams) = src2 ? conv_w2d<0, true> : conv_w2d<0>;
 #ifdef ND_QP_STAMPS
     // diagnostic build only (make STAMPS=1; tools/w2d_ablate.sh): ND_W2D_DBG names one of the ablation masks / the stamped kernel
-    static const int dbg_env = getenv("ND_W2D_DBG") ? atoi(getenv("ND_W2D_DBG")) : 0;
+    static const int dbg_all = getenv("ND_W2D_DBG") ? atoi(getenv("ND_W2D_DBG")) : 0;
+    const int dbg_env = src2 ? 0 : dbg_all;   // (a layer with a second input source runs the production kernel)
     switch (dbg_env) {
         case 1: fn = conv_w2d<1>; break;
         case 2: fn = conv_w2d<2>; break;
@@ -588,6 +617,13 @@ int nd_launch_conv_w2d(const ConvDesc &d, hipStream_t stream) {
     if (roi) {
         p.in += (long)d.roi_r0 * d.in.Wb + d.roi_c0;
         p.out += (long)d.roi_r0 * d.out.Wb + d.roi_c0;
+    }
+    if (src2) {
+        p.in2 = (const f32x4 *)d.in2.base + (long)d.in2_plane0 * d.in2.np() + (roi ? (long)d.roi_r0 * d.in2.Wb + d.roi_c0 : 0);
+        p.in2_plane = d.in2.np();
+        p.origin2 = d.in2_origin;
+        p.kb2 = d.in2_from / 2;
+        p.Wb2 = d.in2.Wb;
     }
     p.Hv = Hv;
     p.Wv = Wg;               // groups per row

@@ -51,8 +51,23 @@ int nd_once_per_device(int dev, int (*init)()) {
 }
 
 // ------------------------------------------------------------------ checks of a conv layer
-int nd_check_in_planes(const char *who, const ConvDesc &d, int KB) {
+int nd_check_in_planes(const char *who, const ConvDesc &d, int KB, bool takes_in2) {
     if (d.in.planes < d.in_plane0 + 2 * KB) ND_FAIL(ND_EINVAL, "%s: input buffer has %d planes, needs %d", who, d.in.planes, d.in_plane0 + 2 * KB);
+    if (d.in2.base && !takes_in2) ND_FAIL(ND_EINVAL, "%s: this kernel form has no second input source", who);
+    return ND_OK;
+}
+
+int nd_check_in2(const char *who, const ConvDesc &d, int KB, long reach) {
+    const QpBuf &q = d.in2;
+    const int n2 = 2 * KB - d.in2_from;   // planes read from the second source
+    if (q.dt != ND_F32 || d.in.dt != ND_F32 || !d.in2_origin || d.in2_from <= 0 || (d.in2_from & 1) || n2 <= 0 || d.in2_plane0 < 0 ||
+        d.in2_plane0 + n2 > q.planes || d.in2_origin_max < 0 || reach <= 0)
+        ND_FAIL(ND_EINVAL, "%s: second input source: planes [%d,+%d) of %d from input plane %d of %d", who, d.in2_plane0, n2, q.planes,
+                d.in2_from, 2 * KB);
+    // the last plane read ends where the buffer's slack ends; every other plane is followed by a plane
+    const long last = d.in2_origin_max + reach, room = (long)(q.planes - d.in2_plane0 - n2 + 1) * q.np() + (long)nd_buf_slack(q.Wb);
+    if (last > room) ND_FAIL(ND_EINVAL, "%s: second input source: a launch reaches element %ld of a plane, the buffer ends at %ld", who, last, room);
+    if ((2 * q.np() + last) * 16 + 65536 >= (1L << 32)) ND_FAIL(ND_EINVAL, "%s: second input source too large for 32-bit byte offsets", who);
     return ND_OK;
 }
 

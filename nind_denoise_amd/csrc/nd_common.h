@@ -78,7 +78,19 @@ struct ConvDesc {
     // 2x2 stride-2 transpose: rectangle of the INPUT grid (each input pixel makes its 2x2 outputs).  Used by the fused denoise
     // loop: the last decoder levels only compute what the useful crop of a tile can reach (utnet_net.h: plan_rois)
     int roi_r0 = 0, roi_c0 = 0, roi_rows = 0, roi_cols = 0;
+    // second input source (in2.base null: none; conv_w2d and the three-pass F(6x6) form): input planes [in2_from, 2 KB) of `in`
+    // are not read from `in` but from planes in2_plane0 + (k - in2_from) of `in2`, where bordered pixel (y, x) of image t is element
+    // in2_origin[t] + y * in2.Wb + x of the plane.  The fused denoise loop reads the skip half of a concat straight from the
+    // band tensor the shared encoder wrote (origins: nd_launch_skip_origins).  in2_origin lives in HBM, one entry per image of the
+    // launch; in2_origin_max bounds its entries (the launcher checks the furthest read against in2 and its slack with it)
+    QpBuf in2 = {};
+    int in2_plane0 = 0, in2_from = 0;
+    const int *in2_origin = nullptr;
+    long in2_origin_max = 0;
 };
+// the furthest element (exclusive) of a plane of d.in2 a launch may touch stays inside the buffer and its slack: `reach` = elements
+// past an image's origin (its window in the layer's bordered input, the kernel's over-read included)
+int nd_check_in2(const char *who, const ConvDesc &d, int KB, long reach);
 // scratch that lets every layer split its partial round: 512 work items of 64 x 1024 accumulators
 static const size_t kSplitScratchBytes = (size_t)512 * 64 * 1024 * 4;
 int nd_launch_conv(const ConvDesc &d, hipStream_t stream);
@@ -119,8 +131,9 @@ int nd_device(int *dev, int *ncus = nullptr);
 int nd_raise_lds(int dev, const void *fn, size_t bytes);
 // runs init() once per device (the first caller on a device runs it; the others wait until it has succeeded)
 int nd_once_per_device(int dev, int (*init)());
-// checks of a conv layer; `who` is the launcher's error prefix.  Input planes [in_plane0, in_plane0 + 2 KB) exist
-int nd_check_in_planes(const char *who, const ConvDesc &d, int KB);
+// checks of a conv layer; `who` is the launcher's error prefix.  Input planes [in_plane0, in_plane0 + 2 KB) exist; a launcher
+// that does not take a second input source (takes_in2) refuses a layer that has one
+int nd_check_in_planes(const char *who, const ConvDesc &d, int KB, bool takes_in2 = false);
 // the destination holds B images of oh x ow plus its border (at_least: or more) and planes [out_plane0, out_plane0 + cout / cpp)
 int nd_check_out(const char *who, const ConvDesc &d, int oh, int ow, bool at_least);
 // the linear pixel index of `in` fits int32
@@ -197,5 +210,12 @@ int nd_launch_gather_band(const float *img, int width, int height, int cs, int u
                           hipStream_t s);
 int nd_launch_gather_strips(const float *img, int width, int height, int cs, int ucs, int ol, int tile_begin, int tile_count,
                             bool vertical, const QpBuf &dst, hipStream_t s);
+// table[t] = where bordered pixel (0, 0) of tile tile_begin + t's buffer (border dst_pad) lies inside a plane of band tensor `src`
+// at a level with tile stride `step`: (band & 1) * slot_elems + ((yi - row0) * step + src.pad - dst_pad) * src.Wb + xi * step +
+// src.pad - dst_pad, with (yi, xi) = the tile's grid position, band = yi / band_rows its band and row0 = band * band_rows that
+// band's first tile row.  Written on the stream (no host-to-device copy); *origin_max = the largest entry
+int nd_launch_skip_origins(const QpBuf &src, int dst_pad, int tile_begin, int tile_count, int cols, int band_rows, int step, long slot_elems,
+                           int *table, long *origin_max, hipStream_t s);
 int nd_launch_splice(const QpBuf &src, int src_p0, const QpBuf &dst, int dst_p0, int planes, int tile_begin, int tile_count, int cols,
-                     int row0, int step, int img_mul, int img_add, int oy, int ox, int r0, int r1, int c0, int c1, hipStream_t s);
+                     int row0, int step, int img_mul, int img_add, int oy, int ox, int r0, int r1, int c0, int c1, hipStream_t s,
+                     int band_rows = 0, long slot_elems = 0);

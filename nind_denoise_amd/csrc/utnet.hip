@@ -220,48 +220,81 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
     const float *blob = (const float *)packed;
     const float *fw = blob + bl.off[kNumLayers - 1];
     char *const band_base = (char *)fws, *const sh_base = band_base + fp.band_bytes, *const sv_base = sh_base + fp.strip_bytes;
+    int *const origins = (int *)(sv_base + fp.strip_bytes);
     const int f4 = funit / 4, cols = fp.cols, S = fp.S;
     StackOpts enc, dec;   // the shared steps of a band / strip batch; the rest of a tile's stack, on the useful regions
     enc.flags = dec.flags = flags;
     enc.step_end = dec.step_begin = kSharedSteps;
     dec.rois = rois;
-    int n = 0;
-    for (int b = tile_begin / (fp.R * cols); b < fp.nbands && b * fp.R * cols < end; ++b) {
-        const int row0 = b * fp.R, nrows = fp.rows - row0 < fp.R ? fp.rows - row0 : fp.R;
-        const int bt0 = tile_begin > row0 * cols ? tile_begin : row0 * cols, bt1 = end < (row0 + nrows) * cols ? end : (row0 + nrows) * cols;
-        // the band: its rows of tiles on the mirrored frame, steps [0, kSharedSteps) once
-        Plan bp = make_enc_plan(funit, band_hx(fp, nrows, cs), fp.wx, 1, fp.hx, fp.wx, 1, band_base, dtype);
-        bp.split = pl.split;
-        ND_TRY(nd_launch_gather_band(img, width, height, cs, ucs, ol, row0, bp.buf[X0], s));
-        ND_TRY(run_stack(funit, act, dtype, blob, bp, s, enc));
-        // its tiles in near-equal launches of at most `batch`
-        const int nt = bt1 - bt0, nl = (nt + batch - 1) / batch;
-        for (int j = 0; j < nl; ++j, ++n) {
-            const int t0 = bt0 + (int)((long)nt * j / nl), cnt = bt0 + (int)((long)nt * (j + 1) / nl) - t0;
-            if (progress) progress(progress_ctx, n, t0, cnt);
-            // border strips: images 2t / 2t + 1 = top / bottom rows (sh), left / right columns (sv) of tile t's input
-            Plan sh = make_enc_plan(funit, kStrip, cs + 4, 2 * cnt, kStrip, cs + 4, 2 * batch, sh_base, dtype);
-            Plan sv = make_enc_plan(funit, cs + 4, kStrip, 2 * cnt, cs + 4, kStrip, 2 * batch, sv_base, dtype);
-            sh.split = sv.split = pl.split;
-            ND_TRY(nd_launch_gather_strips(img, width, height, cs, ucs, ol, t0, cnt, false, sh.buf[X0], s));
-            ND_TRY(nd_launch_gather_strips(img, width, height, cs, ucs, ol, t0, cnt, true, sv.buf[X0], s));
-            ND_TRY(run_stack(funit, act, dtype, blob, sh, s, enc));
-            ND_TRY(run_stack(funit, act, dtype, blob, sv, s, enc));
-            // per tile: the skip halves over the window the decoder reads, P2 whole, then P2's border lines from the strips
-            const Plan tp = make_plan(funit, cs, cs, batch, cnt, (char *)ws, dtype);
-            ND_TRY(nd_launch_splice(bp.buf[CAT4], f4, tp.buf[CAT4], f4, f4, t0, cnt, cols, row0, S, 0, 0, 0, 0, fp.win4[0], fp.win4[1],
-                                    fp.win4[0], fp.win4[1], s));
-            ND_TRY(nd_launch_splice(bp.buf[CAT3], 2 * f4, tp.buf[CAT3], 2 * f4, 2 * f4, t0, cnt, cols, row0, S / 2, 0, 0, 0, 0, fp.win3[0],
-                                    fp.win3[1], fp.win3[0], fp.win3[1], s));
-            const int n2 = enc_extent(cs + 4, P2);
-            ND_TRY(nd_launch_splice(bp.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, row0, S / 4, 0, 0, 0, 0, 0, n2, 0, n2, s));
-            ND_TRY(nd_launch_splice(sh.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 0, 0, 0, 0, 1, 0, n2, s));
-            ND_TRY(nd_launch_splice(sh.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 1, 1 - n2, 0, n2 - 1, n2, 0, n2, s));
-            ND_TRY(nd_launch_splice(sv.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 0, 0, 0, 0, n2, 0, 1, s));
-            ND_TRY(nd_launch_splice(sv.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 1, 0, 1 - n2, 0, n2, n2 - 1, n2, s));
-            ND_TRY(run_stack(funit, act, dtype, blob, tp, s, dec));
-            ND_TRY(nd_launch_final1x1_stitch(tp.buf[T4B], funit, fw, fw + 3 * funit, 2, canvas, width, height, cs, ucs, ol, t0, cnt, s));
+    // The two decoder steps that read a skip half (tconvs4.0: CAT4, tconvs3.0: CAT3) take it from the band where their kernel has a
+    // second input source; else the window is copied into the tile buffer as the layer expects it (k_splice)
+    struct Skip { Buf cat; int planes, step, tstep; const int *win; int *table; bool in_place; } skips[2] = {
+        {CAT4, f4, -1, S, fp.win4, origins, false}, {CAT3, 2 * f4, -1, S / 2, fp.win3, origins + fp.origin_bytes / sizeof(int), false}};
+    for (Skip &k : skips)
+        for (int i = kSharedSteps; i < kNumSteps; ++i)
+            if (kSteps[i].layer >= 0 && kSteps[i].src == k.cat) {
+                k.step = i;
+                k.in_place = form_takes_src2(kSteps[i], step_form(kSteps[i], funit, dtype, flags, pl, bl), funit, flags, pl);
+            }
+    StepSrc2 src2[2];
+    dec.src2 = src2;
+    // Bands are computed as the launches reach them, band b into slot b & 1 of the tensors the launches read; a launch takes `batch`
+    // tiles across a band seam and is cut at its second seam, so it reads two slots at most.  One stream: band b + 2 overwrites
+    // slot b & 1 only after the launches that read band b.  bf: the band plan at full height (slot 0) -- what a launch addresses,
+    // with each tile's band row and slot folded into its origin / its splice
+    const int per_band = fp.R * cols;
+    const Plan bf = make_enc_plan(funit, fp.hx, fp.wx, 1, fp.hx, fp.wx, 1, band_base, dtype, fp.slots);
+    int band_done = tile_begin / per_band - 1;
+    for (int t0 = tile_begin, n = 0; t0 < end; ++n) {
+        const int b0 = t0 / per_band;
+        int cnt = end - t0 < batch ? end - t0 : batch;
+        if (t0 + cnt > (b0 + 2) * per_band) cnt = (b0 + 2) * per_band - t0;
+        for (int b = band_done + 1; b <= (t0 + cnt - 1) / per_band; ++b) {
+            // the band: its rows of tiles on the mirrored frame, steps [0, kSharedSteps) once
+            const int row0 = b * fp.R, nrows = fp.rows - row0 < fp.R ? fp.rows - row0 : fp.R;
+            Plan bp = band_slot(make_enc_plan(funit, band_hx(fp, nrows, cs), fp.wx, 1, fp.hx, fp.wx, 1, band_base, dtype, fp.slots), b & 1, fp.slots);
+            bp.split = pl.split;
+            ND_TRY(nd_launch_gather_band(img, width, height, cs, ucs, ol, row0, bp.buf[X0], s));
+            ND_TRY(run_stack(funit, act, dtype, blob, bp, s, enc));
+            band_done = b;
         }
+        if (progress) progress(progress_ctx, n, t0, cnt);
+        // border strips: images 2t / 2t + 1 = top / bottom rows (sh), left / right columns (sv) of tile t's input
+        Plan sh = make_enc_plan(funit, kStrip, cs + 4, 2 * cnt, kStrip, cs + 4, 2 * batch, sh_base, dtype);
+        Plan sv = make_enc_plan(funit, cs + 4, kStrip, 2 * cnt, cs + 4, kStrip, 2 * batch, sv_base, dtype);
+        sh.split = sv.split = pl.split;
+        ND_TRY(nd_launch_gather_strips(img, width, height, cs, ucs, ol, t0, cnt, false, sh.buf[X0], s));
+        ND_TRY(nd_launch_gather_strips(img, width, height, cs, ucs, ol, t0, cnt, true, sv.buf[X0], s));
+        ND_TRY(run_stack(funit, act, dtype, blob, sh, s, enc));
+        ND_TRY(run_stack(funit, act, dtype, blob, sv, s, enc));
+        // per tile: the skip halves where the decoder reads them, P2 whole, then P2's border lines from the strips
+        const Plan tp = make_plan(funit, cs, cs, batch, cnt, (char *)ws, dtype);
+        dec.nsrc2 = 0;
+        for (const Skip &k : skips) {
+            const QpBuf &src = bf.buf[k.cat];
+            if (!k.in_place) {
+                ND_TRY(nd_launch_splice(src, k.planes, tp.buf[k.cat], k.planes, k.planes, t0, cnt, cols, 0, k.tstep, 0, 0, 0, 0, k.win[0],
+                                        k.win[1], k.win[0], k.win[1], s, fp.R, slot_elems(src, fp.slots)));
+                continue;
+            }
+            StepSrc2 &q = src2[dec.nsrc2++];
+            q.step = k.step;
+            q.buf = src;
+            q.plane0 = q.from = k.planes;   // the skip is the upper half of the concat in the band as in the tile
+            q.origin = k.table;
+            ND_TRY(nd_launch_skip_origins(src, tp.buf[k.cat].pad, t0, cnt, cols, fp.R, k.tstep, slot_elems(src, fp.slots), k.table,
+                                          &q.origin_max, s));
+        }
+        const int n2 = enc_extent(cs + 4, P2);
+        ND_TRY(nd_launch_splice(bf.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, S / 4, 0, 0, 0, 0, 0, n2, 0, n2, s, fp.R,
+                                slot_elems(bf.buf[P2], fp.slots)));
+        ND_TRY(nd_launch_splice(sh.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 0, 0, 0, 0, 1, 0, n2, s));
+        ND_TRY(nd_launch_splice(sh.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 1, 1 - n2, 0, n2 - 1, n2, 0, n2, s));
+        ND_TRY(nd_launch_splice(sv.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 0, 0, 0, 0, n2, 0, 1, s));
+        ND_TRY(nd_launch_splice(sv.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 1, 0, 1 - n2, 0, n2, n2 - 1, n2, s));
+        ND_TRY(run_stack(funit, act, dtype, blob, tp, s, dec));
+        ND_TRY(nd_launch_final1x1_stitch(tp.buf[T4B], funit, fw, fw + 3 * funit, 2, canvas, width, height, cs, ucs, ol, t0, cnt, s));
+        t0 += cnt;
     }
     return ND_OK;
 }

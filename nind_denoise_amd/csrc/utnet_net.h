@@ -362,11 +362,27 @@ inline bool rois_supported(int f, int dt, int flags, const Plan &pl, const BlobL
     return true;
 }
 
+// a step whose upper input planes come from a second source (ConvDesc::in2): the fused loop's skip halves, read from the band
+struct StepSrc2 {
+    int step = -1;         // index into kSteps (-1: unused)
+    QpBuf buf = {};        // the band tensor
+    int plane0 = 0, from = 0;   // first plane of buf; input plane of the step at which buf takes over
+    const int *origin = nullptr;   // per image of the launch (HBM)
+    long origin_max = 0;
+};
+// the kernel a step runs in takes a second input source: conv_w2d and the three-pass F(6x6) form
+inline bool form_takes_src2(const Step &st, Form form, int f, int flags, const Plan &pl) {
+    if (form == FORM_WINO3P) return kWinoTile == 6;
+    return form == FORM_W1D4 && nd_f43_w2d(pl.buf[st.src], lcout(kLayers[st.layer], f), false, flags);
+}
+
 // what one run_stack call does besides the whole inference stack: a call site sets only the members that differ
 struct StackOpts {
     int flags = 0;                     // nd_flags of the call (ND_FLAG_NO_SPLITK: every tile whole; ND_FLAG_DIRECT_CONV: no Winograd form)
     const Roi *rois = nullptr;         // per step: the region the layer computes (plan_rois; rows 0: the whole layer)
     int step_begin = 0, step_end = kNumSteps;   // the steps [step_begin, step_end) of kSteps
+    const StepSrc2 *src2 = nullptr;    // nsrc2 steps with a second input source
+    int nsrc2 = 0;
     hipEvent_t *ev = nullptr;          // profiling: kNumSteps+1 events, ev[i] recorded before step i, ev[kNumSteps] after the last one
     hipEvent_t *ev_x = nullptr;        // profiling, with ev: 2 events per step, recorded after the input transform and after the
                                        // GEMMs of a three-pass layer
@@ -422,6 +438,14 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
             d.roi_rows = o.rois[this_step].rows;
             d.roi_cols = o.rois[this_step].cols;
         }
+        for (int i = 0; i < o.nsrc2; ++i)
+            if (o.src2[i].step == k) {
+                d.in2 = o.src2[i].buf;
+                d.in2_plane0 = o.src2[i].plane0;
+                d.in2_from = o.src2[i].from;
+                d.in2_origin = o.src2[i].origin;
+                d.in2_origin_max = o.src2[i].origin_max;
+            }
         // MaxPool2d(2) fused into the producing layer's epilogue where its kernel can (conv_w2d, three-pass output transform):
         // the pool kernel re-read the whole skip tensor from HBM (2.4 % of the fp32 conv stack)
         const bool next_is_pool = this_step + 1 < step_end && kSteps[this_step + 1].layer < 0;
@@ -459,6 +483,7 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
                     pv.base = d.pool->base + (size_t)b0 * pv.Hb * pv.Wb * 4;
                     c.pool = &pv;
                 }
+                if (d.in2_origin) c.in2_origin = d.in2_origin + b0;   // (in2_origin_max bounds every chunk's entries)
                 // (profiling: the split of a layer's time into its passes is recorded for a single-chunk layer only)
                 ND_TRY(nd_launch_conv_wino(kWinoTile, c, pl.wino, pl.wino_bytes, s, (o.ev_x && nimg <= kWinoChunk) ? o.ev_x + 2 * this_step : nullptr));
             }
@@ -478,10 +503,12 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
 // fp32 useful-region mode shares levels 0 and 1 (convs1.0 ... the second pool: the conv_w2d layers, 64 % of the encoder's time at
 // G24) when S % 4 == 0:
 //   * the band runs steps [0, kSharedSteps) once on its window of the mirrored frame;
-//   * the decoder reads neither the contaminated lines of CAT4 nor those of CAT3 (region plan) -- the tile's skip halves are copied
-//     from the band, only over the window the decoder reads;
+//   * the decoder reads neither the contaminated lines of CAT4 nor those of CAT3 (region plan) -- it reads the tile's skip halves
+//     where the band wrote them (ConvDesc::in2; a step whose kernel has no second input source gets a copy of the window);
 //   * P2 (the level-2 input, computed whole per tile) is copied from the band, and its contaminated rows / cols 0 and n-1 are
 //     recomputed exactly from kStrip-pixel strips of the tile's own input (a 16-row strip yields one P2 row through the 6 steps).
+//   * launches take `batch` tiles across band seams: the band tensors they read (CAT4, CAT3, P2) live in two slots, band b in
+//     slot b & 1, and a launch is cut at its second seam.
 // The deeper levels stay per tile: their exact border lines would need strips of 36 / 76 input rows.
 constexpr int kSharedSteps = 6;
 constexpr int kStrip = 16;
@@ -501,8 +528,10 @@ inline int enc_extent(int x, int b) {
     }
 }
 // X0 ... P2 for B images of hx x wx first-layer input; planes sized for cap images of hcap x wcap (the plane stride does not move
-// when a band or a batch is smaller: plane 1 of X0 and the slack stay zero from the one fill of the workspace)
-Plan make_enc_plan(int f, int hx, int wx, int B, int hcap, int wcap, int cap, char *base, int dt) {
+// when a band or a batch is smaller: plane 1 of X0 and the slack stay zero from the one fill of the workspace).  slots > 1 (bands):
+// the tensors the per-tile launches read -- CAT4, CAT3, P2 -- hold `slots` times the capacity, so that band b + 1 can be computed
+// (into slot (b + 1) & 1: band_slot) while launches still read band b
+Plan make_enc_plan(int f, int hx, int wx, int B, int hcap, int wcap, int cap, char *base, int dt, int slots = 1) {
     Plan p = {};
     size_t off = 0;
     auto add = [&](Buf id, int ch, int pad) {
@@ -514,6 +543,7 @@ Plan make_enc_plan(int f, int hx, int wx, int B, int hcap, int wcap, int cap, ch
         q.Wb = enc_extent(wx, id) + 2 * pad;
         q.pad = pad;
         q.pstride = (long)cap * (enc_extent(hcap, id) + 2 * pad) * (enc_extent(wcap, id) + 2 * pad);
+        if (id == CAT4 || id == CAT3 || id == P2) q.pstride *= slots;
         q.base = (float *)(base + off);
         off += ((size_t)q.planes * q.pstride + nd_buf_slack(enc_extent(wcap, id) + 2 * pad)) * 16;
         off = (off + 255) & ~(size_t)255;
@@ -531,14 +561,22 @@ Plan make_enc_plan(int f, int hx, int wx, int B, int hcap, int wcap, int cap, ch
     return p;
 }
 
+// 16-byte elements between the slots of a two-slot band tensor, and the view of a band plan whose CAT4 / CAT3 / P2 are slot `slot`
+inline long slot_elems(const QpBuf &q, int slots) { return q.pstride / slots; }
+inline Plan band_slot(Plan p, int slot, int slots) {
+    for (Buf id : {CAT4, CAT3, P2}) p.buf[id].base += (size_t)slot * slot_elems(p.buf[id], slots) * 4;
+    return p;
+}
+
 struct FramePlan {
     int D = 0;         // shared encoder levels (2, or 0: every tile runs its whole encoder)
     int aligned = 0;   // levels on which every tile origin is a whole pixel: 1 + the power of 2 in S, at most 4
     int S = 0, cols = 0, rows = 0, pad = 0;
     int R = 0, nbands = 0;   // tile rows per band, bands
+    int slots = 1;           // slots of the band tensors the per-tile launches read (2 when there is more than one band)
     int hx = 0, wx = 0;      // first-layer input of a full band
     int win4[2] = {0, 0}, win3[2] = {0, 0};   // [lo, hi) of the CAT4 / CAT3 skip pixels the decoder reads (both axes)
-    size_t band_bytes = 0, strip_bytes = 0, bytes = 0;
+    size_t band_bytes = 0, strip_bytes = 0, origin_bytes = 0, bytes = 0;   // frame workspace: band | strips (h) | strips (v) | origins
 };
 inline int band_hx(const FramePlan &fp, int nrows, int cs) { return (nrows - 1) * fp.S + cs + 4; }
 
@@ -590,7 +628,9 @@ int frame_plan(int f, int dt, int flags, int W, int H, int cs, int ucs, int ol, 
     fp->nbands = (fp->rows + fp->R - 1) / fp->R;
     fp->R = (fp->rows + fp->nbands - 1) / fp->nbands;
     fp->hx = band_hx(*fp, fp->R, cs);
-    fp->band_bytes = make_enc_plan(f, fp->hx, fp->wx, 1, fp->hx, fp->wx, 1, nullptr, dt).bytes;
+    // (the rows per band are fixed by one slot of every tensor: the second slot is memory on top of kBandBytes)
+    fp->slots = fp->nbands > 1 ? 2 : 1;
+    fp->band_bytes = make_enc_plan(f, fp->hx, fp->wx, 1, fp->hx, fp->wx, 1, nullptr, dt, fp->slots).bytes;
     if ((long)fp->hx * fp->wx >= (1L << 26)) return ND_OK;   // (32-bit offsets of the conv kernels on a band image)
     // every shared step of the band and of both strip shapes must run in conv_w2d (its pool epilogue included)
     const Plan plans[3] = {make_enc_plan(f, fp->hx, fp->wx, 1, fp->hx, fp->wx, 1, nullptr, dt),
@@ -604,7 +644,9 @@ int frame_plan(int f, int dt, int flags, int W, int H, int cs, int ucs, int ol, 
                 return ND_OK;
         }
     fp->strip_bytes = make_enc_plan(f, kStrip, cs + 4, 2 * batch, kStrip, cs + 4, 2 * batch, nullptr, dt).bytes;
-    fp->bytes = fp->band_bytes + 2 * fp->strip_bytes;
+    // where each tile of a launch lies in the band's CAT4 / CAT3 planes (the decoder reads the skip halves in place): two tables
+    fp->origin_bytes = ((size_t)batch * sizeof(int) + 255) & ~(size_t)255;
+    fp->bytes = fp->band_bytes + 2 * fp->strip_bytes + 2 * fp->origin_bytes;
     fp->D = 2;
     return ND_OK;
 }

@@ -249,8 +249,10 @@ __global__ __launch_bounds__(128) void k_wino_output(const f32x4 *__restrict__ m
 //           pass 2 thread (row i, tile)     row transform of r[i][0..A), A position stores, each 512 B contiguous per half wave
 template <int T, int NTL>
 __global__ __launch_bounds__(NTL * (T + 2)) void k_wino_in2(const f32x4 *__restrict__ x, long xnp, int Hb, int Wb, long img_stride, int row_stride, int B,
-                                                            int TY, int TX, f32x4 *__restrict__ v, long vnp, long vbs) {
-    // Hb x Wb: extent of the (view of the) bordered input a tile may read; img_stride / row_stride: of the buffer it lives in
+                                                            int TY, int TX, f32x4 *__restrict__ v, long vnp, long vbs, const f32x4 *__restrict__ x2,
+                                                            long x2np, int row_stride2, const int *__restrict__ origin2, int q2) {
+    // Hb x Wb: extent of the (view of the) bordered input a tile may read; img_stride / row_stride: of the buffer it lives in.
+    // Planes q >= q2 come from the second source (ConvDesc::in2): plane q - q2 of x2, image b at origin2[b], rows row_stride2 apart
     constexpr int A = Wino<T>::A, RS = A * A + 1;   // (+1: pass 2 reads a tile per lane, 16 (A*A+1) B apart: all banks)
     __shared__ f32x4 sm[NTL * RS];
     const long tiles = (long)B * TY * TX;
@@ -263,11 +265,13 @@ __global__ __launch_bounds__(NTL * (T + 2)) void k_wino_in2(const f32x4 *__restr
         if (t < tiles) {
             int tx, ty, b;
     tile_pos(t, TX, TY, tx, ty, b);
-            const f32x4 *src = x + (long)q * xnp + (long)b * img_stride + (long)(T * ty) * row_stride + T * tx + j;
+            const bool s2 = q >= q2;   // block-uniform
+            const long rs = s2 ? row_stride2 : row_stride;
+            const f32x4 *src = (s2 ? x2 + (long)(q - q2) * x2np + origin2[b] : x + (long)q * xnp + (long)b * img_stride) + (long)(T * ty) * rs + T * tx + j;
             f32x4 d[A], o[A];
             const bool okj = T * tx + j < Wb;
 #pragma unroll
-            for (int i = 0; i < A; ++i) d[i] = (okj && T * ty + i < Hb) ? src[(long)i * row_stride] : zero;
+            for (int i = 0; i < A; ++i) d[i] = (okj && T * ty + i < Hb) ? src[(long)i * rs] : zero;
             Wino<T>::bt(d, o);
 #pragma unroll
             for (int i = 0; i < A; ++i) sm[tl * RS + i * A + j] = o[i];
@@ -478,6 +482,12 @@ int nd_launch_conv_wino(int T, const ConvDesc &d, void *scratch, size_t scratch_
     ND_TRY(nd_check_roi("winograd", d, d.in.Hb - 2, d.in.Wb - 2, T != 6 || d.pool, "a layer other than an unpooled F(6x6) one"));
     const bool roi = d.roi_rows > 0;
     const WinoGeo g = wino_geo(T, d.in, d.cin, d.cout, d.roi_rows, d.roi_cols);
+    const bool src2 = d.in2.base != nullptr;
+    if (src2) {
+        if (T != 6) ND_FAIL(ND_EINVAL, "winograd: only the F(6x6) form has a second input source");
+        // (k_wino_in2 reads nothing outside the view of g.Hv + 2 rows x g.Wv + 2 pixels at the region's first pixel)
+        ND_TRY(nd_check_in2("winograd", d, nd_kblocks(d.cin), (long)(d.roi_r0 + g.Hv + 1) * d.in2.Wb + d.roi_c0 + g.Wv + 2));
+    }
     ND_TRY(nd_check_out("winograd", d, d.in.Hb - 2, d.in.Wb - 2, false));
     // a region is the same three passes on shifted base pointers (input view: rows [r0, r0 + rows + 2) of the bordered buffer)
     const long roi_in = roi ? (long)d.roi_r0 * d.in.Wb + d.roi_c0 : 0, roi_out = roi ? (long)d.roi_r0 * d.out.Wb + d.roi_c0 : 0;
@@ -498,7 +508,9 @@ int nd_launch_conv_wino(int T, const ConvDesc &d, void *scratch, size_t scratch_
     if (T == 2)
         hipLaunchKernelGGL(k_wino_input<2>, gi, dim3(256), 0, s, x, d.in.np(), d.in.Hb, d.in.Wb, d.in.B, g.TY, g.TX, v, g.vnp, g.vbs);
     else if (T == 6)
-        hipLaunchKernelGGL((k_wino_in2<6, kNtl>), gi2, dim3(kNtl * 8), 0, s, x, d.in.np(), vHb, vWb, (long)d.in.Hb * d.in.Wb, d.in.Wb, d.in.B, g.TY, g.TX, v, g.vnp, g.vbs);
+        hipLaunchKernelGGL((k_wino_in2<6, kNtl>), gi2, dim3(kNtl * 8), 0, s, x, d.in.np(), vHb, vWb, (long)d.in.Hb * d.in.Wb, d.in.Wb, d.in.B, g.TY, g.TX, v, g.vnp, g.vbs,
+                           src2 ? (const f32x4 *)d.in2.base + (long)d.in2_plane0 * d.in2.np() + (roi ? (long)d.roi_r0 * d.in2.Wb + d.roi_c0 : 0) : nullptr,
+                           d.in2.np(), d.in2.Wb, d.in2_origin, src2 ? d.in2_from : in_planes);
     else
         hipLaunchKernelGGL(k_wino_input<4>, gi, dim3(256), 0, s, x, d.in.np(), d.in.Hb, d.in.Wb, d.in.B, g.TY, g.TX, v, g.vnp, g.vbs);
     ND_HIP(hipGetLastError());
