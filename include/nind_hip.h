@@ -73,7 +73,7 @@ typedef enum nd_flags {
                                  the network output before the canvas +=) -- same canvas, 19 % less work at cs 264 / ucs 200    */
 } nd_flags;
 
-int nd_version(void);   /* 106 = this header */
+int nd_version(void);   /* 107 = this header */
 const char *nd_last_error(void);
 
 /* ---------------------------------------------------------------- tile geometry (host, pure integer)
@@ -109,8 +109,9 @@ size_t nd_utnet_packed_bytes(int funit, int dtype);
 int nd_utnet_pack_weights(int funit, int dtype, const float *const *tensors, int n_tensors,
                           void *packed_host, size_t packed_bytes);
 
-/* The same blob built in HBM from tensors that already live there (fp32 storage only): device-side packers; the Winograd
- * weight transforms are evaluated in fp32 instead of double (packed values agree to ~1e-7 relative).  Stream-ordered. */
+/* The same blob built in HBM from tensors that already live there, for every storage type: device-side packers.  The bf16 / fp16
+ * blob (direct-form layers only) is bit for bit the host function's; in the fp32 blob the Winograd weight transforms are
+ * evaluated in fp32 instead of double (packed values agree to ~1e-7 relative).  Stream-ordered. */
 int nd_utnet_pack_weights_device(int funit, int dtype, const float *const *dev_tensors, int n_tensors, void *packed_dev,
                                  size_t packed_bytes, void *stream);
 

@@ -186,8 +186,8 @@ static inline size_t nd_packed_floats(int kind, int cin, int cout, int dt = ND_F
 }
 void nd_pack_layer(int kind, int cin, int cout, int dt, const float *w, const float *bias, float *packed);
 
-// device-side packers (pack_dev.hip): the same layouts from weights in HBM (fp32)
-int nd_pack_layer_device(int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s);
+// device-side packers (pack_dev.hip): the same layouts from weights in HBM (direct form: any storage type; Winograd forms: fp32)
+int nd_pack_layer_device(int kind, int cin, int cout, int dt, const float *w, const float *bias, float *packed, hipStream_t s);
 int nd_pack_w1d_device(int T, int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s);
 int nd_pack_wino_device(int T, int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s);
 

@@ -1,40 +1,73 @@
-// Device-side weight packing (fp32): the host packers of pack.hip / conv_w1d.hip / winograd.hip as kernels, for weights that
+// Device-side weight packing: the host packers of pack.hip / conv_w1d.hip / winograd.hip as kernels, for weights that
 // live in HBM -- the training step re-packs every step (the weights change every step), and a model load packs here instead of
-// on host threads (the Winograd transforms of UtNet(64) take ~1 s there).  Same layouts, same maps; the Winograd transforms are
+// on host threads (the Winograd transforms of UtNet(64) take ~1 s there).  Same layouts, same maps.  The direct form packs every
+// storage type, bit for bit what the host packer writes; the Winograd forms are fp32 only and their transforms are
 // evaluated in fp32 here (the host packers use double): the packed values agree to ~1e-7 relative.
 #include "nd_common.h"
 
 namespace {
 
-// direct form (pack.hip: nd_pack_layer): nw packed weights followed by nb biases
+// the host's roundings (pack.hip: f32_to_bf16_rne / f32_to_f16_rne), bit for bit
+__device__ __forceinline__ unsigned f32_to_bf16_rne(float f) {
+    const unsigned u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return ((u >> 16) | 0x40) & 0xffffu;   // NaN stays NaN
+    return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
+}
+__device__ __forceinline__ unsigned f32_to_f16_rne(float f) {
+    union {
+        _Float16 h;
+        unsigned short u;
+    } c;
+    c.h = (_Float16)f;   // v_cvt_f16_f32: nearest even, subnormals kept, overflow to +-inf
+    return c.u;
+}
+
+// direct form (pack.hip: nd_pack_layer): nw 4-byte units of packed weights followed by nb biases.  fp32: one thread per value;
+// 16-bit: one thread per 16-byte lane element (its 8 channels, one vector store)
+template <int DT>
 __global__ void k_pack_dev(int kind, int cin, int cout, int M, int KB, int taps, const float *__restrict__ w,
                            const float *__restrict__ bias, float *__restrict__ packed, long nw, int nb) {
+    constexpr int CPL = DT == ND_F32 ? 4 : 8;   // channels per lane of a piece
+    constexpr int PER = DT == ND_F32 ? 1 : 8;   // ... and per thread
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx < nw) {
-        const int s = (int)(idx & 3), lane = (int)((idx >> 2) & 63);
-        long rest = idx >> 8;
+    const long nu = DT == ND_F32 ? nw : nw / 4;   // threads that pack weights
+    if (idx < nu) {
+        const int s0 = DT == ND_F32 ? (int)(idx & 3) : 0, lane = (int)((DT == ND_F32 ? idx >> 2 : idx) & 63);
+        long rest = DT == ND_F32 ? idx >> 8 : idx >> 6;
         const int t = (int)(rest % taps);
         rest /= taps;
         const int kb = (int)(rest % KB), mt = (int)(rest / KB);
-        const int m = 32 * mt + (lane & 31), ci = 8 * kb + 4 * (lane >> 5) + s;
-        float v = 0.f;
-        if (m < M && ci < cin) {
-            switch (kind) {
-                case ND_CONV3: v = w[((long)m * cin + ci) * 9 + t]; break;
-                case ND_CONVT3: v = w[((long)ci * cout + m) * 9 + (8 - t)]; break;
-                case ND_CONVT2S2: {
-                    const NdUpRow r = nd_up_row(m, cout, ND_F32);
-                    v = w[((long)ci * cout + r.co) * 4 + 2 * r.a + r.b];
-                    break;
+        const int m = 32 * mt + (lane & 31), ci0 = 2 * CPL * kb + CPL * (lane >> 5) + s0;
+        float v[PER];
+#pragma unroll
+        for (int s = 0; s < PER; ++s) {
+            const int ci = ci0 + s;
+            v[s] = 0.f;
+            if (m < M && ci < cin) {
+                switch (kind) {
+                    case ND_CONV3: v[s] = w[((long)m * cin + ci) * 9 + t]; break;
+                    case ND_CONVT3: v[s] = w[((long)ci * cout + m) * 9 + (8 - t)]; break;
+                    case ND_CONVT2S2: {
+                        const NdUpRow r = nd_up_row(m, cout, DT);
+                        v[s] = w[((long)ci * cout + r.co) * 4 + 2 * r.a + r.b];
+                        break;
+                    }
+                    case ND_CONV2S2: v[s] = w[((long)m * cin + ci) * 4 + t]; break;
+                    default: v[s] = w[(long)m * cin + ci]; break;
                 }
-                case ND_CONV2S2: v = w[((long)m * cin + ci) * 4 + t]; break;
-                default: v = w[(long)m * cin + ci]; break;
             }
         }
-        packed[idx] = v;
-    } else if (idx < nw + nb) {
-        const int m = (int)(idx - nw);
-        packed[idx] = (m < M && bias) ? bias[kind == ND_CONVT2S2 ? nd_up_row(m, cout, ND_F32).co : m] : 0.f;
+        if constexpr (DT == ND_F32) {
+            packed[idx] = v[0];
+        } else {
+            unsigned h[PER];
+#pragma unroll
+            for (int s = 0; s < PER; ++s) h[s] = DT == ND_BF16 ? f32_to_bf16_rne(v[s]) : f32_to_f16_rne(v[s]);
+            reinterpret_cast<uint4 *>(packed)[idx] = make_uint4(h[0] | h[1] << 16, h[2] | h[3] << 16, h[4] | h[5] << 16, h[6] | h[7] << 16);
+        }
+    } else if (idx < nu + nb) {
+        const int m = (int)(idx - nu);
+        packed[nw + m] = (m < M && bias) ? bias[kind == ND_CONVT2S2 ? nd_up_row(m, cout, DT).co : m] : 0.f;
     }
 }
 
@@ -135,12 +168,16 @@ __global__ void k_pack_wino_dev(int T, int kind, int cin, int cout, int KB, cons
 
 }  // namespace
 
-int nd_pack_layer_device(int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s) {
-    const int MT = nd_mtiles(kind, cout), KB = nd_kblocks(cin), taps = nd_taps(kind);
+int nd_pack_layer_device(int kind, int cin, int cout, int dt, const float *w, const float *bias, float *packed, hipStream_t s) {
+    const int MT = nd_mtiles(kind, cout), KB = nd_kblocks(cin, dt), taps = nd_taps(kind);
     const int M = kind == ND_CONVT2S2 ? 4 * cout : cout;
-    const long nw = (long)nd_bias_offset(kind, cin, cout);
-    hipLaunchKernelGGL(k_pack_dev, dim3((unsigned)((nw + MT * 32 + 255) / 256)), dim3(256), 0, s, kind, cin, cout, M, KB, taps, w, bias,
-                       packed, nw, MT * 32);
+    const long nw = (long)nd_bias_offset(kind, cin, cout, dt);
+    const long threads = (dt == ND_F32 ? nw : nw / 4) + MT * 32;
+    if (dt != ND_F32 && ((uintptr_t)packed & 15)) ND_FAIL(ND_EINVAL, "device packing: a 16-bit layer must be 16-byte aligned");
+    if (kind == ND_CONVT2S2 && cout % nd_cpp(dt)) ND_FAIL(ND_EINVAL, "device packing: 2x2 stride-2 transpose with cout=%d (multiple of %d)", cout, nd_cpp(dt));
+    const auto k = dt == ND_F32 ? k_pack_dev<ND_F32> : dt == ND_BF16 ? k_pack_dev<ND_BF16> : k_pack_dev<ND_F16>;
+    hipLaunchKernelGGL(k, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, kind, cin, cout, M, KB, taps, w, bias, packed, nw,
+                       MT * 32);
     ND_HIP(hipGetLastError());
     return ND_OK;
 }

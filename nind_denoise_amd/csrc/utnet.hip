@@ -57,11 +57,11 @@ extern "C" int nd_utnet_pack_weights(int funit, int dtype, const float *const *t
     return ND_OK;
 }
 
-// Same blob from tensors that already live in HBM (fp32 storage only): device-side packers, nothing touches the host.
+// Same blob from tensors that already live in HBM, any storage type: device-side packers, nothing touches the host.  The 16-bit
+// blob has direct-form layers only (blob_layout) and is bit for bit the host function's.
 extern "C" int nd_utnet_pack_weights_device(int funit, int dtype, const float *const *tensors, int n_tensors, void *packed_dev,
                                             size_t packed_bytes, void *stream) {
     ND_TRY(check_funit(funit, dtype));
-    if (dtype != ND_F32) ND_FAIL(ND_EINVAL, "nd_utnet_pack_weights_device: fp32 storage only (16-bit blobs are packed on the host)");
     if (n_tensors != nd_utnet_num_tensors()) ND_FAIL(ND_EINVAL, "nd_utnet_pack_weights_device: expected %d tensors, got %d", nd_utnet_num_tensors(), n_tensors);
     const BlobLayout bl = blob_layout(funit, dtype);
     if (!packed_dev || packed_bytes < bl.total * sizeof(float)) ND_FAIL(ND_ENOMEM, "nd_utnet_pack_weights_device: packed buffer too small");
@@ -77,7 +77,7 @@ extern "C" int nd_utnet_pack_weights_device(int funit, int dtype, const float *c
             ND_HIP(hipMemcpyAsync(blob + bl.off[i], tensors[wi], sizeof(float) * 3 * ci, hipMemcpyDeviceToDevice, s));
             ND_HIP(hipMemcpyAsync(blob + bl.off[i] + 3 * ci, tensors[bi], sizeof(float) * 3, hipMemcpyDeviceToDevice, s));
         } else {
-            ND_TRY(nd_pack_layer_device(l.kind, ci, co, tensors[wi], tensors[bi], blob + bl.off[i], s));
+            ND_TRY(nd_pack_layer_device(l.kind, ci, co, dtype, tensors[wi], tensors[bi], blob + bl.off[i], s));
             if (bl.woff[i]) ND_TRY(nd_pack_wino_device(kWinoTile, l.kind, ci, co, tensors[wi], tensors[bi], blob + bl.woff[i], s));
             if (bl.w1off[i]) ND_TRY(nd_pack_w1d_device(kW1dTile, l.kind, ci, co, tensors[wi], tensors[bi], blob + bl.w1off[i], s));
             if (bl.w1off2[i]) ND_TRY(nd_pack_w1d_device(2, l.kind, ci, co, tensors[wi], tensors[bi], blob + bl.w1off2[i], s));

@@ -628,13 +628,13 @@ static int train_forward(TrainCtx &c, const float *params, const float *x, float
         if (c.fwd_w1[i])
             nd_pack_w1d_device(kW1dTile, l.kind, ci, co, w, b, fblob + bl.off[i], s);
         else
-            nd_pack_layer_device(l.kind, ci, co, w, b, fblob + bl.off[i], s);
+            nd_pack_layer_device(l.kind, ci, co, ND_F32, w, b, fblob + bl.off[i], s);
         if (i > 0) {   // transposed role: cin' = co, cout' = ci, no bias
             const int kt = transposed_kind(l.kind);
             if (c.bwd_w1[i])
                 nd_pack_w1d_device(kW1dTile, kt, co, ci, w, nullptr, bblob + bb.off[i], s);
             else
-                nd_pack_layer_device(kt, co, ci, w, nullptr, bblob + bb.off[i], s);
+                nd_pack_layer_device(kt, co, ci, ND_F32, w, nullptr, bblob + bb.off[i], s);
         }
     }
     ND_HIP(hipGetLastError());

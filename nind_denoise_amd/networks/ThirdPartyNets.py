@@ -10,6 +10,7 @@ import torch
 from torch import nn
 
 from .. import _lib
+from .UtNet import canonical_compute_dtype
 
 
 class _Box(nn.Module):
@@ -27,8 +28,11 @@ def _double_conv(in_ch, out_ch):
 
 
 class UNet(nn.Module):
-    def __init__(self, n_channels=3, n_classes=3, funit=64, find_noise=False):
+    def __init__(self, n_channels=3, n_classes=3, funit=64, find_noise=False, compute_dtype='f32'):
         super().__init__()
+        if canonical_compute_dtype(compute_dtype) != 'f32':
+            raise NotImplementedError(f"UNet: compute_dtype={compute_dtype!r}: 16-bit storage exists for UtNet only "
+                                      "(the UNet executor is fp32)")
         if int(n_channels) != 3 or int(n_classes) != 3:
             raise NotImplementedError("the HIP UNet path is built for RGB in / RGB out (the reference's defaults)")
         self.inc = _Box(conv=_double_conv(3, 64))

@@ -16,6 +16,14 @@ from .. import _lib
 from ..synth import utnet_layer_table, utnet_prelu_keys
 
 _ACTIVATIONS = {"PReLU": nn.PReLU, "ELU": nn.ELU, "Hardswish": nn.Hardswish}
+_SHORT_DTYPE = {_lib.ND_F32: "f32", _lib.ND_BF16: "bf16", _lib.ND_F16: "f16"}
+
+
+def canonical_compute_dtype(name):
+    """Short form ("f32" | "bf16" | "f16") of any spelling _lib.DTYPE knows; ValueError with the choices otherwise."""
+    if name not in _lib.DTYPE:
+        raise ValueError(f"unknown compute dtype {name!r}; choose one of {', '.join(_lib.DTYPE)}")
+    return _SHORT_DTYPE[_lib.DTYPE[name]]
 
 
 def valid_cs(cs):
@@ -131,9 +139,10 @@ class UtNet(nn.Module):
     fused_pool = True
     share_encoder = True
 
-    def __init__(self, funit=64, activation='PReLU'):
+    def __init__(self, funit=64, activation='PReLU', compute_dtype='f32'):
         super().__init__()
         funit = int(funit)
+        compute_dtype = canonical_compute_dtype(compute_dtype)
         if activation not in _ACTIVATIONS:
             exit(f'UtNet: unknown activation function: {activation}')
         self.funit, self.activation = funit, activation
@@ -161,18 +170,17 @@ class UtNet(nn.Module):
             g = groups[name]
             self.add_module(name, nn.Sequential(*[g[i] for i in sorted(g)]) if isinstance(g, dict) else g)
         self._packed = {}         # dtype -> (key, device blob)
-        self.pack_on_device = True   # fp32: build the packed blob in HBM (nd_utnet_pack_weights_device); False: host packer
+        self.pack_on_device = True   # build the packed blob in HBM (nd_utnet_pack_weights_device); False: host packer
         self._workspaces = {}     # (device, h, w, batch, dtype) -> uint8 tensor
         self.max_cached_workspaces = 2
-        self.compute_dtype = "f32"   # storage of activations + weights inside the conv stack: "f32" | "bf16" | "f16"
+        self.compute_dtype = compute_dtype   # storage of activations + weights inside the conv stack: "f32" | "bf16" | "f16"
         self.weights_generation = 0   # bumped by whoever rewrites the parameters through raw pointers (train.UtNetTrainer)
 
     def set_compute_dtype(self, name):
         """"f32": fp32 storage, exact-fp32 MFMA (the reference's arithmetic).  "bf16" / "f16": 16-bit storage of
-        activations and weights with fp32 accumulation (BASELINE configs 3 / 4); inputs and outputs stay float32."""
-        if name not in ("f32", "bf16", "f16"):
-            raise ValueError(f"unknown compute dtype {name!r}")
-        self.compute_dtype = name
+        activations and weights with fp32 accumulation (BASELINE configs 3 / 4); inputs and outputs stay float32.
+        Same spellings as the constructor's compute_dtype (the model parameter `--model_parameters compute_dtype=...` sets)."""
+        self.compute_dtype = canonical_compute_dtype(name)
         return self
 
     @property
@@ -202,8 +210,8 @@ class UtNet(nn.Module):
         if nbytes == 0:
             raise ValueError(f"UtNet: funit={self.funit} is not supported by the HIP path for {self.compute_dtype} "
                              "(multiple of 8 for f32, of 16 for bf16 / f16)")
-        on_device = self.compute_dtype == "f32" and self.pack_on_device
-        where = device if on_device else "cpu"     # fp32: pack in HBM (device-side packers); 16-bit: on the host
+        on_device = self.pack_on_device
+        where = device if on_device else "cpu"     # pack in HBM (device-side packers), or on the host (the yardstick)
         keep = []
         ptrs = (ctypes.c_void_p * len(names))()
         for i, n in enumerate(names):
