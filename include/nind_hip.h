@@ -140,13 +140,15 @@ int nd_utnet_denoise_tiles(int funit, int act, int dtype, int flags, const void 
  * by 4 (nd_utnet_frame_plan: D = 2): the first two encoder levels (convs1.0 ... the second pool) run once per band of tile rows
  * on the band's window of the mirrored frame (valid 3x3 convolutions and 2x2 pools are translation-equivariant); the decoder
  * reads each tile's skip tensors where the band holds them, the pooled level-2 input is copied from the band, and the border lines
- * a tile's own ReflectionPad2d(2) reaches are recomputed from 16-pixel strips of its input.  Launches hold exactly `batch` tiles
+ * a tile's own ReflectionPad2d(2) reaches come from 16-pixel edge images computed with the band -- one pair per tile row and one
+ * per tile column, which all tiles of that row / column share -- and four corner patches per tile.  Launches hold exactly `batch` tiles
  * (the last one fewer) and may cross one band seam; a launch that would reach a third band is cut at its second seam.  Same
  * canvas as the per-tile encoder up to fp32 re-association (<= 1e-5); bits do not depend on `batch` or the tile range with
  * ND_FLAG_NO_SPLITK.  Every other case runs nd_utnet_denoise_tiles.
  * frame_ws: nd_utnet_frame_workspace_bytes, zero-filled once (null / 0 when that is 0): the band tensors (those the launches
  * read in two slots when the frame has more than one band, so that the next band can be computed while launches still read the
- * last one), the strip tensors of 2 x batch strips, and two tables of `batch` tile origins.  No state is carried from one call to
+ * last one), the row and column edge tensors of one band (their pooled lines in the same two slots), the corner tensors of
+ * 4 x batch patches, and two tables of `batch` tile origins.  No state is carried from one call to
  * the next.  progress (optional) is called with (progress_ctx, launch index, first tile, tile count) before each launch is
  * enqueued. */
 typedef void (*nd_progress_fn)(void *ctx, int n, int tile_begin, int tile_count);

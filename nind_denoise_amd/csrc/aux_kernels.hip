@@ -152,17 +152,25 @@ int nd_launch_gather_pack(const float *img, int W, int H, int cs, int ucs, int o
     return ND_OK;
 }
 
-// ------------------------------------------------------------------ shared encoder (fp32): band gather, strip gather, splice
+// ------------------------------------------------------------------ shared encoder (fp32): band gather, edge gather, splice
 // Every gathered tile is the window of the symmetric-padded frame at its origin, so a band of tile rows is gathered as one image:
 // band pixel (v, u) = frame pixel (by0 + v, bx0 + u) under the same mirror.  The outer ring that no tile reaches unpadded (the
-// 2-pixel reflect border of the first and last tiles) only feeds lines the strips recompute: it is clamped into the frame.
+// 2-pixel reflect border of the first and last tiles) only feeds lines the edge images recompute: it is clamped into the frame.
+__device__ __forceinline__ int band_axis(int b0, int line, int n) {
+    const int v = mirror_sym(b0 + line, n);
+    return v < 0 ? 0 : (v >= n ? n - 1 : v);
+}
+// line `line` of the `len` first (side 0) or last (side 1) lines of tile index ti's reflect-padded input along one axis: gather +
+// ReflectionPad2d(2), as k_gather_pack
+__device__ __forceinline__ int tile_axis(const TileGeo &g, int ti, int line, int side, int len, int n) {
+    return mirror_sym(ti * g.stride - g.pad + reflect_nr(line + (side ? g.cs + 4 - len : 0) - 2, g.cs), n);
+}
+
 __global__ void k_gather_band(const float *__restrict__ img, TileGeo g, int by0, int bx0, f32x4 *__restrict__ dst, int Hb, int Wb) {
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
     const int v = blockIdx.y;
     if (u >= Wb) return;
-    int sx = mirror_sym(bx0 + u, g.W), sy = mirror_sym(by0 + v, g.H);
-    sx = sx < 0 ? 0 : (sx >= g.W ? g.W - 1 : sx);
-    sy = sy < 0 ? 0 : (sy >= g.H ? g.H - 1 : sy);
+    const int sx = band_axis(bx0, u, g.W), sy = band_axis(by0, v, g.H);
     const size_t plane = (size_t)g.W * g.H;
     const float *s = img + (size_t)sy * g.W + sx;
     f32x4 o = {s[0], s[plane], s[2 * plane], 0.f};
@@ -181,52 +189,67 @@ int nd_launch_gather_band(const float *img, int W, int H, int cs, int ucs, int o
     return ND_OK;
 }
 
-// The first-layer input (gather + ReflectionPad2d(2), as k_gather_pack) of two border strips per tile: image 2t = rows (vertical:
-// columns) [0, n) of tile t's (cs+4)^2 input, image 2t+1 = rows (columns) [cs+4-n, cs+4).
-__global__ void k_gather_strips(const float *__restrict__ img, TileGeo g, int tile_begin, int vertical, f32x4 *__restrict__ dst,
-                                int Hs, int Ws) {
+// The first-layer input of the images that yield P2's border lines (nd_edge_set).  Along an axis an image either follows a tile's
+// own input (tile_axis: its reflections included) or the band image (band_axis), so that its interior is a window of both:
+//   ND_EDGE_ROWS     image 2 * yrel + side: the top / bottom Hs rows of tile row `first` + yrel, over the band's width
+//   ND_EDGE_COLS     image 2 * xi + side: the left / right Ws columns of tile column xi, over the height of the band whose
+//                    first tile row is `first`
+//   ND_EDGE_CORNERS  image 4 * t + 2 * bottom + right: that Hs x Ws corner of tile `first` + t, reflected along both axes
+__global__ void k_gather_edges(const float *__restrict__ img, TileGeo g, int set, int first, f32x4 *__restrict__ dst, int Hs, int Ws) {
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
     const int v = blockIdx.y;
     const int b = blockIdx.z;
     if (u >= Ws) return;
-    const int i = tile_begin + (b >> 1), side = b & 1;
-    const int yi = i / g.cols, xi = i - yi * g.cols;
-    const int n = vertical ? Ws : Hs;
-    const int row = v + (!vertical && side ? g.cs + 4 - n : 0), col = u + (vertical && side ? g.cs + 4 - n : 0);
-    const int qx = reflect_nr(col - 2, g.cs), qy = reflect_nr(row - 2, g.cs);
-    const int sx = mirror_sym(xi * g.stride - g.pad + qx, g.W);
-    const int sy = mirror_sym(yi * g.stride - g.pad + qy, g.H);
+    int sx, sy;
+    if (set == ND_EDGE_ROWS) {
+        sy = tile_axis(g, first + (b >> 1), v, b & 1, Hs, g.H);
+        sx = band_axis(-g.pad - 2, u, g.W);
+    } else if (set == ND_EDGE_COLS) {
+        sy = band_axis(first * g.stride - g.pad - 2, v, g.H);
+        sx = tile_axis(g, b >> 1, u, b & 1, Ws, g.W);
+    } else {
+        const int i = first + (b >> 2), yi = i / g.cols, xi = i - yi * g.cols;
+        sy = tile_axis(g, yi, v, (b >> 1) & 1, Hs, g.H);
+        sx = tile_axis(g, xi, u, b & 1, Ws, g.W);
+    }
     const size_t plane = (size_t)g.W * g.H;
     const float *s = img + (size_t)sy * g.W + sx;
     f32x4 o = {s[0], s[plane], s[2 * plane], 0.f};
     dst[((size_t)b * Hs + v) * Ws + u] = o;
 }
 
-int nd_launch_gather_strips(const float *img, int W, int H, int cs, int ucs, int ol, int tile_begin, int tile_count, bool vertical,
-                            const QpBuf &dst, hipStream_t s) {
+// count: tile rows of the band from tile row `first` (ND_EDGE_ROWS, ND_EDGE_COLS) or tiles from tile `first` (ND_EDGE_CORNERS)
+int nd_launch_gather_edges(const float *img, int W, int H, int cs, int ucs, int ol, int set, int first, int count, const QpBuf &dst,
+                           hipStream_t s) {
     TileGeo g;
     ND_TRY(make_geo(W, H, cs, ucs, ol, &g));
-    const int n = vertical ? dst.Wb : dst.Hb, len = vertical ? dst.Hb : dst.Wb;
-    if (tile_begin < 0 || tile_count <= 0 || tile_begin + tile_count > g.cols * g.rows || dst.B != 2 * tile_count ||
-        dst.dt != ND_F32 || dst.pad != 0 || len != cs + 4 || n < 1 || n > cs + 4 || dst.used() > dst.pstride)
-        ND_FAIL(ND_EINVAL, "gather_strips: bad tile range [%d,+%d) or destination", tile_begin, tile_count);
+    const bool corners = set == ND_EDGE_CORNERS;
+    // a tile axis takes lines [0, cs + 4) of a tile inside the grid (their mirror stays inside the frame: make_geo); a band axis
+    // is clamped into the frame at any length
+    bool ok = img && dst.base && dst.dt == ND_F32 && dst.pad == 0 && dst.Hb >= 1 && dst.Wb >= 1 && dst.used() <= dst.pstride &&
+              dst.B <= 65535 && dst.Hb <= 65535 && first >= 0 && count > 0 && cs >= 3;
+    if (set == ND_EDGE_ROWS) ok = ok && first + count <= g.rows && dst.B == 2 * count && dst.Hb <= cs + 4;
+    else if (set == ND_EDGE_COLS) ok = ok && first + count <= g.rows && dst.B == 2 * g.cols && dst.Wb <= cs + 4;
+    else ok = ok && corners && first + count <= g.cols * g.rows && dst.B == 4 * count && dst.Hb <= cs + 4 && dst.Wb <= cs + 4;
+    if (!ok) ND_FAIL(ND_EINVAL, "gather_edges: bad set %d, range [%d,+%d) or destination", set, first, count);
     dim3 grid((dst.Wb + 255) / 256, dst.Hb, dst.B);
-    hipLaunchKernelGGL(k_gather_strips, grid, dim3(256), 0, s, img, g, tile_begin, vertical ? 1 : 0, (f32x4 *)dst.base, dst.Hb, dst.Wb);
+    hipLaunchKernelGGL(k_gather_edges, grid, dim3(256), 0, s, img, g, set, first, (f32x4 *)dst.base, dst.Hb, dst.Wb);
     ND_HIP(hipGetLastError());
     return ND_OK;
 }
 
-// dst image t, plane dst_p0 + p, interior pixel (r, c) of [r0, r1) x [c0, c1)  <-  src image img_mul * t + img_add, plane
-// src_p0 + p, interior pixel (yrel * step + r + oy, xi * step + c + ox), (yi, xi) = grid position of tile tile_begin + t,
-// yrel = yi - row0.  A band tensor: img_mul = 0, step = the tile stride at its level; a strip: step = 0.  band_rows > 0: the source
-// holds bands of band_rows tile rows in two slots, slot_elems apart -- a tile reads band yi / band_rows in slot (band & 1), row0 =
-// the band's first tile row (a launch may cross a band seam).
+// dst image dst_img0 + t, plane dst_p0 + p, interior pixel (r, c) of [r0, r1) x [c0, c1)  <-  src plane src_p0 + p, image
+// m.img_t * t + m.img_y * yrel + m.img_x * xi + m.img_add, interior pixel (yrel * m.step_y + r + m.oy, xi * m.step_x + c + m.ox),
+// (yi, xi) = grid position of tile tile_begin + t, yrel = yi - row0 (SpliceMap: nd_common.h).  band_rows > 0: the source holds bands
+// of band_rows tile rows in two slots, slot_elems apart -- a tile reads band yi / band_rows in slot (band & 1), row0 = the band's
+// first tile row (a launch may cross a band seam).
 struct SpliceArgs {
     const f32x4 *src;
     f32x4 *dst;
     long src_np, dst_np;
     int src_Hb, src_Wb, src_pad, dst_Hb, dst_Wb, dst_pad;
-    int tile_begin, cols, row0, step, img_mul, img_add, oy, ox, r0, c0, rows, ccols, planes;
+    int tile_begin, cols, row0, r0, c0, rows, ccols, planes, dst_img0;
+    SpliceMap m;
     int band_rows;
     long slot_elems;
 };
@@ -237,27 +260,29 @@ __global__ void k_splice(SpliceArgs a) {
     const int t = blockIdx.y / a.planes, p = blockIdx.y - t * a.planes;
     const int i = a.tile_begin + t;
     const int yi = i / a.cols, xi = i - yi * a.cols;
-    const int band = a.band_rows > 0 ? yi / a.band_rows : 0, row0 = a.band_rows > 0 ? band * a.band_rows : a.row0;
-    const int sy = (yi - row0) * a.step + r + a.oy + a.src_pad, sx = xi * a.step + c + a.ox + a.src_pad;
-    const long si = (long)p * a.src_np + (band & 1) * a.slot_elems + ((long)(a.img_mul * t + a.img_add) * a.src_Hb + sy) * a.src_Wb + sx;
-    a.dst[(long)p * a.dst_np + ((long)t * a.dst_Hb + r + a.dst_pad) * a.dst_Wb + c + a.dst_pad] = a.src[si];
+    const int band = a.band_rows > 0 ? yi / a.band_rows : 0, yrel = yi - (a.band_rows > 0 ? band * a.band_rows : a.row0);
+    const int simg = a.m.img_t * t + a.m.img_y * yrel + a.m.img_x * xi + a.m.img_add;
+    const int sy = yrel * a.m.step_y + r + a.m.oy + a.src_pad, sx = xi * a.m.step_x + c + a.m.ox + a.src_pad;
+    const long si = (long)p * a.src_np + (band & 1) * a.slot_elems + ((long)simg * a.src_Hb + sy) * a.src_Wb + sx;
+    a.dst[(long)p * a.dst_np + ((long)(a.dst_img0 + t) * a.dst_Hb + r + a.dst_pad) * a.dst_Wb + c + a.dst_pad] = a.src[si];
 }
 
 int nd_launch_splice(const QpBuf &src, int src_p0, const QpBuf &dst, int dst_p0, int planes, int tile_begin, int tile_count, int cols,
-                     int row0, int step, int img_mul, int img_add, int oy, int ox, int r0, int r1, int c0, int c1, hipStream_t s,
-                     int band_rows, long slot_elems) {
+                     int row0, const SpliceMap &m, int r0, int r1, int c0, int c1, hipStream_t s, int band_rows, long slot_elems,
+                     int dst_img0) {
     const int sH = src.Hb - 2 * src.pad, sW = src.Wb - 2 * src.pad, dH = dst.Hb - 2 * dst.pad, dW = dst.Wb - 2 * dst.pad;
-    bool ok = src.dt == ND_F32 && dst.dt == ND_F32 && tile_begin >= 0 && cols > 0 && tile_count > 0 && tile_count <= dst.B && planes > 0 &&
+    bool ok = src.dt == ND_F32 && dst.dt == ND_F32 && tile_begin >= 0 && cols > 0 && tile_count > 0 && dst_img0 >= 0 &&
+              dst_img0 + tile_count <= dst.B && dst.used() <= dst.np() && src.used() <= src.np() && planes > 0 &&
               src_p0 >= 0 && src_p0 + planes <= src.planes && dst_p0 >= 0 && dst_p0 + planes <= dst.planes &&
               r0 >= 0 && c0 >= 0 && r1 > r0 && c1 > c0 && r1 <= dH && c1 <= dW && band_rows >= 0 &&
-              (band_rows == 0 || (slot_elems >= 0 && img_mul == 0 && img_add == 0)) &&
-              img_add >= 0 && img_mul * (tile_count - 1) + img_add < src.B && (long)tile_count * planes <= 65535;
-    // the source window of every tile of the launch (a launch has at most a few hundred tiles)
+              (band_rows == 0 || slot_elems >= 0) && (long)tile_count * planes <= 65535;
+    // the source image and window of every tile of the launch (a launch has at most a few hundred tiles)
     for (int t = 0; t < tile_count && ok; ++t) {
         const int yi = (tile_begin + t) / cols, xi = (tile_begin + t) % cols;
         const int yrel = yi - (band_rows > 0 ? yi / band_rows * band_rows : row0);
-        if (band_rows > 0 && (yi / band_rows & 1)) ok = slot_elems >= (long)src.Hb * src.Wb && slot_elems + (long)src.Hb * src.Wb <= src.np();
-        ok = ok && yrel >= 0 && yrel * step + r0 + oy >= 0 && yrel * step + r1 - 1 + oy < sH && xi * step + c0 + ox >= 0 && xi * step + c1 - 1 + ox < sW;
+        const int simg = m.img_t * t + m.img_y * yrel + m.img_x * xi + m.img_add, y = yrel * m.step_y + m.oy, x = xi * m.step_x + m.ox;
+        if (band_rows > 0 && (yi / band_rows & 1)) ok = slot_elems >= src.used() && slot_elems + src.used() <= src.np();
+        ok = ok && yrel >= 0 && simg >= 0 && simg < src.B && y + r0 >= 0 && y + r1 - 1 < sH && x + c0 >= 0 && x + c1 - 1 < sW;
     }
     if (!ok) ND_FAIL(ND_EINVAL, "splice: region [%d,%d) x [%d,%d) of %d tiles x %d planes outside its source / destination", r0, r1, c0, c1,
                      tile_count, planes);
@@ -267,8 +292,8 @@ int nd_launch_splice(const QpBuf &src, int src_p0, const QpBuf &dst, int dst_p0,
     a.src_np = src.np(); a.dst_np = dst.np();
     a.src_Hb = src.Hb; a.src_Wb = src.Wb; a.src_pad = src.pad;
     a.dst_Hb = dst.Hb; a.dst_Wb = dst.Wb; a.dst_pad = dst.pad;
-    a.tile_begin = tile_begin; a.cols = cols; a.row0 = row0; a.step = step; a.img_mul = img_mul; a.img_add = img_add;
-    a.oy = oy; a.ox = ox; a.r0 = r0; a.c0 = c0; a.rows = r1 - r0; a.ccols = c1 - c0; a.planes = planes;
+    a.tile_begin = tile_begin; a.cols = cols; a.row0 = row0; a.m = m; a.dst_img0 = dst_img0;
+    a.r0 = r0; a.c0 = c0; a.rows = r1 - r0; a.ccols = c1 - c0; a.planes = planes;
     a.band_rows = band_rows; a.slot_elems = slot_elems;
     dim3 grid(((r1 - r0) * (c1 - c0) + 255) / 256, tile_count * planes);
     hipLaunchKernelGGL(k_splice, grid, dim3(256), 0, s, a);

@@ -204,18 +204,26 @@ int nd_launch_final1x1_stitch(const QpBuf &src, int cin, const float *w, const f
 int nd_launch_gather_pack(const float *img, int width, int height, int cs, int ucs, int ol, int tile_begin,
                           int tile_count, const QpBuf &dst, hipStream_t s);
 // shared encoder of the fused loop (fp32): band of tile rows from band_row0 as one first-layer input image (B = 1, no reflect
-// border); two border strips per tile (images 2t, 2t+1: top / bottom rows or, vertical, left / right columns of the tile's input);
-// per-tile copy of a window of a band or strip tensor into a tile buffer (see k_splice)
+// border); the images that yield P2's border lines (k_gather_edges: two row edges per tile row of a band, two column edges per
+// tile column of a band, four corners per tile of a launch); per-tile copy of a window of a band or edge tensor into a tile buffer
+// (see k_splice)
 int nd_launch_gather_band(const float *img, int width, int height, int cs, int ucs, int ol, int band_row0, const QpBuf &dst,
                           hipStream_t s);
-int nd_launch_gather_strips(const float *img, int width, int height, int cs, int ucs, int ol, int tile_begin, int tile_count,
-                            bool vertical, const QpBuf &dst, hipStream_t s);
+enum nd_edge_set { ND_EDGE_ROWS = 0, ND_EDGE_COLS = 1, ND_EDGE_CORNERS = 2 };
+int nd_launch_gather_edges(const float *img, int width, int height, int cs, int ucs, int ol, int set, int first, int count,
+                           const QpBuf &dst, hipStream_t s);
 // table[t] = where bordered pixel (0, 0) of tile tile_begin + t's buffer (border dst_pad) lies inside a plane of band tensor `src`
 // at a level with tile stride `step`: (band & 1) * slot_elems + ((yi - row0) * step + src.pad - dst_pad) * src.Wb + xi * step +
 // src.pad - dst_pad, with (yi, xi) = the tile's grid position, band = yi / band_rows its band and row0 = band * band_rows that
 // band's first tile row.  Written on the stream (no host-to-device copy); *origin_max = the largest entry
 int nd_launch_skip_origins(const QpBuf &src, int dst_pad, int tile_begin, int tile_count, int cols, int band_rows, int step, long slot_elems,
                            int *table, long *origin_max, hipStream_t s);
+// where tile t of a splice launch, at grid position (yi, xi) and yrel tile rows into its band, reads in the source: image
+// img_t * t + img_y * yrel + img_x * xi + img_add, its region shifted by (yrel * step_y + oy, xi * step_x + ox).  A band tensor: one
+// image, both steps = the tile stride at its level; the row / column edge lines: one step and img_y / img_x = 2; corners: img_t = 4
+struct SpliceMap {
+    int step_y = 0, step_x = 0, img_t = 0, img_y = 0, img_x = 0, img_add = 0, oy = 0, ox = 0;
+};
 int nd_launch_splice(const QpBuf &src, int src_p0, const QpBuf &dst, int dst_p0, int planes, int tile_begin, int tile_count, int cols,
-                     int row0, int step, int img_mul, int img_add, int oy, int ox, int r0, int r1, int c0, int c1, hipStream_t s,
-                     int band_rows = 0, long slot_elems = 0);
+                     int row0, const SpliceMap &m, int r0, int r1, int c0, int c1, hipStream_t s, int band_rows = 0,
+                     long slot_elems = 0, int dst_img0 = 0);

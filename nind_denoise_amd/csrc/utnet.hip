@@ -219,10 +219,11 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
     hipStream_t s = (hipStream_t)stream;
     const float *blob = (const float *)packed;
     const float *fw = blob + bl.off[kNumLayers - 1];
-    char *const band_base = (char *)fws, *const sh_base = band_base + fp.band_bytes, *const sv_base = sh_base + fp.strip_bytes;
-    int *const origins = (int *)(sv_base + fp.strip_bytes);
+    char *const band_base = (char *)fws, *const rows_base = band_base + fp.band_bytes, *const cols_base = rows_base + fp.row_edge_bytes;
+    char *const corner_base = cols_base + fp.col_edge_bytes;
+    int *const origins = (int *)(corner_base + fp.corner_bytes);
     const int f4 = funit / 4, cols = fp.cols, S = fp.S;
-    StackOpts enc, dec;   // the shared steps of a band / strip batch; the rest of a tile's stack, on the useful regions
+    StackOpts enc, dec;   // the shared steps of a band / a set of edge images; the rest of a tile's stack, on the useful regions
     enc.flags = dec.flags = flags;
     enc.step_end = dec.step_begin = kSharedSteps;
     dec.rois = rois;
@@ -238,7 +239,8 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
             }
     StepSrc2 src2[2];
     dec.src2 = src2;
-    // Bands are computed as the launches reach them, band b into slot b & 1 of the tensors the launches read; a launch takes `batch`
+    // Bands are computed as the launches reach them, band b into slot b & 1 of the tensors the launches read (the P2 lines of its
+    // row and column edge images among them: a function of the frame geometry alone, as the band is); a launch takes `batch`
     // tiles across a band seam and is cut at its second seam, so it reads two slots at most.  One stream: band b + 2 overwrites
     // slot b & 1 only after the launches that read band b.  bf: the band plan at full height (slot 0) -- what a launch addresses,
     // with each tile's band row and slot folded into its origin / its splice
@@ -256,25 +258,32 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
             bp.split = pl.split;
             ND_TRY(nd_launch_gather_band(img, width, height, cs, ucs, ol, row0, bp.buf[X0], s));
             ND_TRY(run_stack(funit, act, dtype, blob, bp, s, enc));
+            // its edge images, the same steps: top / bottom rows of every tile row, left / right columns of every tile column
+            Plan re = band_slot(row_edge_plan(fp, funit, dtype, nrows, rows_base), b & 1, fp.slots, P2);
+            Plan ce = band_slot(col_edge_plan(fp, funit, dtype, nrows, cs, cols_base), b & 1, fp.slots, P2);
+            re.split = ce.split = pl.split;
+            ND_TRY(nd_launch_gather_edges(img, width, height, cs, ucs, ol, ND_EDGE_ROWS, row0, nrows, re.buf[X0], s));
+            ND_TRY(nd_launch_gather_edges(img, width, height, cs, ucs, ol, ND_EDGE_COLS, row0, nrows, ce.buf[X0], s));
+            ND_TRY(run_stack(funit, act, dtype, blob, re, s, enc));
+            ND_TRY(run_stack(funit, act, dtype, blob, ce, s, enc));
             band_done = b;
         }
         if (progress) progress(progress_ctx, n, t0, cnt);
-        // border strips: images 2t / 2t + 1 = top / bottom rows (sh), left / right columns (sv) of tile t's input
-        Plan sh = make_enc_plan(funit, kStrip, cs + 4, 2 * cnt, kStrip, cs + 4, 2 * batch, sh_base, dtype);
-        Plan sv = make_enc_plan(funit, cs + 4, kStrip, 2 * cnt, cs + 4, kStrip, 2 * batch, sv_base, dtype);
-        sh.split = sv.split = pl.split;
-        ND_TRY(nd_launch_gather_strips(img, width, height, cs, ucs, ol, t0, cnt, false, sh.buf[X0], s));
-        ND_TRY(nd_launch_gather_strips(img, width, height, cs, ucs, ol, t0, cnt, true, sv.buf[X0], s));
-        ND_TRY(run_stack(funit, act, dtype, blob, sh, s, enc));
-        ND_TRY(run_stack(funit, act, dtype, blob, sv, s, enc));
-        // per tile: the skip halves where the decoder reads them, P2 whole, then P2's border lines from the strips
+        // corner patches: images 4t ... 4t + 3 = top-left, top-right, bottom-left, bottom-right kStrip x kStrip pixels of tile t's input
+        Plan cp = corner_plan(funit, dtype, cnt, batch, corner_base);
+        cp.split = pl.split;
+        ND_TRY(nd_launch_gather_edges(img, width, height, cs, ucs, ol, ND_EDGE_CORNERS, t0, cnt, cp.buf[X0], s));
+        ND_TRY(run_stack(funit, act, dtype, blob, cp, s, enc));
+        // per tile: the skip halves where the decoder reads them, P2 whole, then P2's border lines and corner pixels
         const Plan tp = make_plan(funit, cs, cs, batch, cnt, (char *)ws, dtype);
         dec.nsrc2 = 0;
         for (const Skip &k : skips) {
             const QpBuf &src = bf.buf[k.cat];
             if (!k.in_place) {
-                ND_TRY(nd_launch_splice(src, k.planes, tp.buf[k.cat], k.planes, k.planes, t0, cnt, cols, 0, k.tstep, 0, 0, 0, 0, k.win[0],
-                                        k.win[1], k.win[0], k.win[1], s, fp.R, slot_elems(src, fp.slots)));
+                SpliceMap m;
+                m.step_y = m.step_x = k.tstep;
+                ND_TRY(nd_launch_splice(src, k.planes, tp.buf[k.cat], k.planes, k.planes, t0, cnt, cols, 0, m, k.win[0], k.win[1], k.win[0],
+                                        k.win[1], s, fp.R, slot_elems(src, fp.slots)));
                 continue;
             }
             StepSrc2 &q = src2[dec.nsrc2++];
@@ -286,12 +295,38 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
                                           &q.origin_max, s));
         }
         const int n2 = enc_extent(cs + 4, P2);
-        ND_TRY(nd_launch_splice(bf.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, S / 4, 0, 0, 0, 0, 0, n2, 0, n2, s, fp.R,
+        SpliceMap whole;
+        whole.step_y = whole.step_x = S / 4;
+        ND_TRY(nd_launch_splice(bf.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, whole, 0, n2, 0, n2, s, fp.R,
                                 slot_elems(bf.buf[P2], fp.slots)));
-        ND_TRY(nd_launch_splice(sh.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 0, 0, 0, 0, 1, 0, n2, s));
-        ND_TRY(nd_launch_splice(sh.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 1, 1 - n2, 0, n2 - 1, n2, 0, n2, s));
-        ND_TRY(nd_launch_splice(sv.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 0, 0, 0, 0, n2, 0, 1, s));
-        ND_TRY(nd_launch_splice(sv.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, 0, 2, 1, 0, 1 - n2, 0, n2, n2 - 1, n2, s));
+        // rows 0 / n2 - 1 and columns 0 / n2 - 1: the tile's window of its tile row's / tile column's lines (side 0 / 1), band by
+        // band of the launch -- the column images of a short last band are shorter
+        for (int b = b0; b <= (t0 + cnt - 1) / per_band; ++b) {
+            const int lo = t0 > b * per_band ? t0 : b * per_band, hi = t0 + cnt < (b + 1) * per_band ? t0 + cnt : (b + 1) * per_band;
+            const int row0 = b * fp.R, nrows = fp.rows - row0 < fp.R ? fp.rows - row0 : fp.R;
+            const QpBuf rl = band_slot(row_edge_plan(fp, funit, dtype, nrows, rows_base), b & 1, fp.slots, P2).buf[P2];
+            const QpBuf cl = band_slot(col_edge_plan(fp, funit, dtype, nrows, cs, cols_base), b & 1, fp.slots, P2).buf[P2];
+            for (int side = 0; side < 2; ++side) {
+                const int at = side * (n2 - 1);
+                SpliceMap mr, mc;
+                mr.step_x = mc.step_y = S / 4;
+                mr.img_y = mc.img_x = 2;
+                mr.img_add = mc.img_add = side;
+                mr.oy = mc.ox = -at;
+                ND_TRY(nd_launch_splice(rl, 0, tp.buf[P2], 0, 2 * f4, lo, hi - lo, cols, row0, mr, at, at + 1, 0, n2, s, 0, 0, lo - t0));
+                ND_TRY(nd_launch_splice(cl, 0, tp.buf[P2], 0, 2 * f4, lo, hi - lo, cols, row0, mc, 0, n2, at, at + 1, s, 0, 0, lo - t0));
+            }
+        }
+        // the four corner pixels last: both reflections of the tile reach them
+        for (int k = 0; k < 4; ++k) {
+            const int r = (k >> 1) * (n2 - 1), c = (k & 1) * (n2 - 1);
+            SpliceMap m;
+            m.img_t = 4;
+            m.img_add = k;
+            m.oy = -r;
+            m.ox = -c;
+            ND_TRY(nd_launch_splice(cp.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, m, r, r + 1, c, c + 1, s));
+        }
         ND_TRY(run_stack(funit, act, dtype, blob, tp, s, dec));
         ND_TRY(nd_launch_final1x1_stitch(tp.buf[T4B], funit, fw, fw + 3 * funit, 2, canvas, width, height, cs, ucs, ol, t0, cnt, s));
         t0 += cnt;

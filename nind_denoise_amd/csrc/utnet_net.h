@@ -505,10 +505,18 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
 //   * the band runs steps [0, kSharedSteps) once on its window of the mirrored frame;
 //   * the decoder reads neither the contaminated lines of CAT4 nor those of CAT3 (region plan) -- it reads the tile's skip halves
 //     where the band wrote them (ConvDesc::in2; a step whose kernel has no second input source gets a copy of the window);
-//   * P2 (the level-2 input, computed whole per tile) is copied from the band, and its contaminated rows / cols 0 and n-1 are
-//     recomputed exactly from kStrip-pixel strips of the tile's own input (a 16-row strip yields one P2 row through the 6 steps).
-//   * launches take `batch` tiles across band seams: the band tensors they read (CAT4, CAT3, P2) live in two slots, band b in
-//     slot b & 1, and a launch is cut at its second seam.
+//   * P2 (the level-2 input, computed whole per tile) is copied from the band, and its contaminated rows / cols 0 and n-1 come
+//     from kStrip-pixel edge images (16 input rows yield one P2 row through the 6 steps).  All tiles of a tile row reflect about
+//     the same two frame lines, so their top / bottom rows are windows of two kStrip x wx images per tile row that follow the
+//     tile along y (its reflection included) and the band along x: row_edge_plan, computed with the band.  Likewise two
+//     hx x kStrip images per tile column of the band: col_edge_plan.  A windowed line is the tile's own except at its two end
+//     pixels, where the tile's reflection along the other axis reaches: P2's four corner pixels come from kStrip x kStrip
+//     patches reflected along both axes, four per tile of a launch (corner_plan).  Every image starts on the tile grid (S % 4 ==
+//     0), so an F(4,3) pixel group of its first level covers the same pixels as in a strip of the tile's own input: with 8 | S a
+//     windowed line has that strip's bits on pixels 2 ... n - 3; pixels 1 and n - 2 come from groups that also hold neighbours
+//     of the reflected pixels and differ from it by fp32 rounding;
+//   * launches take `batch` tiles across band seams: what they read of a band (CAT4, CAT3, P2 and the P2 lines of both edge
+//     sets) lives in two slots, band b in slot b & 1, and a launch is cut at its second seam.
 // The deeper levels stay per tile: their exact border lines would need strips of 36 / 76 input rows.
 constexpr int kSharedSteps = 6;
 constexpr int kStrip = 16;
@@ -529,9 +537,9 @@ inline int enc_extent(int x, int b) {
 }
 // X0 ... P2 for B images of hx x wx first-layer input; planes sized for cap images of hcap x wcap (the plane stride does not move
 // when a band or a batch is smaller: plane 1 of X0 and the slack stay zero from the one fill of the workspace).  slots > 1 (bands):
-// the tensors the per-tile launches read -- CAT4, CAT3, P2 -- hold `slots` times the capacity, so that band b + 1 can be computed
-// (into slot (b + 1) & 1: band_slot) while launches still read band b
-Plan make_enc_plan(int f, int hx, int wx, int B, int hcap, int wcap, int cap, char *base, int dt, int slots = 1) {
+// the tensors the per-tile launches read -- CAT4, CAT3, P2 from `slotted` on (a band: all three, its edge images: P2) -- hold
+// `slots` times the capacity, so that band b + 1 can be computed (into slot (b + 1) & 1: band_slot) while launches still read band b
+Plan make_enc_plan(int f, int hx, int wx, int B, int hcap, int wcap, int cap, char *base, int dt, int slots = 1, Buf slotted = CAT4) {
     Plan p = {};
     size_t off = 0;
     auto add = [&](Buf id, int ch, int pad) {
@@ -543,7 +551,7 @@ Plan make_enc_plan(int f, int hx, int wx, int B, int hcap, int wcap, int cap, ch
         q.Wb = enc_extent(wx, id) + 2 * pad;
         q.pad = pad;
         q.pstride = (long)cap * (enc_extent(hcap, id) + 2 * pad) * (enc_extent(wcap, id) + 2 * pad);
-        if (id == CAT4 || id == CAT3 || id == P2) q.pstride *= slots;
+        if ((id == CAT4 || id == CAT3 || id == P2) && id >= slotted) q.pstride *= slots;
         q.base = (float *)(base + off);
         off += ((size_t)q.planes * q.pstride + nd_buf_slack(enc_extent(wcap, id) + 2 * pad)) * 16;
         off = (off + 255) & ~(size_t)255;
@@ -561,10 +569,11 @@ Plan make_enc_plan(int f, int hx, int wx, int B, int hcap, int wcap, int cap, ch
     return p;
 }
 
-// 16-byte elements between the slots of a two-slot band tensor, and the view of a band plan whose CAT4 / CAT3 / P2 are slot `slot`
+// 16-byte elements between the slots of a two-slot band tensor, and the view of a plan whose slotted tensors are slot `slot`
 inline long slot_elems(const QpBuf &q, int slots) { return q.pstride / slots; }
-inline Plan band_slot(Plan p, int slot, int slots) {
-    for (Buf id : {CAT4, CAT3, P2}) p.buf[id].base += (size_t)slot * slot_elems(p.buf[id], slots) * 4;
+inline Plan band_slot(Plan p, int slot, int slots, Buf slotted = CAT4) {
+    for (Buf id : {CAT4, CAT3, P2})
+        if (id >= slotted) p.buf[id].base += (size_t)slot * slot_elems(p.buf[id], slots) * 4;
     return p;
 }
 
@@ -576,13 +585,25 @@ struct FramePlan {
     int slots = 1;           // slots of the band tensors the per-tile launches read (2 when there is more than one band)
     int hx = 0, wx = 0;      // first-layer input of a full band
     int win4[2] = {0, 0}, win3[2] = {0, 0};   // [lo, hi) of the CAT4 / CAT3 skip pixels the decoder reads (both axes)
-    size_t band_bytes = 0, strip_bytes = 0, origin_bytes = 0, bytes = 0;   // frame workspace: band | strips (h) | strips (v) | origins
+    // frame workspace: band | row edges | column edges | corners | origins
+    size_t band_bytes = 0, row_edge_bytes = 0, col_edge_bytes = 0, corner_bytes = 0, origin_bytes = 0, bytes = 0;
 };
 inline int band_hx(const FramePlan &fp, int nrows, int cs) { return (nrows - 1) * fp.S + cs + 4; }
+// the edge images of a band of nrows tile rows (planes sized for a full band; P2 in the band's slots) and the corner patches of a
+// launch of ntiles tiles (planes sized for cap): see the comment block above
+inline Plan row_edge_plan(const FramePlan &fp, int f, int dt, int nrows, char *base) {
+    return make_enc_plan(f, kStrip, fp.wx, 2 * nrows, kStrip, fp.wx, 2 * fp.R, base, dt, fp.slots, P2);
+}
+inline Plan col_edge_plan(const FramePlan &fp, int f, int dt, int nrows, int cs, char *base) {
+    return make_enc_plan(f, band_hx(fp, nrows, cs), kStrip, 2 * fp.cols, fp.hx, kStrip, 2 * fp.cols, base, dt, fp.slots, P2);
+}
+inline Plan corner_plan(int f, int dt, int ntiles, int cap, char *base) {
+    return make_enc_plan(f, kStrip, kStrip, 4 * ntiles, kStrip, kStrip, 4 * cap, base, dt);
+}
 
 extern "C" int nd_tile_grid(int W, int H, int cs, int ucs, int ol, int *cols, int *rows, int *pad);
 
-// the band plan: a function of the frame geometry, the dtype and the flags (batch only sizes the strip buffers)
+// the band plan: a function of the frame geometry, the dtype and the flags (batch only sizes the corner buffers and the tables)
 int frame_plan(int f, int dt, int flags, int W, int H, int cs, int ucs, int ol, int batch, FramePlan *fp) {
     *fp = FramePlan();
     ND_TRY(check_funit(f, dt));
@@ -632,10 +653,9 @@ int frame_plan(int f, int dt, int flags, int W, int H, int cs, int ucs, int ol, 
     fp->slots = fp->nbands > 1 ? 2 : 1;
     fp->band_bytes = make_enc_plan(f, fp->hx, fp->wx, 1, fp->hx, fp->wx, 1, nullptr, dt, fp->slots).bytes;
     if ((long)fp->hx * fp->wx >= (1L << 26)) return ND_OK;   // (32-bit offsets of the conv kernels on a band image)
-    // every shared step of the band and of both strip shapes must run in conv_w2d (its pool epilogue included)
-    const Plan plans[3] = {make_enc_plan(f, fp->hx, fp->wx, 1, fp->hx, fp->wx, 1, nullptr, dt),
-                           make_enc_plan(f, kStrip, cs + 4, 2, kStrip, cs + 4, 2, nullptr, dt),
-                           make_enc_plan(f, cs + 4, kStrip, 2, cs + 4, kStrip, 2, nullptr, dt)};
+    // every shared step of the band and of the three edge shapes must run in conv_w2d (its pool epilogue included)
+    const Plan plans[4] = {make_enc_plan(f, fp->hx, fp->wx, 1, fp->hx, fp->wx, 1, nullptr, dt), row_edge_plan(*fp, f, dt, fp->R, nullptr),
+                           col_edge_plan(*fp, f, dt, fp->R, cs, nullptr), corner_plan(f, dt, batch, batch, nullptr)};
     for (const Plan &pp : plans)
         for (int i = 0; i < kSharedSteps; ++i) {
             const Step &st = kSteps[i];
@@ -643,10 +663,12 @@ int frame_plan(int f, int dt, int flags, int W, int H, int cs, int ucs, int ol, 
             if (step_form(st, f, dt, flags, pp, bl) != FORM_W1D4 || !nd_f43_w2d(pp.buf[st.src], lcout(kLayers[st.layer], f), false, flags))
                 return ND_OK;
         }
-    fp->strip_bytes = make_enc_plan(f, kStrip, cs + 4, 2 * batch, kStrip, cs + 4, 2 * batch, nullptr, dt).bytes;
+    fp->row_edge_bytes = plans[1].bytes;
+    fp->col_edge_bytes = plans[2].bytes;
+    fp->corner_bytes = plans[3].bytes;
     // where each tile of a launch lies in the band's CAT4 / CAT3 planes (the decoder reads the skip halves in place): two tables
     fp->origin_bytes = ((size_t)batch * sizeof(int) + 255) & ~(size_t)255;
-    fp->bytes = fp->band_bytes + 2 * fp->strip_bytes + 2 * fp->origin_bytes;
+    fp->bytes = fp->band_bytes + fp->row_edge_bytes + fp->col_edge_bytes + fp->corner_bytes + 2 * fp->origin_bytes;
     fp->D = 2;
     return ND_OK;
 }
