@@ -67,13 +67,16 @@ typedef enum nd_flags {
                                  epilogue wherever its kernel can -- identical values)                                        */
     ND_FLAG_TILE_ENCODER = 32, /* A/B switch: nd_utnet_denoise_frame runs every tile's whole encoder (default: the first two
                                  levels once per band of tile rows, see nd_utnet_frame_plan)                                   */
+    ND_FLAG_TILE_LEVEL2 = 64,  /* A/B switch: nd_utnet_denoise_frame keeps the third encoder level per tile where it would share it
+                                 too (nd_utnet_frame_levels: 3).  Taken by the frame-loop entry points only (nd_utnet_frame_*,
+                                 nd_utnet_denoise_frame); an unknown bit everywhere else                                          */
     ND_FLAG_FULL_TILES = 8    /* nd_utnet_denoise_tiles / nd_utnet_profile_stack: compute every layer on the whole tile, as
                                  UtNet.forward does.  Default there: the last decoder levels compute only the pixels that the
                                  useful crop [pad, cs - pad) of a tile can reach (denoise_image.py:249-258 discards the rest of
                                  the network output before the canvas +=) -- same canvas, 19 % less work at cs 264 / ucs 200    */
 } nd_flags;
 
-int nd_version(void);   /* 107 = this header */
+int nd_version(void);   /* 108 = this header */
 const char *nd_last_error(void);
 
 /* ---------------------------------------------------------------- tile geometry (host, pure integer)
@@ -163,6 +166,16 @@ int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, const void 
  * per band, bands, stride, grid columns, grid rows, band input rows of a full band}.  A function of the frame geometry, the dtype
  * and the flags only (batch enters only through the workspace size). */
 int nd_utnet_frame_plan(int funit, int dtype, int flags, int width, int height, int cs, int ucs, int ol, int *out);
+/* Host-only query: the encoder levels nd_utnet_denoise_frame shares in all -- 0, 2 (D above), or 3 where the tile stride is also
+ * divisible by 8 and the decoder's region plan leaves the border lines of the third skip unread (crop >= 32 at every valid cs):
+ * then convs3.0, convs3.2 and the third pool also run once per band, on the band's pooled level-2 input; tconvs2.0 reads its skip
+ * half where the band wrote it; a tile's pooled level-3 input is its window of the band's, with its border lines from 6-line
+ * images at level-2 resolution (two per tile row and two per tile column of a band, built from the level-2 edge lines and the
+ * band's clean neighbours) and its corner pixels from four 6 x 6 patches of the tile's own level-2 input; and the per-tile stack
+ * starts at convs4.0.  Level-2 values are fp32 re-associations of the per-tile ones (the band's F(6x6) tile grid differs from a
+ * tile's).  The frame workspace then also holds a third origin table, the level-2 band, line and corner tensors and their
+ * Winograd scratch.  ND_FLAG_TILE_LEVEL2 keeps it at 2.  *levels is written; same arguments and errors as nd_utnet_frame_plan. */
+int nd_utnet_frame_levels(int funit, int dtype, int flags, int width, int height, int cs, int ucs, int ol, int *levels);
 
 /* Profiling entry point for the roofline report: one pass of the conv stack (22 MFMA conv layers + 4 pools, the launches
  * between the input pack and the final 1x1) with a HIP event recorded on `stream` between launches.  Synchronises the stream.

@@ -14,7 +14,7 @@ DTYPE = {"f32": 0, "fp32": 0, "float32": 0, "bf16": 1, "bfloat16": 1, "f16": 2, 
 ACT = {"none": 0, "PReLU": 1, "ELU": 2, "Hardswish": 3}
 KIND = {"conv3": 0, "convT3": 1, "convT2s2": 2, "conv1": 3, "conv2s2": 4}
 # nd_flags (include/nind_hip.h): per-call arithmetic switches
-FLAG_NO_SPLITK, FLAG_DIRECT_CONV, FLAG_W1D_REGS, FLAG_FULL_TILES, FLAG_UNFUSED_POOL, FLAG_TILE_ENCODER = 1, 2, 4, 8, 16, 32
+FLAG_NO_SPLITK, FLAG_DIRECT_CONV, FLAG_W1D_REGS, FLAG_FULL_TILES, FLAG_UNFUSED_POOL, FLAG_TILE_ENCODER, FLAG_TILE_LEVEL2 = 1, 2, 4, 8, 16, 32, 64
 # nd_progress_fn: (ctx, launch index, first tile, tile count)
 PROGRESS_FN = ctypes.CFUNCTYPE(None, c_void_p, c_int, c_int, c_int)
 
@@ -68,6 +68,7 @@ _SIGNATURES = {
     "nd_utnet_useful_region": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int)]),
     "nd_utnet_frame_workspace_bytes": (c_size_t, [c_int] * 9),
     "nd_utnet_frame_plan": (c_int, [c_int] * 8 + [POINTER(c_int)]),
+    "nd_utnet_frame_levels": (c_int, [c_int] * 8 + [POINTER(c_int)]),
     "nd_utnet_denoise_frame": (c_int, [c_int] * 4 + [c_void_p] * 3 + [c_int] * 8 + [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                                                                     PROGRESS_FN, c_void_p]),
     "nd_layer_packed_bytes": (c_size_t, [c_int] * 4),

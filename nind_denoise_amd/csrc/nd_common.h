@@ -140,9 +140,13 @@ int nd_check_out(const char *who, const ConvDesc &d, int oh, int ow, bool at_lea
 int nd_check_int32(const char *who, const QpBuf &in);
 // d's region of interest (if any) lies inside the Hv x Wv grid; refused: the launcher takes no region for this layer (`why`)
 int nd_check_roi(const char *who, const ConvDesc &d, int Hv, int Wv, bool refused, const char *why);
-// the arithmetic switches every flags-taking entry point accepts (include/nind_hip.h: nd_flags); unknown bits are an error
-static inline int nd_check_flags(int flags) {
-    if (flags & ~(ND_FLAG_NO_SPLITK | ND_FLAG_DIRECT_CONV | ND_FLAG_W1D_REGS | ND_FLAG_FULL_TILES | ND_FLAG_UNFUSED_POOL | ND_FLAG_TILE_ENCODER)) ND_FAIL(ND_EINVAL, "unknown flag bits 0x%x", flags);
+// the arithmetic switches every flags-taking entry point accepts (include/nind_hip.h: nd_flags); unknown bits are an error.
+// frame_loop: the frame-loop entry points (nd_utnet_frame_*, nd_utnet_denoise_frame) also take ND_FLAG_TILE_LEVEL2, which means
+// nothing anywhere else
+static inline int nd_check_flags(int flags, bool frame_loop = false) {
+    const int known = ND_FLAG_NO_SPLITK | ND_FLAG_DIRECT_CONV | ND_FLAG_W1D_REGS | ND_FLAG_FULL_TILES | ND_FLAG_UNFUSED_POOL |
+                      ND_FLAG_TILE_ENCODER | (frame_loop ? ND_FLAG_TILE_LEVEL2 : 0);
+    if (flags & ~known) ND_FAIL(ND_EINVAL, "unknown flag bits 0x%x", flags);
     return ND_OK;
 }
 const char *nd_conv_variant_label(int v);

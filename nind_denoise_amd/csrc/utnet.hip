@@ -173,12 +173,12 @@ extern "C" int nd_utnet_denoise_tiles(int funit, int act, int dtype, int flags, 
 extern "C" size_t nd_utnet_frame_workspace_bytes(int funit, int dtype, int flags, int width, int height, int cs, int ucs, int ol,
                                                  int batch) {
     FramePlan fp;
-    if (nd_check_flags(flags) != ND_OK || frame_plan(funit, dtype, flags, width, height, cs, ucs, ol, batch, &fp) != ND_OK) return 0;
+    if (nd_check_flags(flags, true) != ND_OK || frame_plan(funit, dtype, flags, width, height, cs, ucs, ol, batch, &fp) != ND_OK) return 0;
     return fp.bytes;
 }
 
 extern "C" int nd_utnet_frame_plan(int funit, int dtype, int flags, int width, int height, int cs, int ucs, int ol, int *out) {
-    ND_TRY(nd_check_flags(flags));
+    ND_TRY(nd_check_flags(flags, true));
     if (!out) ND_FAIL(ND_EINVAL, "nd_utnet_frame_plan: null output");
     FramePlan fp;
     ND_TRY(frame_plan(funit, dtype, flags, width, height, cs, ucs, ol, 1, &fp));
@@ -187,11 +187,20 @@ extern "C" int nd_utnet_frame_plan(int funit, int dtype, int flags, int width, i
     return ND_OK;
 }
 
+extern "C" int nd_utnet_frame_levels(int funit, int dtype, int flags, int width, int height, int cs, int ucs, int ol, int *levels) {
+    ND_TRY(nd_check_flags(flags, true));
+    if (!levels) ND_FAIL(ND_EINVAL, "nd_utnet_frame_levels: null output");
+    FramePlan fp;
+    ND_TRY(frame_plan(funit, dtype, flags, width, height, cs, ucs, ol, 1, &fp));
+    *levels = fp.levels;
+    return ND_OK;
+}
+
 extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, const void *packed, const float *img, float *canvas,
                                       int width, int height, int cs, int ucs, int ol, int tile_begin, int tile_count, int batch,
                                       void *ws, size_t ws_bytes, void *fws, size_t fws_bytes, void *stream, nd_progress_fn progress,
                                       void *progress_ctx) {
-    ND_TRY(nd_check_flags(flags));
+    ND_TRY(nd_check_flags(flags, true));
     FramePlan fp;
     ND_TRY(frame_plan(funit, dtype, flags, width, height, cs, ucs, ol, batch, &fp));
     if (tile_begin < 0 || tile_count < 0 || tile_begin + tile_count > fp.cols * fp.rows)
@@ -208,7 +217,7 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
         for (int t0 = tile_begin; t0 < end; t0 += batch, ++n) {
             const int cnt = end - t0 < batch ? end - t0 : batch;
             if (progress) progress(progress_ctx, n, t0, cnt);
-            ND_TRY(nd_utnet_denoise_tiles(funit, act, dtype, flags, packed, img, canvas, width, height, cs, ucs, ol, t0, cnt, batch, ws,
+            ND_TRY(nd_utnet_denoise_tiles(funit, act, dtype, flags & ~ND_FLAG_TILE_LEVEL2, packed, img, canvas, width, height, cs, ucs, ol, t0, cnt, batch, ws,
                                           ws_bytes, stream));
         }
         return ND_OK;
@@ -222,22 +231,41 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
     char *const band_base = (char *)fws, *const rows_base = band_base + fp.band_bytes, *const cols_base = rows_base + fp.row_edge_bytes;
     char *const corner_base = cols_base + fp.col_edge_bytes;
     int *const origins = (int *)(corner_base + fp.corner_bytes);
+    // level 2 (utnet_net.h: frame_plan_level2): a third origin table, then its band, line image and corner patch tensors and scratch
+    const bool l2 = fp.levels == 3;
+    char *const l2_band_base = (char *)origins + 3 * fp.origin_bytes, *const l2_rows_base = l2_band_base + fp.l2_band_bytes;
+    char *const l2_cols_base = l2_rows_base + fp.l2_row_bytes, *const l2_corner_base = l2_cols_base + fp.l2_col_bytes;
+    char *const l2_wino = l2_corner_base + fp.l2_corner_bytes;
     const int f4 = funit / 4, cols = fp.cols, S = fp.S;
-    StackOpts enc, dec;   // the shared steps of a band / a set of edge images; the rest of a tile's stack, on the useful regions
-    enc.flags = dec.flags = flags;
-    enc.step_end = dec.step_begin = kSharedSteps;
+    const int n2 = enc_extent(cs + 4, P2), n3 = l2_extent(n2, P3);
+    // the shared steps of a band / a set of edge images; level 2 of a band / a set of its images; the rest of a tile's stack, on
+    // the useful regions
+    StackOpts enc, enc2, dec;
+    enc.flags = enc2.flags = dec.flags = flags;
+    enc.step_end = enc2.step_begin = kSharedSteps;
+    enc2.step_end = kLevel2End;
+    dec.step_begin = l2 ? kLevel2End : kSharedSteps;
     dec.rois = rois;
+    auto l2_scratch = [&](Plan p) {
+        p.split = pl.split;
+        p.wino = l2_wino;
+        p.wino_bytes = fp.l2_wino_bytes;
+        return p;
+    };
     // The two decoder steps that read a skip half (tconvs4.0: CAT4, tconvs3.0: CAT3) take it from the band where their kernel has a
     // second input source; else the window is copied into the tile buffer as the layer expects it (k_splice)
-    struct Skip { Buf cat; int planes, step, tstep; const int *win; int *table; bool in_place; } skips[2] = {
-        {CAT4, f4, -1, S, fp.win4, origins, false}, {CAT3, 2 * f4, -1, S / 2, fp.win3, origins + fp.origin_bytes / sizeof(int), false}};
+    // (with level 2 also tconvs2.0: CAT2)
+    struct Skip { Buf cat; int planes, step, tstep; const int *win; int *table; bool in_place; } skips[3] = {
+        {CAT4, f4, -1, S, fp.win4, origins, false}, {CAT3, 2 * f4, -1, S / 2, fp.win3, origins + fp.origin_bytes / sizeof(int), false},
+        {CAT2, 4 * f4, -1, S / 4, fp.win2, origins + 2 * fp.origin_bytes / sizeof(int), false}};
+    const int nskips = l2 ? 3 : 2;
     for (Skip &k : skips)
         for (int i = kSharedSteps; i < kNumSteps; ++i)
             if (kSteps[i].layer >= 0 && kSteps[i].src == k.cat) {
                 k.step = i;
                 k.in_place = form_takes_src2(kSteps[i], step_form(kSteps[i], funit, dtype, flags, pl, bl), funit, flags, pl);
             }
-    StepSrc2 src2[2];
+    StepSrc2 src2[3];
     dec.src2 = src2;
     // Bands are computed as the launches reach them, band b into slot b & 1 of the tensors the launches read (the P2 lines of its
     // row and column edge images among them: a function of the frame geometry alone, as the band is); a launch takes `batch`
@@ -246,6 +274,7 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
     // with each tile's band row and slot folded into its origin / its splice
     const int per_band = fp.R * cols;
     const Plan bf = make_enc_plan(funit, fp.hx, fp.wx, 1, fp.hx, fp.wx, 1, band_base, dtype, fp.slots);
+    const Plan bf2 = l2 ? l2_band_plan(fp, funit, dtype, fp.R, cs, l2_band_base) : Plan();
     int band_done = tile_begin / per_band - 1;
     for (int t0 = tile_begin, n = 0; t0 < end; ++n) {
         const int b0 = t0 / per_band;
@@ -266,6 +295,32 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
             ND_TRY(nd_launch_gather_edges(img, width, height, cs, ucs, ol, ND_EDGE_COLS, row0, nrows, ce.buf[X0], s));
             ND_TRY(run_stack(funit, act, dtype, blob, re, s, enc));
             ND_TRY(run_stack(funit, act, dtype, blob, ce, s, enc));
+            if (l2) {
+                // level 2 of the band on its P2, then of its line images: the P2 edge line of a tile row (column) next to the five
+                // clean band rows (columns) inside it
+                Plan b2 = l2_scratch(l2_slot(l2_band_plan(fp, funit, dtype, nrows, cs, l2_band_base), b & 1, fp.slots));
+                b2.buf[P2] = bp.buf[P2];
+                ND_TRY(run_stack(funit, act, dtype, blob, b2, s, enc2));
+                const Plan r2 = l2_scratch(l2_slot(l2_row_plan(fp, funit, dtype, nrows, l2_rows_base), b & 1, fp.slots, P3));
+                const Plan c2 = l2_scratch(l2_slot(l2_col_plan(fp, funit, dtype, nrows, cs, l2_cols_base), b & 1, fp.slots, P3));
+                const int h2 = bp.buf[P2].Hb, w2 = bp.buf[P2].Wb;
+                for (int side = 0; side < 2; ++side) {
+                    // (splice: "tile" t = tile row t of the band on a grid of one column / tile column t on a grid of one row)
+                    const int at = side * (kStrip2 - 1), in0 = 1 - side, in1 = kStrip2 - side;
+                    SpliceMap br, lr, bc, lc;
+                    br.step_y = bc.step_x = S / 4;
+                    br.oy = bc.ox = side * (n2 - kStrip2);
+                    lr.img_y = lc.img_x = 2;
+                    lr.img_add = lc.img_add = side;
+                    lr.oy = lc.ox = -at;
+                    ND_TRY(nd_launch_splice(bp.buf[P2], 0, r2.buf[P2], 0, 2 * f4, 0, nrows, 1, 0, br, in0, in1, 0, w2, s, 0, 0, side * nrows));
+                    ND_TRY(nd_launch_splice(re.buf[P2], 0, r2.buf[P2], 0, 2 * f4, 0, nrows, 1, 0, lr, at, at + 1, 0, w2, s, 0, 0, side * nrows));
+                    ND_TRY(nd_launch_splice(bp.buf[P2], 0, c2.buf[P2], 0, 2 * f4, 0, cols, cols, 0, bc, 0, h2, in0, in1, s, 0, 0, side * cols));
+                    ND_TRY(nd_launch_splice(ce.buf[P2], 0, c2.buf[P2], 0, 2 * f4, 0, cols, cols, 0, lc, 0, h2, at, at + 1, s, 0, 0, side * cols));
+                }
+                ND_TRY(run_stack(funit, act, dtype, blob, r2, s, enc2));
+                ND_TRY(run_stack(funit, act, dtype, blob, c2, s, enc2));
+            }
             band_done = b;
         }
         if (progress) progress(progress_ctx, n, t0, cnt);
@@ -277,8 +332,9 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
         // per tile: the skip halves where the decoder reads them, P2 whole, then P2's border lines and corner pixels
         const Plan tp = make_plan(funit, cs, cs, batch, cnt, (char *)ws, dtype);
         dec.nsrc2 = 0;
-        for (const Skip &k : skips) {
-            const QpBuf &src = bf.buf[k.cat];
+        for (int ki = 0; ki < nskips; ++ki) {
+            const Skip &k = skips[ki];
+            const QpBuf &src = k.cat == CAT2 ? bf2.buf[k.cat] : bf.buf[k.cat];
             if (!k.in_place) {
                 SpliceMap m;
                 m.step_y = m.step_x = k.tstep;
@@ -294,7 +350,6 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
             ND_TRY(nd_launch_skip_origins(src, tp.buf[k.cat].pad, t0, cnt, cols, fp.R, k.tstep, slot_elems(src, fp.slots), k.table,
                                           &q.origin_max, s));
         }
-        const int n2 = enc_extent(cs + 4, P2);
         SpliceMap whole;
         whole.step_y = whole.step_x = S / 4;
         ND_TRY(nd_launch_splice(bf.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, whole, 0, n2, 0, n2, s, fp.R,
@@ -326,6 +381,49 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
             m.oy = -r;
             m.ox = -c;
             ND_TRY(nd_launch_splice(cp.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, m, r, r + 1, c, c + 1, s));
+        }
+        if (l2) {
+            // level 2 of the four 6 x 6 corner patches of every tile's P2 (image k * cnt + t): the P3 corner pixels
+            const Plan k2 = l2_scratch(l2_corner_plan(funit, dtype, cnt, batch, l2_corner_base));
+            for (int k = 0; k < 4; ++k) {
+                SpliceMap m;   // ("tile" t of a grid of one row: image t of the launch)
+                m.img_t = 1;
+                m.oy = (k >> 1) * (n2 - kStrip2);
+                m.ox = (k & 1) * (n2 - kStrip2);
+                ND_TRY(nd_launch_splice(tp.buf[P2], 0, k2.buf[P2], 0, 2 * f4, 0, cnt, cnt, 0, m, 0, kStrip2, 0, kStrip2, s, 0, 0, k * cnt));
+            }
+            ND_TRY(run_stack(funit, act, dtype, blob, k2, s, enc2));
+            // P3 as P2 above: the window of the band's, its four lines from the band's line images, its corner pixels last
+            SpliceMap whole3;
+            whole3.step_y = whole3.step_x = S / 8;
+            ND_TRY(nd_launch_splice(bf2.buf[P3], 0, tp.buf[P3], 0, 4 * f4, t0, cnt, cols, 0, whole3, 0, n3, 0, n3, s, fp.R,
+                                    slot_elems(bf2.buf[P3], fp.slots)));
+            for (int b = b0; b <= (t0 + cnt - 1) / per_band; ++b) {
+                const int lo = t0 > b * per_band ? t0 : b * per_band, hi = t0 + cnt < (b + 1) * per_band ? t0 + cnt : (b + 1) * per_band;
+                const int row0 = b * fp.R, nrows = fp.rows - row0 < fp.R ? fp.rows - row0 : fp.R;
+                const QpBuf rl = l2_slot(l2_row_plan(fp, funit, dtype, nrows, l2_rows_base), b & 1, fp.slots, P3).buf[P3];
+                const QpBuf cl = l2_slot(l2_col_plan(fp, funit, dtype, nrows, cs, l2_cols_base), b & 1, fp.slots, P3).buf[P3];
+                for (int side = 0; side < 2; ++side) {
+                    const int at = side * (n3 - 1);
+                    SpliceMap mr, mc;
+                    mr.step_x = mc.step_y = S / 8;
+                    mr.img_y = mc.img_x = 1;
+                    mr.img_add = side * nrows;
+                    mc.img_add = side * cols;
+                    mr.oy = mc.ox = -at;
+                    ND_TRY(nd_launch_splice(rl, 0, tp.buf[P3], 0, 4 * f4, lo, hi - lo, cols, row0, mr, at, at + 1, 0, n3, s, 0, 0, lo - t0));
+                    ND_TRY(nd_launch_splice(cl, 0, tp.buf[P3], 0, 4 * f4, lo, hi - lo, cols, row0, mc, 0, n3, at, at + 1, s, 0, 0, lo - t0));
+                }
+            }
+            for (int k = 0; k < 4; ++k) {
+                const int r = (k >> 1) * (n3 - 1), c = (k & 1) * (n3 - 1);
+                SpliceMap m;
+                m.img_t = 1;
+                m.img_add = k * cnt;
+                m.oy = -r;
+                m.ox = -c;
+                ND_TRY(nd_launch_splice(k2.buf[P3], 0, tp.buf[P3], 0, 4 * f4, t0, cnt, cols, 0, m, r, r + 1, c, c + 1, s));
+            }
         }
         ND_TRY(run_stack(funit, act, dtype, blob, tp, s, dec));
         ND_TRY(nd_launch_final1x1_stitch(tp.buf[T4B], funit, fw, fw + 3 * funit, 2, canvas, width, height, cs, ucs, ol, t0, cnt, s));

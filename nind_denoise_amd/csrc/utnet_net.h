@@ -587,6 +587,11 @@ struct FramePlan {
     int win4[2] = {0, 0}, win3[2] = {0, 0};   // [lo, hi) of the CAT4 / CAT3 skip pixels the decoder reads (both axes)
     // frame workspace: band | row edges | column edges | corners | origins
     size_t band_bytes = 0, row_edge_bytes = 0, col_edge_bytes = 0, corner_bytes = 0, origin_bytes = 0, bytes = 0;
+    // level 2 (levels == 3): behind the above, a third origin table | band | row images | column images | corner patches | Winograd scratch
+    int levels = 0;          // encoder levels shared in all: D, or 3 with level 2
+    int h2 = 0, w2 = 0;      // P2 of a full band
+    int win2[2] = {0, 0};    // [lo, hi) of the CAT2 skip pixels the decoder reads
+    size_t l2_band_bytes = 0, l2_row_bytes = 0, l2_col_bytes = 0, l2_corner_bytes = 0, l2_wino_bytes = 0;
 };
 inline int band_hx(const FramePlan &fp, int nrows, int cs) { return (nrows - 1) * fp.S + cs + 4; }
 // the edge images of a band of nrows tile rows (planes sized for a full band; P2 in the band's slots) and the corner patches of a
@@ -601,7 +606,131 @@ inline Plan corner_plan(int f, int dt, int ntiles, int cap, char *base) {
     return make_enc_plan(f, kStrip, kStrip, 4 * ntiles, kStrip, kStrip, 4 * cap, base, dt);
 }
 
+// ---------------------------------------------------------------- level 2 of the shared encoder
+// With 8 | S a tile origin is a whole P3 pixel too, and level 2 (convs3.0, convs3.2, the third pool: steps [kSharedSteps, kLevel2End))
+// is shared the same way one level down:
+//   * the band runs the three steps once on its P2.  A tile's reflection reaches only lines 0 and n - 1 of every level-2 tensor;
+//   * tconvs2.0 leaves lines 0 and n - 1 of the CAT2 skip unread (region plan) and reads it where the band wrote it;
+//   * a tile's P3 is its window of the band's P3, and its border lines come from kStrip2-line images at P2 resolution (6 P2 rows
+//     yield one P3 row): the tile row's P2 edge line, which the level-0/1 row-edge images already produce, next to the five clean
+//     band rows below (above) it -- two 6 x w2 images per tile row of a band, image side * nrows + row.  Likewise two h2 x 6 images
+//     per tile column, image side * cols + column.  The four P3 corner pixels come from the 6 x 6 corner patches of the tile's own
+//     assembled P2, image k * ntiles + t of a launch (k = 2 * bottom + right);
+//   * the per-tile stack starts at convs4.0.
+// Level 3 stays per tile: its border images would be one F(6x6) tile row of a 30-pixel tile side.
+constexpr int kLevel2End = 9;
+constexpr int kStrip2 = 6;
+
+// extent of level-2 buffer b (P2 ... P3) for a P2 of extent x
+inline int l2_extent(int x, int b) {
+    switch (b) {
+        case P2: return x;
+        case A3: return x - 2;
+        case CAT2: return x - 4;
+        default: return (x - 4) / 2;   // P3
+    }
+}
+// (P2) A3 CAT2 P3 for B images with a P2 of h2 x w2; planes sized for cap images of hcap x wcap.  The tensors the per-tile launches
+// read -- CAT2 and P3 from `slotted` on (a band: both, its edge images: P3) -- hold `slots` times the capacity (make_enc_plan).
+// own_p2 = false: P2 is the caller's (a band's, from its level-0/1 plan)
+Plan make_l2_plan(int f, int h2, int w2, int B, int hcap, int wcap, int cap, char *base, int dt, int slots = 1, Buf slotted = CAT2,
+                  bool own_p2 = true) {
+    Plan p = {};
+    size_t off = 0;
+    auto add = [&](Buf id, int ch, int pad) {
+        QpBuf &q = p.buf[id];
+        q.planes = (ch + nd_cpp(dt) - 1) / nd_cpp(dt);
+        q.dt = dt;
+        q.B = B;
+        q.Hb = l2_extent(h2, id) + 2 * pad;
+        q.Wb = l2_extent(w2, id) + 2 * pad;
+        q.pad = pad;
+        q.pstride = (long)cap * (l2_extent(hcap, id) + 2 * pad) * (l2_extent(wcap, id) + 2 * pad);
+        if ((id == CAT2 || id == P3) && id >= slotted) q.pstride *= slots;
+        q.base = (float *)(base + off);
+        off += ((size_t)q.planes * q.pstride + nd_buf_slack(l2_extent(wcap, id) + 2 * pad)) * 16;
+        off = (off + 255) & ~(size_t)255;
+    };
+    if (own_p2) add(P2, 2 * f, 0);
+    add(A3, 4 * f, 0);
+    add(CAT2, 8 * f, 2);
+    add(P3, 4 * f, 0);
+    p.split = nullptr;
+    p.wino = nullptr;
+    p.bytes = off;
+    return p;
+}
+inline Plan l2_slot(Plan p, int slot, int slots, Buf slotted = CAT2) {
+    for (Buf id : {CAT2, P3})
+        if (id >= slotted) p.buf[id].base += (size_t)slot * slot_elems(p.buf[id], slots) * 4;
+    return p;
+}
+
 extern "C" int nd_tile_grid(int W, int H, int cs, int ucs, int ol, int *cols, int *rows, int *pad);
+
+inline int band_h2(const FramePlan &fp, int nrows, int cs) { return enc_extent(band_hx(fp, nrows, cs), P2); }
+inline Plan l2_band_plan(const FramePlan &fp, int f, int dt, int nrows, int cs, char *base) {
+    return make_l2_plan(f, band_h2(fp, nrows, cs), fp.w2, 1, fp.h2, fp.w2, 1, base, dt, fp.slots, CAT2, false);
+}
+inline Plan l2_row_plan(const FramePlan &fp, int f, int dt, int nrows, char *base) {
+    return make_l2_plan(f, kStrip2, fp.w2, 2 * nrows, kStrip2, fp.w2, 2 * fp.R, base, dt, fp.slots, P3);
+}
+inline Plan l2_col_plan(const FramePlan &fp, int f, int dt, int nrows, int cs, char *base) {
+    return make_l2_plan(f, band_h2(fp, nrows, cs), kStrip2, 2 * fp.cols, fp.h2, kStrip2, 2 * fp.cols, base, dt, fp.slots, P3);
+}
+inline Plan l2_corner_plan(int f, int dt, int ntiles, int cap, char *base) {
+    return make_l2_plan(f, kStrip2, kStrip2, 4 * ntiles, kStrip2, kStrip2, 4 * cap, base, dt);
+}
+
+// Level 2 on top of a level-0/1 plan (fp->D == 2): shared when 8 | S, the decoder leaves lines 0 and n - 1 of the CAT2 skip unread,
+// and every level-2 step of the band, the two line image shapes and the corner patches runs in a kernel that takes any image
+// shape and pools in its epilogue (conv_w2d, three-pass F(6x6)).  rois: the region plan of a tile
+inline void frame_plan_level2(int f, int dt, int flags, int cs, int batch, const BlobLayout &bl, const Roi *rois, FramePlan *fp) {
+    fp->levels = fp->D;
+    if ((flags & ND_FLAG_TILE_LEVEL2) || fp->S % 8) return;
+    const int n2 = enc_extent(cs + 4, P2), n = l2_extent(n2, CAT2);
+    if (n2 < kStrip2 + 2 || l2_extent(n2, P3) < 3) return;
+    bool reads_cat2 = false;
+    for (int i = kLevel2End; i < kNumSteps; ++i) {
+        const Step &st = kSteps[i];
+        if (st.layer < 0 || st.src != CAT2 || kLayers[st.layer].kind != ND_CONVT3) continue;
+        if (rois[i].rows <= 0 || rois[i].r0 != rois[i].c0 || rois[i].rows != rois[i].cols) return;
+        fp->win2[0] = rois[i].r0 - 2 < 0 ? 0 : rois[i].r0 - 2;
+        fp->win2[1] = rois[i].r0 + rois[i].rows > n ? n : rois[i].r0 + rois[i].rows;
+        if (fp->win2[0] < 1 || fp->win2[1] > n - 1 || fp->win2[1] <= fp->win2[0]) return;
+        reads_cat2 = true;
+    }
+    if (!reads_cat2) return;
+    fp->h2 = enc_extent(fp->hx, P2);
+    fp->w2 = enc_extent(fp->wx, P2);
+    Plan plans[4] = {l2_band_plan(*fp, f, dt, fp->R, cs, nullptr), l2_row_plan(*fp, f, dt, fp->R, nullptr),
+                     l2_col_plan(*fp, f, dt, fp->R, cs, nullptr), l2_corner_plan(f, dt, batch, batch, nullptr)};
+    plans[0].buf[P2] = make_enc_plan(f, fp->hx, fp->wx, 1, fp->hx, fp->wx, 1, nullptr, dt).buf[P2];
+    size_t wino = 0;
+    for (const Plan &pp : plans)
+        for (int i = kSharedSteps; i < kLevel2End; ++i) {
+            const Step &st = kSteps[i];
+            if (st.layer < 0) continue;
+            const LayerSpec &l = kLayers[st.layer];
+            const Form form = step_form(st, f, dt, flags, pp, bl);
+            if (form == FORM_WINO3P) {
+                // (the tile workspace's scratch is sized for the tiles of a launch: level 2 carries its own, for any batch)
+                QpBuf v = pp.buf[st.src];
+                v.B = v.B < kWinoChunk ? v.B : kWinoChunk;
+                const size_t need = nd_wino_scratch_bytes(kWinoTile, v, lcin(l, f), lcout(l, f));
+                wino = need > wino ? need : wino;
+            } else if (form != FORM_W1D4 || !nd_f43_w2d(pp.buf[st.src], lcout(l, f), false, flags)) {
+                return;
+            }
+        }
+    fp->l2_band_bytes = plans[0].bytes;
+    fp->l2_row_bytes = plans[1].bytes;
+    fp->l2_col_bytes = plans[2].bytes;
+    fp->l2_corner_bytes = plans[3].bytes;
+    fp->l2_wino_bytes = (wino + 255) & ~(size_t)255;
+    fp->bytes += fp->origin_bytes + fp->l2_band_bytes + fp->l2_row_bytes + fp->l2_col_bytes + fp->l2_corner_bytes + fp->l2_wino_bytes;
+    fp->levels = 3;
+}
 
 // the band plan: a function of the frame geometry, the dtype and the flags (batch only sizes the corner buffers and the tables)
 int frame_plan(int f, int dt, int flags, int W, int H, int cs, int ucs, int ol, int batch, FramePlan *fp) {
@@ -670,6 +799,7 @@ int frame_plan(int f, int dt, int flags, int W, int H, int cs, int ucs, int ol, 
     fp->origin_bytes = ((size_t)batch * sizeof(int) + 255) & ~(size_t)255;
     fp->bytes = fp->band_bytes + fp->row_edge_bytes + fp->col_edge_bytes + fp->corner_bytes + 2 * fp->origin_bytes;
     fp->D = 2;
+    frame_plan_level2(f, dt, flags, cs, batch, bl, rois, fp);
     return ND_OK;
 }
 

@@ -132,12 +132,15 @@ class UtNet(nn.Module):
     #   fused_pool = False -> A/B switch: every MaxPool2d(2) as its own kernel instead of from the producing layer's epilogue (same values)
     #   share_encoder = False -> A/B switch: the fused frame loop runs every tile's whole encoder instead of the first two levels
     #                            once per band of tile rows (fp32 useful-region mode; same canvas up to fp32 re-association)
+    #   share_level2 = False -> A/B switch: the shared loop keeps the third encoder level (convs3.x) per tile where it would run it
+    #                           once per band too (nd_utnet_frame_levels: 3; same canvas up to fp32 re-association)
     split_k = True
     winograd = True
     w1d_regs = False
     useful_only = True
     fused_pool = True
     share_encoder = True
+    share_level2 = True
 
     def __init__(self, funit=64, activation='PReLU', compute_dtype='f32'):
         super().__init__()
@@ -192,6 +195,11 @@ class UtNet(nn.Module):
         return ((0 if self.split_k else _lib.FLAG_NO_SPLITK) | (0 if self.winograd else _lib.FLAG_DIRECT_CONV) |
                 (_lib.FLAG_W1D_REGS if self.w1d_regs else 0) | (0 if self.useful_only else _lib.FLAG_FULL_TILES) |
                 (0 if self.fused_pool else _lib.FLAG_UNFUSED_POOL) | (0 if self.share_encoder else _lib.FLAG_TILE_ENCODER))
+
+    @property
+    def frame_flags(self):
+        """flags of the frame-loop entry points (nd_utnet_frame_*, nd_utnet_denoise_frame): they alone take FLAG_TILE_LEVEL2."""
+        return self.flags | (0 if self.share_level2 else _lib.FLAG_TILE_LEVEL2)
 
     # ------------------------------------------------------------------ weights
     def _weights_key(self, device):
@@ -257,7 +265,7 @@ class UtNet(nn.Module):
         """Band and strip buffers of the shared encoder for one frame geometry (nd_utnet_frame_workspace_bytes; zero-filled once,
         then cached with the activation workspaces), or None where the frame loop runs every tile's whole encoder."""
         lib = _lib.load()
-        nbytes = lib.nd_utnet_frame_workspace_bytes(self.funit, self._dt, self.flags, width, height, cs, ucs, ol, batch)
+        nbytes = lib.nd_utnet_frame_workspace_bytes(self.funit, self._dt, self.frame_flags, width, height, cs, ucs, ol, batch)
         if nbytes == 0:
             return None
         key = (str(device), "frame", nbytes)

@@ -64,7 +64,7 @@ def denoise_frame(model, img, cs, ucs, ol, batch=16, tile_range=None, canvas=Non
             ws = model.workspace(cs, batch, img.device)
             fws = model.frame_workspace(width, height, cs, ucs, ol, batch, img.device)
             cb = _lib.PROGRESS_FN(lambda _ctx, n, t0, cnt: progress(n, t0, cnt)) if progress is not None else _lib.PROGRESS_FN()
-            _lib.check(lib.nd_utnet_denoise_frame(model.funit, _lib.ACT[model.activation], _lib.DTYPE[model.compute_dtype], model.flags,
+            _lib.check(lib.nd_utnet_denoise_frame(model.funit, _lib.ACT[model.activation], _lib.DTYPE[model.compute_dtype], model.frame_flags,
                                                   blob.data_ptr(), img.data_ptr(), canvas.data_ptr(), width, height, cs, ucs, ol,
                                                   begin, end - begin, batch, ws.data_ptr(), ws.numel(),
                                                   fws.data_ptr() if fws is not None else None, fws.numel() if fws is not None else 0,

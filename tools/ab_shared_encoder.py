@@ -1,6 +1,8 @@
 """A/B of the fused frame loop: per-tile encoder (UtNet.share_encoder = False) against the shared encoder, alternating.
 
-    python3 tools/ab_shared_encoder.py [--rounds 3] [--steps 5] [--only tile|shared]
+    python3 tools/ab_shared_encoder.py [--rounds 3] [--steps 5] [--only tile|level2|shared]
+
+--only level2 (or --level2: a third mode between the two) shares levels 0-1 and keeps level 2 per tile (UtNet.share_level2 = False).
 
 bench.py's flagship workload (fp32 G24: 6000x4000, cs 264 / ucs 200 / ol 64, UtNet(64), 256 tiles per launch), timed with CUDA
 events around `steps` whole frames after one warm-up frame per mode.  Prints one JSON line per round and a summary; --only runs
@@ -22,7 +24,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256)
-    ap.add_argument("--only", choices=("tile", "shared"))
+    ap.add_argument("--only", choices=("tile", "level2", "shared"))
+    ap.add_argument("--level2", action="store_true")
     a = ap.parse_args()
     W, H, cs, ucs, ol = 6000, 4000, 264, 200, 64
     dev = torch.device("cuda:0")
@@ -31,10 +34,11 @@ def main():
     net = net.eval().to(dev)
     img = torch.from_numpy(synth.make_frame(W, H, seed=24)).to(dev)
     canvas = torch.zeros_like(img)
-    modes = [a.only] if a.only else ["tile", "shared"]
+    modes = [a.only] if a.only else (["tile", "level2", "shared"] if a.level2 else ["tile", "shared"])
 
     def run(mode, steps):
-        net.share_encoder = mode == "shared"
+        net.share_encoder = mode != "tile"
+        net.share_level2 = mode != "level2"
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(steps):
@@ -53,7 +57,7 @@ def main():
             res[m].append(ms)
             print(json.dumps({"round": r, "mode": m, "ms_per_frame": round(ms, 2), "mp_per_s": round(W * H / ms / 1e3, 2)}), flush=True)
     summary = {m: {"ms_per_frame": [round(x, 2) for x in v], "best_mp_per_s": round(W * H / min(v) / 1e3, 2)} for m, v in res.items()}
-    if len(modes) == 2:
+    if "tile" in res and "shared" in res:
         summary["speedup_median"] = round(sorted(res["tile"])[len(res["tile"]) // 2] / sorted(res["shared"])[len(res["shared"]) // 2], 3)
     print(json.dumps(summary))
 
