@@ -70,13 +70,16 @@ typedef enum nd_flags {
     ND_FLAG_TILE_LEVEL2 = 64,  /* A/B switch: nd_utnet_denoise_frame keeps the third encoder level per tile where it would share it
                                  too (nd_utnet_frame_levels: 3).  Taken by the frame-loop entry points only (nd_utnet_frame_*,
                                  nd_utnet_denoise_frame); an unknown bit everywhere else                                          */
+    ND_FLAG_FIND_NOISE = 128,  /* nd_unet_denoise_frame only (an unknown bit everywhere else): UNet(find_noise=True), ThirdPartyNets.py:
+                                 167-168 -- a tile contributes its input minus the network output                                   */
     ND_FLAG_FULL_TILES = 8    /* nd_utnet_denoise_tiles / nd_utnet_profile_stack: compute every layer on the whole tile, as
                                  UtNet.forward does.  Default there: the last decoder levels compute only the pixels that the
                                  useful crop [pad, cs - pad) of a tile can reach (denoise_image.py:249-258 discards the rest of
-                                 the network output before the canvas +=) -- same canvas, 19 % less work at cs 264 / ucs 200    */
+                                 the network output before the canvas +=) -- same canvas, 19 % less work at cs 264 / ucs 200.
+                                 nd_unet_denoise_frame: the same switch for the UNet decoder (nd_unet_useful_region)             */
 } nd_flags;
 
-int nd_version(void);   /* 108 = this header */
+int nd_version(void);   /* 109 = this header */
 const char *nd_last_error(void);
 
 /* ---------------------------------------------------------------- tile geometry (host, pure integer)
@@ -217,6 +220,36 @@ size_t nd_unet_workspace_bytes(int h, int w, int batch, int dtype);
 int nd_unet_workspace_init(void *workspace, size_t workspace_bytes, int h, int w, int batch, int dtype, void *stream);
 int nd_unet_forward(int dtype, const void *packed_dev, const float *x_nchw, float *y_nchw, int batch, int h, int w,
                     void *workspace, size_t workspace_bytes, void *stream);
+
+/* The same blob (bit for bit) built in HBM from tensors that already live there: eval-mode BatchNorm is folded by a small kernel
+ * (per-channel scale and bias, each operation rounded once, in the host packer's order) and the scale is multiplied in while the
+ * fragments are written.  No host copy of the weights; stream-ordered; allocates nothing. */
+int nd_unet_pack_weights_device(int dtype, const float *const *dev_tensors, int n_tensors, void *packed_dev, size_t packed_bytes,
+                                void *stream);
+
+/* Host-only: the step list of the UNet stack (26 steps: 22 conv launches and 4 pools, between the input pack and the final 1x1).
+ * nd_unet_step_name: module path of the step's layer ("inc.conv.conv.0", "up1.up", ...), "pool" for pools.
+ * nd_unet_useful_region: region {r0, c0, rows, cols} of step `step` that nd_unet_denoise_frame computes when the centre
+ * [crop, cs - crop) of a tile is kept -- output grid of a 3x3 layer, input grid of a 2x2 stride-2 transpose; zeros: the whole tensor
+ * (always for the encoder and the pools: their outputs are skips).  Walking the decoder backwards from the kept centre, per axis: a
+ * 3x3 layer with outputs [lo, hi) reads inputs [max(lo - 1, 0), min(hi + 1, size)), a transpose makes them from input rows
+ * [lo >> 1, min((hi + 1) >> 1, size_in)).  Returns the number of restricted steps (>= 0) or a negative nd_status. */
+int nd_unet_num_steps(void);
+const char *nd_unet_step_name(int i);
+int nd_unet_useful_region(int cs, int crop, int step, int *rect);
+
+/* The hot loop of denoise_image.py:240-267 with UNet for tiles [tile_begin, tile_begin + tile_count) of one frame, in ascending
+ * launches of at most `batch` tiles: gather (+symmetric mirror) straight into the first layer's input, the conv stack, then final
+ * 1x1 + Sigmoid + useful crop + seamless edges + canvas += in one kernel; no NCHW tile batch is written.  The decoder computes only
+ * what the kept centre of a tile depends on (nd_unet_useful_region; all layers whole if a region fits no workgroup shape of the
+ * direct kernel) unless ND_FLAG_FULL_TILES is set: same canvas bit for bit under ND_FLAG_NO_SPLITK, else up to fp32
+ * re-association of the split-K tail.  workspace: nd_unet_workspace_bytes(cs, cs, batch, ND_F32), initialised by
+ * nd_unet_workspace_init.  dtype: ND_F32 only.  flags: ND_FLAG_NO_SPLITK, ND_FLAG_FULL_TILES and ND_FLAG_FIND_NOISE switch something
+ * here; the other known bits of nd_flags (Winograd forms, fused pools, shared encoder: this stack has none of them) are accepted and
+ * ignored; unknown bits are an error.  progress: as in nd_utnet_denoise_frame. */
+int nd_unet_denoise_frame(int dtype, int flags, const void *packed_dev, const float *img_chw, float *canvas_chw, int width,
+                          int height, int cs, int ucs, int ol, int tile_begin, int tile_count, int batch, void *workspace,
+                          size_t workspace_bytes, void *stream, nd_progress_fn progress, void *progress_ctx);
 
 /* FLOP per tile by the reference's own accounting, for roofline reports. */
 double nd_utnet_flops(int funit, int cs);

@@ -15,6 +15,7 @@ ACT = {"none": 0, "PReLU": 1, "ELU": 2, "Hardswish": 3}
 KIND = {"conv3": 0, "convT3": 1, "convT2s2": 2, "conv1": 3, "conv2s2": 4}
 # nd_flags (include/nind_hip.h): per-call arithmetic switches
 FLAG_NO_SPLITK, FLAG_DIRECT_CONV, FLAG_W1D_REGS, FLAG_FULL_TILES, FLAG_UNFUSED_POOL, FLAG_TILE_ENCODER, FLAG_TILE_LEVEL2 = 1, 2, 4, 8, 16, 32, 64
+FLAG_FIND_NOISE = 128   # nd_unet_denoise_frame only
 # nd_progress_fn: (ctx, launch index, first tile, tile count)
 PROGRESS_FN = ctypes.CFUNCTYPE(None, c_void_p, c_int, c_int, c_int)
 
@@ -62,6 +63,11 @@ _SIGNATURES = {
     "nd_unet_workspace_bytes": (c_size_t, [c_int] * 4),
     "nd_unet_workspace_init": (c_int, [c_void_p, c_size_t] + [c_int] * 4 + [c_void_p]),
     "nd_unet_forward": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "nd_unet_pack_weights_device": (c_int, [c_int, POINTER(c_void_p), c_int, c_void_p, c_size_t, c_void_p]),
+    "nd_unet_num_steps": (c_int, []),
+    "nd_unet_step_name": (c_char_p, [c_int]),
+    "nd_unet_useful_region": (c_int, [c_int, c_int, c_int, POINTER(c_int)]),
+    "nd_unet_denoise_frame": (c_int, [c_int, c_int] + [c_void_p] * 3 + [c_int] * 8 + [c_void_p, c_size_t, c_void_p, PROGRESS_FN, c_void_p]),
     "nd_utnet_flops": (c_double, [c_int, c_int]),
     "nd_utnet_profile_stack": (c_int, [c_int] * 4 + [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_int]),
     "nd_utnet_step_name": (c_char_p, [c_int]),

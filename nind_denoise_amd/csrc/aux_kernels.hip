@@ -117,16 +117,20 @@ extern "C" int nd_tile_gather(const float *img, int W, int H, int cs, int ucs, i
     return ND_OK;
 }
 
-// fused: gather(+symmetric mirror) -> ReflectionPad2d(2) -> quad-planar first-layer input (plane 0 = r,g,b,0)
+// fused: gather(+symmetric mirror) -> quad-planar first-layer input (plane 0 = r,g,b,0) of Sb = cs + 2 * border lines.  reflect: every
+// line, the border = ReflectionPad2d(border) of the tile (UtNet.py:27,98); else the cs interior lines only (UNet: the border is the
+// zero padding of Conv2d(3, padding=1) and stays untouched)
 template <int DT>
-__global__ void k_gather_pack(const float *__restrict__ img, TileGeo g, int tile_begin, typename Elem<DT>::vec *__restrict__ dst, int Sb) {
-    const int u = blockIdx.x * blockDim.x + threadIdx.x;  // column in the reflect-padded tile
+__global__ void k_gather_pack(const float *__restrict__ img, TileGeo g, int tile_begin, typename Elem<DT>::vec *__restrict__ dst, int Sb,
+                              int border, int reflect) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;  // column in the bordered tile (reflect) or in the tile
     const int v = blockIdx.y;
     const int t = blockIdx.z;
-    if (u >= Sb) return;
+    if (u >= (reflect ? Sb : g.cs)) return;
     const int i = tile_begin + t;
     const int yi = i / g.cols, xi = i - yi * g.cols;
-    const int qx = reflect_nr(u - 2, g.cs), qy = reflect_nr(v - 2, g.cs);
+    const int qx = reflect ? reflect_nr(u - border, g.cs) : u, qy = reflect ? reflect_nr(v - border, g.cs) : v;
+    const int du = reflect ? u : u + border, dv = reflect ? v : v + border;
     const int sx = mirror_sym(xi * g.stride - g.pad + qx, g.W);
     const int sy = mirror_sym(yi * g.stride - g.pad + qy, g.H);
     const size_t plane = (size_t)g.W * g.H;
@@ -135,19 +139,23 @@ __global__ void k_gather_pack(const float *__restrict__ img, TileGeo g, int tile
     o[0] = (typename Elem<DT>::scalar)s[0];
     o[1] = (typename Elem<DT>::scalar)s[plane];
     o[2] = (typename Elem<DT>::scalar)s[2 * plane];
-    dst[((size_t)t * Sb + v) * Sb + u] = o;
+    dst[((size_t)t * Sb + dv) * Sb + du] = o;
 }
 
 int nd_launch_gather_pack(const float *img, int W, int H, int cs, int ucs, int ol, int tile_begin, int tile_count,
-                          const QpBuf &dst, hipStream_t s) {
+                          const QpBuf &dst, hipStream_t s, int border, bool reflect) {
     TileGeo g;
     ND_TRY(make_geo(W, H, cs, ucs, ol, &g));
     if (tile_begin < 0 || tile_count <= 0 || tile_begin + tile_count > g.cols * g.rows || tile_count > dst.B)
         ND_FAIL(ND_EINVAL, "gather_pack: bad tile range [%d,+%d)", tile_begin, tile_count);
-    if (dst.Hb != cs + 4 || dst.Wb != cs + 4 || dst.pad != 0) ND_FAIL(ND_EINVAL, "gather_pack: destination is not (cs+4)^2");
-    dim3 grid((cs + 4 + 255) / 256, cs + 4, tile_count);
+    const int Sb = cs + 2 * border;
+    // (a reflected border is part of the buffer's pixels: pad 0; a zero border is the buffer's own)
+    if (border < 0 || border >= cs || dst.Hb != Sb || dst.Wb != Sb || dst.pad != (reflect ? 0 : border) || dst.used() > dst.np())
+        ND_FAIL(ND_EINVAL, "gather_pack: destination is not (cs+%d)^2", 2 * border);
+    const int n = reflect ? Sb : cs;
+    dim3 grid((n + 255) / 256, n, tile_count);
     ND_DISPATCH_DT(dst.dt, hipLaunchKernelGGL(k_gather_pack<DT>, grid, dim3(256), 0, s, img, g, tile_begin,
-                                              (typename Elem<DT>::vec *)dst.base, cs + 4));
+                                              (typename Elem<DT>::vec *)dst.base, Sb, border, reflect ? 1 : 0));
     ND_HIP(hipGetLastError());
     return ND_OK;
 }
@@ -588,21 +596,38 @@ int nd_launch_final1x1(const QpBuf &src, int cin, const float *w, const float *b
     return ND_OK;
 }
 
-// fused: final 1x1 + crop + useful crop + seamless edges + canvas += (no NCHW tile batch in HBM)
+// fused: final 1x1 (+ Sigmoid) + crop + useful crop + seamless edges + canvas += (no NCHW tile batch in HBM).  noise_img: the
+// contribution of a tile is frame pixel - result (UNet's find_noise; a useful pixel of a tile is the frame's pixel (Y, X) itself)
 template <int DT>
 __global__ void k_final1x1_stitch(const typename Elem<DT>::vec *__restrict__ src, long np, int Hb, int Wb, int planes, int cin,
                                   const float *__restrict__ w, const float *__restrict__ bias, int crop,
-                                  float *__restrict__ canvas, TileGeo g, int tile_begin, int tile_count, int y_first) {
+                                  float *__restrict__ canvas, TileGeo g, int tile_begin, int tile_count, int y_first, int sigmoid,
+                                  const float *__restrict__ noise_img) {
     const int X = blockIdx.x * blockDim.x + threadIdx.x;
     const int Y = y_first + blockIdx.y;
     if (X >= g.W || Y >= g.H) return;
     const size_t plane = (size_t)g.W * g.H;
     float *c = canvas + (size_t)Y * g.W + X;
     float v0 = c[0], v1 = c[plane], v2 = c[2 * plane];
+    float n0 = 0.f, n1 = 0.f, n2 = 0.f;
+    if (noise_img) {
+        const float *n = noise_img + (size_t)Y * g.W + X;
+        n0 = n[0]; n1 = n[plane]; n2 = n[2 * plane];
+    }
     bool any = false;
     for_each_cover(g, X, Y, tile_begin, tile_count, [&](int t, int iy, int ix, float f) {
         float o0 = bias[0], o1 = bias[1], o2 = bias[2];
         dot3<DT>(src + ((size_t)t * Hb + iy + crop) * Wb + ix + crop, np, planes, w, cin, o0, o1, o2);
+        if (sigmoid) {   // UNet head (ThirdPartyNets.py:169), as k_final1x1
+            o0 = 1.f / (1.f + expf(-o0));
+            o1 = 1.f / (1.f + expf(-o1));
+            o2 = 1.f / (1.f + expf(-o2));
+        }
+        if (noise_img) {   // ThirdPartyNets.py:168
+            o0 = n0 - o0;
+            o1 = n1 - o1;
+            o2 = n2 - o2;
+        }
         v0 += o0 * f;
         v1 += o1 * f;
         v2 += o2 * f;
@@ -616,7 +641,8 @@ __global__ void k_final1x1_stitch(const typename Elem<DT>::vec *__restrict__ src
 }
 
 int nd_launch_final1x1_stitch(const QpBuf &src, int cin, const float *w, const float *bias, int crop, float *canvas,
-                              int W, int H, int cs, int ucs, int ol, int tile_begin, int tile_count, hipStream_t s) {
+                              int W, int H, int cs, int ucs, int ol, int tile_begin, int tile_count, hipStream_t s, int sigmoid,
+                              const float *noise_img) {
     TileGeo g;
     ND_TRY(make_geo(W, H, cs, ucs, ol, &g));
     if (src.pad != 0 || src.Hb != cs + 2 * crop || src.Wb != cs + 2 * crop || tile_count > src.B)
@@ -628,7 +654,7 @@ int nd_launch_final1x1_stitch(const QpBuf &src, int cin, const float *w, const f
     const int n = nd_cpp(src.dt);
     ND_DISPATCH_DT(src.dt, hipLaunchKernelGGL(k_final1x1_stitch<DT>, grid, dim3(256), 0, s, (const typename Elem<DT>::vec *)src.base,
                                               src.np(), src.Hb, src.Wb, (cin + n - 1) / n, cin, w, bias, crop, canvas, g,
-                                              tile_begin, tile_count, yf));
+                                              tile_begin, tile_count, yf, sigmoid, noise_img));
     ND_HIP(hipGetLastError());
     return ND_OK;
 }

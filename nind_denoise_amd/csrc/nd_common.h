@@ -142,10 +142,10 @@ int nd_check_int32(const char *who, const QpBuf &in);
 int nd_check_roi(const char *who, const ConvDesc &d, int Hv, int Wv, bool refused, const char *why);
 // the arithmetic switches every flags-taking entry point accepts (include/nind_hip.h: nd_flags); unknown bits are an error.
 // frame_loop: the frame-loop entry points (nd_utnet_frame_*, nd_utnet_denoise_frame) also take ND_FLAG_TILE_LEVEL2, which means
-// nothing anywhere else
-static inline int nd_check_flags(int flags, bool frame_loop = false) {
+// nothing anywhere else; unet_frame: nd_unet_denoise_frame also takes ND_FLAG_FIND_NOISE
+static inline int nd_check_flags(int flags, bool frame_loop = false, bool unet_frame = false) {
     const int known = ND_FLAG_NO_SPLITK | ND_FLAG_DIRECT_CONV | ND_FLAG_W1D_REGS | ND_FLAG_FULL_TILES | ND_FLAG_UNFUSED_POOL |
-                      ND_FLAG_TILE_ENCODER | (frame_loop ? ND_FLAG_TILE_LEVEL2 : 0);
+                      ND_FLAG_TILE_ENCODER | (frame_loop ? ND_FLAG_TILE_LEVEL2 : 0) | (unet_frame ? ND_FLAG_FIND_NOISE : 0);
     if (flags & ~known) ND_FAIL(ND_EINVAL, "unknown flag bits 0x%x", flags);
     return ND_OK;
 }
@@ -191,7 +191,13 @@ static inline size_t nd_packed_floats(int kind, int cin, int cout, int dt = ND_F
 void nd_pack_layer(int kind, int cin, int cout, int dt, const float *w, const float *bias, float *packed);
 
 // device-side packers (pack_dev.hip): the same layouts from weights in HBM (direct form: any storage type; Winograd forms: fp32)
-int nd_pack_layer_device(int kind, int cin, int cout, int dt, const float *w, const float *bias, float *packed, hipStream_t s);
+// scale (nullable, HBM): one factor per output channel, multiplied into its weights as they are packed
+int nd_pack_layer_device(int kind, int cin, int cout, int dt, const float *w, const float *bias, float *packed, hipStream_t s,
+                         const float *scale = nullptr);
+// eval-mode BatchNorm2d folded into the conv before it: scale[co] = g / sqrt(rv + 1e-5), fbias[co] = (b - rm) * scale + be, rounded
+// operation by operation as the host packer of unet.hip does
+int nd_launch_bn_fold(int cout, const float *b, const float *g, const float *be, const float *rm, const float *rv, float *scale,
+                      float *fbias, hipStream_t s);
 int nd_pack_w1d_device(int T, int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s);
 int nd_pack_wino_device(int T, int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s);
 
@@ -202,11 +208,15 @@ int nd_launch_reflect_pack(const float *x_nchw, int B, int H, int W, const QpBuf
 int nd_launch_maxpool2(const QpBuf &src, int src_plane0, int planes, const QpBuf &dst, hipStream_t s);
 int nd_launch_final1x1(const QpBuf &src, int cin, const float *w, const float *bias, int crop, float *y_nchw, int H,
                        int W, hipStream_t s, int sigmoid = 0);
+// sigmoid: the UNet head; noise_img (nullable): the frame -- a tile then contributes frame pixel - result (UNet's find_noise: the
+// useful part of a tile is never mirrored, so its input pixel there is the frame pixel)
 int nd_launch_final1x1_stitch(const QpBuf &src, int cin, const float *w, const float *bias, int crop, float *canvas,
                               int width, int height, int cs, int ucs, int ol, int tile_begin, int tile_count,
-                              hipStream_t s);
+                              hipStream_t s, int sigmoid = 0, const float *noise_img = nullptr);
+// gather (+symmetric mirror) of tiles into plane 0 of a first-layer input of (cs + 2 * border)^2.  reflect: the border is
+// ReflectionPad2d(border) of the tile (UtNet); else only the interior is written and the border stays as it is (UNet: zero)
 int nd_launch_gather_pack(const float *img, int width, int height, int cs, int ucs, int ol, int tile_begin,
-                          int tile_count, const QpBuf &dst, hipStream_t s);
+                          int tile_count, const QpBuf &dst, hipStream_t s, int border = 2, bool reflect = true);
 // shared encoder of the fused loop (fp32): band of tile rows from band_row0 as one first-layer input image (B = 1, no reflect
 // border); the images that yield P2's border lines (k_gather_edges: two row edges per tile row of a band, two column edges per
 // tile column of a band, four corners per tile of a launch); per-tile copy of a window of a band or edge tensor into a tile buffer

@@ -23,10 +23,11 @@ __device__ __forceinline__ unsigned f32_to_f16_rne(float f) {
 }
 
 // direct form (pack.hip: nd_pack_layer): nw 4-byte units of packed weights followed by nb biases.  fp32: one thread per value;
-// 16-bit: one thread per 16-byte lane element (its 8 channels, one vector store)
+// 16-bit: one thread per 16-byte lane element (its 8 channels, one vector store).  scale (nullable): one factor per output channel,
+// applied to every weight of that channel as it is written (the folded BatchNorm of UNet; `bias` is then the folded bias)
 template <int DT>
 __global__ void k_pack_dev(int kind, int cin, int cout, int M, int KB, int taps, const float *__restrict__ w,
-                           const float *__restrict__ bias, float *__restrict__ packed, long nw, int nb) {
+                           const float *__restrict__ bias, float *__restrict__ packed, long nw, int nb, const float *__restrict__ scale) {
     constexpr int CPL = DT == ND_F32 ? 4 : 8;   // channels per lane of a piece
     constexpr int PER = DT == ND_F32 ? 1 : 8;   // ... and per thread
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -55,6 +56,7 @@ __global__ void k_pack_dev(int kind, int cin, int cout, int M, int KB, int taps,
                     case ND_CONV2S2: v[s] = w[((long)m * cin + ci) * 4 + t]; break;
                     default: v[s] = w[(long)m * cin + ci]; break;
                 }
+                if (scale) v[s] = v[s] * scale[kind == ND_CONVT2S2 ? nd_up_row(m, cout, DT).co : m];   // one rounding, as the host's w * sc
             }
         }
         if constexpr (DT == ND_F32) {
@@ -69,6 +71,19 @@ __global__ void k_pack_dev(int kind, int cin, int cout, int M, int KB, int taps,
         const int m = (int)(idx - nu);
         packed[nw + m] = (m < M && bias) ? bias[kind == ND_CONVT2S2 ? nd_up_row(m, cout, DT).co : m] : 0.f;
     }
+}
+
+// eval-mode BatchNorm2d folded into the conv before it (unet.hip: nd_unet_pack_weights): scale = g / sqrt(rv + eps),
+// folded bias = (b - rm) * scale + be.  Every operation rounds once, in the host packer's order: no contraction into an FMA
+__global__ void k_bn_fold(int cout, const float *__restrict__ b, const float *__restrict__ g, const float *__restrict__ be,
+                          const float *__restrict__ rm, const float *__restrict__ rv, float *__restrict__ scale, float *__restrict__ fbias) {
+#pragma clang fp contract(off)
+    const int co = blockIdx.x * blockDim.x + threadIdx.x;
+    if (co >= cout) return;
+    const float sc = g[co] / sqrtf(rv[co] + 1e-5f);   // (correctly rounded division and square root: hipcc's default)
+    scale[co] = sc;
+    const float d = (b[co] - rm[co]) * sc;
+    fbias[co] = d + be[co];
 }
 
 // one row of G g for F(T,3): u[0 .. T+2)
@@ -168,7 +183,16 @@ __global__ void k_pack_wino_dev(int T, int kind, int cin, int cout, int KB, cons
 
 }  // namespace
 
-int nd_pack_layer_device(int kind, int cin, int cout, int dt, const float *w, const float *bias, float *packed, hipStream_t s) {
+int nd_launch_bn_fold(int cout, const float *b, const float *g, const float *be, const float *rm, const float *rv, float *scale,
+                      float *fbias, hipStream_t s) {
+    if (cout <= 0 || !b || !g || !be || !rm || !rv || !scale || !fbias) ND_FAIL(ND_EINVAL, "bn_fold: null tensor");
+    hipLaunchKernelGGL(k_bn_fold, dim3((cout + 255) / 256), dim3(256), 0, s, cout, b, g, be, rm, rv, scale, fbias);
+    ND_HIP(hipGetLastError());
+    return ND_OK;
+}
+
+int nd_pack_layer_device(int kind, int cin, int cout, int dt, const float *w, const float *bias, float *packed, hipStream_t s,
+                         const float *scale) {
     const int MT = nd_mtiles(kind, cout), KB = nd_kblocks(cin, dt), taps = nd_taps(kind);
     const int M = kind == ND_CONVT2S2 ? 4 * cout : cout;
     const long nw = (long)nd_bias_offset(kind, cin, cout, dt);
@@ -177,7 +201,7 @@ int nd_pack_layer_device(int kind, int cin, int cout, int dt, const float *w, co
     if (kind == ND_CONVT2S2 && cout % nd_cpp(dt)) ND_FAIL(ND_EINVAL, "device packing: 2x2 stride-2 transpose with cout=%d (multiple of %d)", cout, nd_cpp(dt));
     const auto k = dt == ND_F32 ? k_pack_dev<ND_F32> : dt == ND_BF16 ? k_pack_dev<ND_BF16> : k_pack_dev<ND_F16>;
     hipLaunchKernelGGL(k, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, kind, cin, cout, M, KB, taps, w, bias, packed, nw,
-                       MT * 32);
+                       MT * 32, scale);
     ND_HIP(hipGetLastError());
     return ND_OK;
 }

@@ -28,6 +28,11 @@ def _double_conv(in_ch, out_ch):
 
 
 class UNet(nn.Module):
+    # arithmetic switches of the frame loop (nd_unet_denoise_frame); class attributes so that a test or a benchmark can flip them
+    split_k = True          # False: ND_FLAG_NO_SPLITK (a tile's bits do not depend on the launch it shares)
+    useful_only = True      # False: ND_FLAG_FULL_TILES (every decoder layer on the whole tile)
+    pack_on_device = True   # False: fold BatchNorm and pack on the host (nd_unet_pack_weights), then upload
+
     def __init__(self, n_channels=3, n_classes=3, funit=64, find_noise=False, compute_dtype='f32'):
         super().__init__()
         if canonical_compute_dtype(compute_dtype) != 'f32':
@@ -55,17 +60,29 @@ class UNet(nn.Module):
         lib = _lib.load()
         sd = self.state_dict()
         n = lib.nd_unet_num_tensors()
-        host, ptrs = [], (ctypes.c_void_p * n)()
+        where = device if self.pack_on_device else "cpu"
+        keep, ptrs = [], (ctypes.c_void_p * n)()
         for i in range(n):
-            t = sd[lib.nd_unet_tensor_name(i).decode()].detach().to(device="cpu", dtype=torch.float32).contiguous()
-            host.append(t)
+            t = sd[lib.nd_unet_tensor_name(i).decode()].detach().to(device=where, dtype=torch.float32).contiguous()
+            keep.append(t)
             ptrs[i] = t.data_ptr()
         nbytes = lib.nd_unet_packed_bytes(_lib.ND_F32)
-        blob = torch.empty(nbytes // 4, dtype=torch.float32)
-        _lib.check(lib.nd_unet_pack_weights(_lib.ND_F32, ptrs, n, blob.data_ptr(), nbytes), "nd_unet_pack_weights")
-        dev_blob = blob.to(device)
+        if self.pack_on_device:
+            dev_blob = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+            with torch.cuda.device(device):
+                _lib.check(lib.nd_unet_pack_weights_device(_lib.ND_F32, ptrs, n, dev_blob.data_ptr(), nbytes, _lib.stream_ptr(device)),
+                           "nd_unet_pack_weights_device")
+                torch.cuda.current_stream(device).synchronize()     # `keep` may be freed after this
+        else:
+            blob = torch.empty(nbytes // 4, dtype=torch.float32)
+            _lib.check(lib.nd_unet_pack_weights(_lib.ND_F32, ptrs, n, blob.data_ptr(), nbytes), "nd_unet_pack_weights")
+            dev_blob = blob.to(device)
         self._packed = (key, dev_blob)
         return dev_blob
+
+    @property
+    def flags(self):
+        return (0 if self.split_k else _lib.FLAG_NO_SPLITK) | (0 if self.useful_only else _lib.FLAG_FULL_TILES)
 
     def workspace(self, h, w, batch, device):
         key = (str(device), h, w, batch)

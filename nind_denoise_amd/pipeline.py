@@ -3,12 +3,14 @@
 The frame stays in HBM as float32 CHW; tiles are gathered, denoised and stitched on the GPU in batches,
 in ascending tile index order (the reference's fp32 summation order), with no host synchronisation
 inside the loop.  For ``UtNet`` the three stages are fused by ``nd_utnet_denoise_frame`` (no NCHW tile
-batch is ever materialised; in fp32 the first two encoder levels run once per band of tile rows); any
-other callable model goes through ``nd_tile_gather`` -> model -> ``nd_stitch_add``.
+batch is ever materialised; in fp32 the first two encoder levels run once per band of tile rows), for
+``UNet`` by ``nd_unet_denoise_frame`` (same fusion, the decoder restricted to what the kept centre of a
+tile needs); any other callable model goes through ``nd_tile_gather`` -> model -> ``nd_stitch_add``.
 """
 import torch
 
 from . import _lib
+from .networks.ThirdPartyNets import UNet
 from .networks.UtNet import UtNet
 
 
@@ -69,6 +71,20 @@ def denoise_frame(model, img, cs, ucs, ol, batch=16, tile_range=None, canvas=Non
                                                   begin, end - begin, batch, ws.data_ptr(), ws.numel(),
                                                   fws.data_ptr() if fws is not None else None, fws.numel() if fws is not None else 0,
                                                   _lib.stream_ptr(img.device), cb, None), "nd_utnet_denoise_frame")
+            return canvas
+        if isinstance(model, UNet):
+            if end <= begin:
+                return canvas
+            if model.training:
+                raise RuntimeError("nind_denoise_amd.UNet implements eval mode (BatchNorm running statistics) only; call .eval()")
+            batch = max(1, min(batch, end - begin))
+            blob = model.packed_weights(img.device)
+            ws = model.workspace(cs, cs, batch, img.device)
+            cb = _lib.PROGRESS_FN(lambda _ctx, n, t0, cnt: progress(n, t0, cnt)) if progress is not None else _lib.PROGRESS_FN()
+            flags = model.flags | (_lib.FLAG_FIND_NOISE if model.find_noise else 0)
+            _lib.check(lib.nd_unet_denoise_frame(_lib.ND_F32, flags, blob.data_ptr(), img.data_ptr(), canvas.data_ptr(), width, height,
+                                                 cs, ucs, ol, begin, end - begin, batch, ws.data_ptr(), ws.numel(),
+                                                 _lib.stream_ptr(img.device), cb, None), "nd_unet_denoise_frame")
             return canvas
         for n, t0 in enumerate(range(begin, end, batch)):
             cnt = min(batch, end - t0)

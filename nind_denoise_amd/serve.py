@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import pipeline
+from .networks.ThirdPartyNets import UNet
 
 
 class FrameEngine:
@@ -59,7 +60,11 @@ class FrameEngine:
         if hasattr(model, "packed_weights"):
             with torch.cuda.device(self.device), torch.cuda.stream(self.compute):
                 model.packed_weights(self.device)
-                model.workspace(cs, min(batch, self.total), self.device)
+                n = min(batch, self.total)
+                if isinstance(model, UNet):   # UNet.workspace takes (h, w, batch, device)
+                    model.workspace(cs, cs, n, self.device)
+                else:
+                    model.workspace(cs, n, self.device)
 
     def submit(self, frame):
         """frame: float32 CHW numpy array / CPU tensor (or a CUDA tensor: then no host copy).  Non-blocking unless every
