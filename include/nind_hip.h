@@ -72,6 +72,9 @@ typedef enum nd_flags {
                                  nd_utnet_denoise_frame); an unknown bit everywhere else                                          */
     ND_FLAG_FIND_NOISE = 128,  /* nd_unet_denoise_frame only (an unknown bit everywhere else): UNet(find_noise=True), ThirdPartyNets.py:
                                  167-168 -- a tile contributes its input minus the network output                                   */
+    ND_FLAG_TILE_SKIPS = 256,  /* A/B switch: nd_utnet_denoise_frame keeps the skip halves of tconvs4.0 / 3.0 / 2.0 in the per-tile sums
+                                 where it would compute their products once per band (nd_utnet_frame_folds).  Taken by the
+                                 frame-loop entry points only; an unknown bit everywhere else                                      */
     ND_FLAG_FULL_TILES = 8    /* nd_utnet_denoise_tiles / nd_utnet_profile_stack: compute every layer on the whole tile, as
                                  UtNet.forward does.  Default there: the last decoder levels compute only the pixels that the
                                  useful crop [pad, cs - pad) of a tile can reach (denoise_image.py:249-258 discards the rest of
@@ -79,7 +82,7 @@ typedef enum nd_flags {
                                  nd_unet_denoise_frame: the same switch for the UNet decoder (nd_unet_useful_region)             */
 } nd_flags;
 
-int nd_version(void);   /* 109 = this header */
+int nd_version(void);   /* 110 = this header */
 const char *nd_last_error(void);
 
 /* ---------------------------------------------------------------- tile geometry (host, pure integer)
@@ -179,6 +182,17 @@ int nd_utnet_frame_plan(int funit, int dtype, int flags, int width, int height, 
  * tile's).  The frame workspace then also holds a third origin table, the level-2 band, line and corner tensors and their
  * Winograd scratch.  ND_FLAG_TILE_LEVEL2 keeps it at 2.  *levels is written; same arguments and errors as nd_utnet_frame_plan. */
 int nd_utnet_frame_levels(int funit, int dtype, int flags, int width, int height, int cs, int ucs, int ol, int *levels);
+/* Host-only query: the decoder layers whose skip half nd_utnet_denoise_frame folds out of the per-tile sums.  The first layer of a
+ * decoder level is a ConvTranspose2d(3) on cat([up, skip]) and linear in its input channels: act(b + W_up * up + W_skip * skip) =
+ * act(W_up * up + P) with P = W_skip * skip + b.  Where the skip is a band tensor (the shared encoder levels) P is the same for
+ * every tile that overlaps a pixel, so it is computed once per band -- into the never-written up-sampled half of the band's
+ * concat tensor: the frame workspace does not grow -- and the per-tile layer runs on the up-sampled half of its K blocks with P as
+ * its addend.  Bit k of *mask is set when tconvs(4-k).0 is folded: a step that takes its skip from the band (tconvs4.0, tconvs3.0;
+ * tconvs2.0 where level 2 is shared) and runs in a kernel that takes an addend (conv_w2d; the three-pass F(6x6) form, whose band
+ * launches carry Winograd scratch of their own in the frame workspace).  0 with ND_FLAG_TILE_SKIPS and wherever no encoder level
+ * is shared.  Same canvas up to fp32 re-association (the two halves' sums are added in another order).  A function
+ * of the frame geometry, the dtype and the flags only; same arguments and errors as nd_utnet_frame_plan. */
+int nd_utnet_frame_folds(int funit, int dtype, int flags, int width, int height, int cs, int ucs, int ol, int *mask);
 
 /* Profiling entry point for the roofline report: one pass of the conv stack (22 MFMA conv layers + 4 pools, the launches
  * between the input pack and the final 1x1) with a HIP event recorded on `stream` between launches.  Synchronises the stream.

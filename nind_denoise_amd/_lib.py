@@ -16,6 +16,7 @@ KIND = {"conv3": 0, "convT3": 1, "convT2s2": 2, "conv1": 3, "conv2s2": 4}
 # nd_flags (include/nind_hip.h): per-call arithmetic switches
 FLAG_NO_SPLITK, FLAG_DIRECT_CONV, FLAG_W1D_REGS, FLAG_FULL_TILES, FLAG_UNFUSED_POOL, FLAG_TILE_ENCODER, FLAG_TILE_LEVEL2 = 1, 2, 4, 8, 16, 32, 64
 FLAG_FIND_NOISE = 128   # nd_unet_denoise_frame only
+FLAG_TILE_SKIPS = 256   # frame-loop entry points only: the skip halves of tconvs4.0 / 3.0 / 2.0 stay in the per-tile sums
 # nd_progress_fn: (ctx, launch index, first tile, tile count)
 PROGRESS_FN = ctypes.CFUNCTYPE(None, c_void_p, c_int, c_int, c_int)
 
@@ -75,6 +76,7 @@ _SIGNATURES = {
     "nd_utnet_frame_workspace_bytes": (c_size_t, [c_int] * 9),
     "nd_utnet_frame_plan": (c_int, [c_int] * 8 + [POINTER(c_int)]),
     "nd_utnet_frame_levels": (c_int, [c_int] * 8 + [POINTER(c_int)]),
+    "nd_utnet_frame_folds": (c_int, [c_int] * 8 + [POINTER(c_int)]),
     "nd_utnet_denoise_frame": (c_int, [c_int] * 4 + [c_void_p] * 3 + [c_int] * 8 + [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                                                                     PROGRESS_FN, c_void_p]),
     "nd_layer_packed_bytes": (c_size_t, [c_int] * 4),

@@ -268,7 +268,8 @@ int nd_launch_conv(const ConvDesc &d, hipStream_t stream) {
     const int KB = nd_kblocks(d.cin, dt);
     const int M = up ? 4 * d.cout : d.cout;
     if (d.cout % nd_cpp(dt)) ND_FAIL(ND_EINVAL, "conv: cout=%d must be a multiple of %d", d.cout, nd_cpp(dt));
-    ND_TRY(nd_check_in_planes("conv", d, KB));
+    ND_TRY(nd_check_in_planes("conv", d, KB, false, true));   // (a K-block sub-range of the weights: yes; an addend source: no)
+    if (d.add.base) ND_FAIL(ND_EINVAL, "conv: this kernel form takes no addend source");
     ND_TRY(nd_check_int32("conv", d.in));
 
     int dev = 0, ncus = 0;
@@ -280,6 +281,10 @@ int nd_launch_conv(const ConvDesc &d, hipStream_t stream) {
     if (KB % V.kbc) ND_FAIL(ND_EINVAL, "conv: Cin/8=%d not a multiple of the variant's K chunk %d", KB, V.kbc);
 
     ConvParams p = nd_conv_params(d, KB, M);
+    if (d.w_kb) {   // K blocks [w_kb0, w_kb0 + KB) of a blob packed for w_kb: 1 KiB pieces [mtile][kb][tap]
+        p.KBw = d.w_kb;
+        p.wpk += (size_t)d.w_kb0 * taps * 256;
+    }
     valid_grid(taps, d.in, &p.Hv, &p.Wv, &p.stride);
     const bool roi = d.roi_rows > 0;
     // region of the valid grid (of the INPUT grid for a 2x2 stride-2 transpose): same launch, shifted first pixel, smaller valid

@@ -129,6 +129,15 @@ struct ConvParams {
     long in2_plane;
     const int *origin2;
     int kb2, Wb2;
+    // conv_qp, conv_w2d.hip: K blocks per M tile of the packed weights (ConvDesc::w_kb; = KB unless the launch runs a K-block
+    // sub-range, whose first block wpk already points at)
+    int KBw;
+    // conv_w2d.hip, addend source (ConvDesc::add; null: none): the addend of valid output pixel (y, x) of image t, channel quad q, is
+    // element origin_add[t] + y * W_add + x of plane q (the border and region shifts are folded into `add`)
+    const f32x4 *add;
+    long add_plane;
+    const int *origin_add;
+    int W_add;
 };
 
 static inline void nd_conv_fastdivs(ConvParams &p) {
@@ -341,7 +350,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_qp(ConvParams p) {
         f_end = it.c1;
         const int z = (int)fdiv((unsigned)it.tile, p.fd_tpp), id = it.tile - z * p.tiles_per_problem;
         const int nb = (int)fdiv((unsigned)id, p.fd_ntm), mb = id - nb * p.n_tiles_m;   // M tiles of one N tile run back to back
-        f_w = p.wpk + z * p.w_bs + (size_t)mb * MTB * p.KB * TAPS * 256 + lane * 4;
+        f_w = p.wpk + z * p.w_bs + (size_t)mb * MTB * p.KBw * TAPS * 256 + lane * 4;
         f_a = p.in + z * p.in_bs + tile_q0(nb) + lane;
     };
     set_fill_tile(f_id);
@@ -380,7 +389,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_qp(ConvParams p) {
         if (p.dbg & (i < MTB ? 2 : 1)) return;   // timing experiment (make ABLATE=1): 1 = no activation DMA, 2 = no weight DMA
 #endif
         if (i < MTB) {
-            const float *src = f_w + ((size_t)i * p.KB + (size_t)f_c * KBC) * TAPS * 256;
+            const float *src = f_w + ((size_t)i * p.KBw + (size_t)f_c * KBC) * TAPS * 256;
             char *dst = fill_sb + i * RW * 1024;
             for (int q = wave; q < RW; q += NFILL) glds16(src + q * 256, dst + q * 1024);
         } else {

@@ -80,8 +80,10 @@ __device__ __forceinline__ unsigned long long stamp() {
 struct Strip { int img, y0, x0; bool ok; };
 
 // DBG: ablation bits for timing experiments (tools/w2d_ablate.sh); 0 = the production kernel.  SRC2: the layer has a second input
-// source (ConvParams::in2) -- an instantiation of its own, so that the kernel every other layer runs keeps its registers
-template <int DBG, bool SRC2 = false>
+// source (ConvParams::in2) -- an instantiation of its own, so that the kernel every other layer runs keeps its registers.  ADD: the
+// layer has an addend source (ConvParams::add) in place of its bias -- likewise its own instantiation, never pooled, no
+// pre-activation copy, no second input source
+template <int DBG, bool SRC2 = false, bool ADD = false>
 __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
@@ -166,7 +168,7 @@ __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
         f_c = it.c0;
         f_end = it.c1;
         const int nb = (int)fdiv((unsigned)it.tile, p.fd_ntm), mb = it.tile - nb * p.n_tiles_m;
-        f_w = p.wpk + (size_t)mb * kMTB * p.KB * kTaps * 256;     // wave-uniform: the lane's 16 bytes are added as a 32-bit offset
+        f_w = p.wpk + (size_t)mb * kMTB * p.KBw * kTaps * 256;     // wave-uniform: the lane's 16 bytes are added as a 32-bit offset
         if constexpr (SRC2) f_nb = nb;
 #pragma unroll
         for (int ps = 0; ps < 2; ++ps)
@@ -241,7 +243,7 @@ __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
             // 64-bit add each) and immediate offsets -- with a 64-bit pointer computed per piece every piece cost ~4 VALU-slot
             // instructions, each of which waits for a 64-cycle MFMA slot of the SIMD partner (12 pieces took 5,200 cycles)
             const int mt = dw >> 1, pl0 = (dw & 1) * 9;
-            const char *src = (const char *)(f_w + (((size_t)mt * p.KB + (size_t)f_c) * kTaps + pl0) * 256) + lane16;
+            const char *src = (const char *)(f_w + (((size_t)mt * p.KBw + (size_t)f_c) * kTaps + pl0) * 256) + lane16;
             char *dst = smem + f_stage * kStage + (mt * kTaps + pl0) * 1024;
             glds16o<-4096>(src + 4096, dst + 4096);
             glds16o<-3072>(src + 4096, dst + 4096);
@@ -311,6 +313,7 @@ __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
     const int e_row = lane >> 4, e_px = lane & 15;                  // reader side: rows e_row and e_row + 4, pixel e_px of the wave's 16
     f32x4 biasq[4];                                                 // bias of channels 8g + 4h .. + 3 of this wave's M tile
     auto load_bias = [&](int id) {
+        if constexpr (ADD) return;   // (the addend carries the bias: these registers are the budget of its loads)
         const int mb = id - (int)fdiv((unsigned)id, p.fd_ntm) * p.n_tiles_m;
 #pragma unroll
         for (int g = 0; g < 4; ++g) biasq[g] = *(const f32x4 *)(p.bias + (mb * kMTB + wm) * 32 + 8 * g + 4 * h);
@@ -330,7 +333,28 @@ __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
         // row e_row, pooled pixel e_px & 1 of the strip the lane already decoded (strips start on rows = 0 mod 8, pixels = 0 mod 4)
         const int pp_i = (e_px & ~3) + 2 * (e_px & 1);              // scratch column of the 2x2 block's first pixel
         const int pxp = (st.x0 >> 1) + (e_px & 1), pyp = (st.y0 >> 1) + e_row;
-        const bool okP = !SRC2 && p.pool && !(lane & 2) && st.ok && 2 * pxp + 1 < p.wpx && 2 * pyp + 1 < p.Hv;
+        // ADD: where this lane's two STORED pixels find their addends (bytes inside a plane, < 2^32: nd_check_add).  The loads run
+        // two store passes ahead of their use -- the first two go out here, each pass then requests the one two behind it -- so their
+        // HBM latency is met once per tile and not once per pass; bias and activation move behind the transpose for them
+        unsigned offQA = 0, offQB = 0;
+        f32x4 qa[8], qb[8];
+        // (unconditional loads: a lane or a channel quad that stores nothing reads element 0 of plane 0 instead -- a branch
+        //  around a load would end the scheduling region and with it the distance between a load and its use)
+        auto add_loads = [&](int k) {
+            const int qq = (q0 + k) * 4 < p.M ? q0 + k : 0;
+            const char *pq = (const char *)(p.add + (size_t)qq * p.add_plane);   // wave-uniform plane base
+            qa[k] = *(const f32x4 *)(pq + offQA);
+            qb[k] = *(const f32x4 *)(pq + offQB);
+        };
+        if constexpr (ADD) {
+            const unsigned oq = 16u * ((unsigned)p.origin_add[st.img] + (unsigned)(st.y0 + e_row) * (unsigned)p.W_add + (unsigned)ex);
+            offQA = okA ? oq : 0u;
+            offQB = okB ? oq + 64u * (unsigned)p.W_add : 0u;
+            add_loads(0);
+            add_loads(1);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        const bool okP = !SRC2 && !ADD && p.pool && !(lane & 2) && st.ok && 2 * pxp + 1 < p.wpx && 2 * pyp + 1 < p.Hv;
         const unsigned offP = (unsigned)((st.img * p.pool_P + (pyp + p.pool_pad) * p.pool_W + pxp + p.pool_pad) * 16);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -344,8 +368,13 @@ __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
                     acc[x][4 * g + 2 * pr] = 0.f;
                     acc[x][4 * g + 2 * pr + 1] = 0.f;
                 }
-                const f32x2 bq = {biasq[g][2 * pr], biasq[g][2 * pr + 1]};
-                const f32x2 a = m[1] + m[2] + bq, b = m[1] - m[2] + bq, c = m[3] + m[4], e = m[3] - m[4];   // A^T m, bias folded in once
+                f32x2 a = m[1] + m[2], b = m[1] - m[2];
+                const f32x2 c = m[3] + m[4], e = m[3] - m[4];   // A^T m
+                if constexpr (!ADD) {   // the bias folded in once (ADD: the addend carries it)
+                    const f32x2 bq = {biasq[g][2 * pr], biasq[g][2 * pr + 1]};
+                    a += bq;
+                    b += bq;
+                }
                 f32x2 y[4];
                 y[0] = m[0] + a + c;
                 y[1] = b + 2.f * e;
@@ -355,7 +384,9 @@ __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
                 for (int i = 0; i < 4; ++i) {
                     ypre[i][2 * pr] = y[i][0];
                     ypre[i][2 * pr + 1] = y[i][1];
-                    if constexpr (decltype(fast)::value) {
+                    if constexpr (ADD) {
+                        // (raw sums: addend and activation follow the transpose)
+                    } else if constexpr (decltype(fast)::value) {
                         const f32x2 t = y[i] * slope2;
                         y[i] = f32x2{fmaxf(y[i][0], t[0]), fmaxf(y[i][1], t[1])};
                     } else {
@@ -365,7 +396,7 @@ __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
                     yy[i][2 * pr + 1] = y[i][1];
                 }
             }
-            if (!SRC2 && p.pre) {   // training forward: acc + bias for the activation's backward pass, compact planes [C/4][B][Hv][wpx]
+            if (!SRC2 && !ADD && p.pre) {   // training forward: acc + bias for the activation's backward pass, compact planes [C/4][B][Hv][wpx]
                 const Strip so = strip_of(nb, sl);
                 const int yo = so.y0 + rr, m4 = (q0 + 2 * g + h) * 4, left = p.wpx - so.x0;
                 if (so.ok && yo < p.Hv && m4 < p.M) {
@@ -399,10 +430,29 @@ __global__ __launch_bounds__(512) void conv_w2d(ConvParams p) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                const f32x4 va = *((const f32x4 *)scratch + e_row * 16 + e_px);
-                const f32x4 vb2 = *((const f32x4 *)scratch + (e_row + 4) * 16 + e_px);
+                f32x4 va = *((const f32x4 *)scratch + e_row * 16 + e_px);
+                f32x4 vb2 = *((const f32x4 *)scratch + (e_row + 4) * 16 + e_px);
+                if constexpr (ADD) {
+                    const int k = 2 * g + hq;
+                    va += qa[k];
+                    vb2 += qb[k];
+                    if (k + 2 < 8) {
+                        add_loads(k + 2);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if constexpr (decltype(fast)::value) {
+                            va[e] = fmaxf(va[e], va[e] * slope);
+                            vb2[e] = fmaxf(vb2[e], vb2[e] * slope);
+                        } else {
+                            va[e] = apply_act(va[e], p.act, slope);
+                            vb2[e] = apply_act(vb2[e], p.act, slope);
+                        }
+                    }
+                }
                 f32x4 vp = va;
-                if (!SRC2 && p.pool) {   // wave-uniform
+                if (!SRC2 && !ADD && p.pool) {   // wave-uniform
                     const f32x4 *blk = (const f32x4 *)scratch + (2 * e_row) * 16 + pp_i;
                     const f32x4 p00 = blk[0], p01 = blk[1], p10 = blk[16], p11 = blk[17];
 #pragma unroll
@@ -534,7 +584,7 @@ __global__ __launch_bounds__(256) void k_w2d_split_finish(ConvParams p) {
     const int m4 = mb * (kMTB * 32) + quad * 4;
     if (m4 >= p.M) return;
     const float slope = p.act == ND_ACT_NONE ? 1.f : (p.slope_dev ? *p.slope_dev : p.slope);
-    const f32x4 bv = *(const f32x4 *)(p.bias + m4);
+    const f32x4 bv = p.add ? f32x4{0.f, 0.f, 0.f, 0.f} : *(const f32x4 *)(p.bias + m4);
     const unsigned tot = (unsigned)p.nimg * (unsigned)p.PV;
     for (int l = threadIdx.x; l < kSlots; l += 256) {
         const int i = l & 3, jj = l >> 2, wn = jj >> 5, j = jj & 31;
@@ -548,7 +598,10 @@ __global__ __launch_bounds__(256) void k_w2d_split_finish(ConvParams p) {
         if (y >= p.Hv || x >= p.wpx) continue;
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
         for (int ks = 0; ks < p.S; ++ks) acc += p.part[((size_t)(t * p.S + ks) * (kMTB * 8) + quad) * kSlots + l];
-        acc += bv;
+        if (p.add)
+            acc += p.add[(long)(m4 >> 2) * p.add_plane + (long)p.origin_add[img] + (long)y * p.W_add + x];
+        else
+            acc += bv;
         f32x4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[e] = p.act <= ND_ACT_PRELU ? (acc[e] > 0.f ? acc[e] : acc[e] * slope) : apply_act(acc[e], p.act, slope);
@@ -577,8 +630,12 @@ int nd_launch_conv_w2d(const ConvDesc &d, hipStream_t stream) {
     const int Hv = roi ? d.roi_rows : Hfull, Wpx = roi ? d.roi_cols : Wfull, Wg = (Wpx + 3) / 4, NB = (Hv + kR - 1) / kR;
     if (d.pre && (roi || d.pool)) ND_FAIL(ND_EINVAL, "w2d: a pre-activation copy goes with whole, unpooled layers only");
     if (d.cout % 4) ND_FAIL(ND_EINVAL, "w2d: cout must be a multiple of 4");
-    ND_TRY(nd_check_in_planes("w2d", d, KB, true));
-    const bool src2 = d.in2.base != nullptr;
+    ND_TRY(nd_check_in_planes("w2d", d, KB, true, true));
+    const bool src2 = d.in2.base != nullptr, add = d.add.base != nullptr;
+    if (add && (d.pool || d.pre || src2))
+        ND_FAIL(ND_EINVAL, "w2d: a layer with an addend source is neither pooled nor keeps a pre-activation copy nor has a second input source");
+    // (the addend of every valid output pixel, and of no other, is read)
+    if (add) ND_TRY(nd_check_add("w2d", d, (long)(d.roi_r0 + Hv - 1 + d.add.pad) * d.add.Wb + d.roi_c0 + Wpx - 1 + d.add.pad + 1));
     if (src2 && (d.pool || d.pre)) ND_FAIL(ND_EINVAL, "w2d: a layer with a second input source is neither pooled nor keeps a pre-activation copy");
     // (a strip of the last band / group reads kR + 2 rows x 6 pixels from its first pixel, valid or not: see below)
     if (src2) ND_TRY(nd_check_in2("w2d", d, KB, (long)(d.roi_r0 + (NB - 1) * kR + kRI - 1) * d.in2.Wb + d.roi_c0 + 4 * (Wg - 1) + 6));
@@ -590,11 +647,11 @@ int nd_launch_conv_w2d(const ConvDesc &d, hipStream_t stream) {
 
     int dev = 0, ncus = 0;
     ND_TRY(nd_device(&dev, &ncus));
-    void (*fn)(ConvParams) = src2 ? conv_w2d<0, true> : conv_w2d<0>;
+    void (*fn)(ConvParams) = add ? conv_w2d<0, false, true> : src2 ? conv_w2d<0, true> : conv_w2d<0>;
 #ifdef ND_QP_STAMPS
     // diagnostic build only (make STAMPS=1; tools/w2d_ablate.sh): ND_W2D_DBG names one of the ablation masks / the stamped kernel
     static const int dbg_all = getenv("ND_W2D_DBG") ? atoi(getenv("ND_W2D_DBG")) : 0;
-    const int dbg_env = src2 ? 0 : dbg_all;   // (a layer with a second input source runs the production kernel)
+    const int dbg_env = src2 || add ? 0 : dbg_all;   // (a layer with a second input or an addend source runs the production kernel)
     switch (dbg_env) {
         case 1: fn = conv_w2d<1>; break;
         case 2: fn = conv_w2d<2>; break;
@@ -624,6 +681,17 @@ int nd_launch_conv_w2d(const ConvDesc &d, hipStream_t stream) {
         p.origin2 = d.in2_origin;
         p.kb2 = d.in2_from / 2;
         p.Wb2 = d.in2.Wb;
+    }
+    if (d.w_kb) {
+        p.KBw = d.w_kb;
+        p.wpk += (size_t)d.w_kb0 * kTaps * 256;
+    }
+    if (add) {
+        p.add = (const f32x4 *)d.add.base + (long)d.add_plane0 * d.add.np() + (long)((roi ? d.roi_r0 : 0) + d.add.pad) * d.add.Wb +
+                (roi ? d.roi_c0 : 0) + d.add.pad;
+        p.add_plane = d.add.np();
+        p.origin_add = d.add_origin;
+        p.W_add = d.add.Wb;
     }
     p.Hv = Hv;
     p.Wv = Wg;               // groups per row

@@ -51,9 +51,25 @@ int nd_once_per_device(int dev, int (*init)()) {
 }
 
 // ------------------------------------------------------------------ checks of a conv layer
-int nd_check_in_planes(const char *who, const ConvDesc &d, int KB, bool takes_in2) {
+int nd_check_in_planes(const char *who, const ConvDesc &d, int KB, bool takes_in2, bool takes_add) {
     if (d.in.planes < d.in_plane0 + 2 * KB) ND_FAIL(ND_EINVAL, "%s: input buffer has %d planes, needs %d", who, d.in.planes, d.in_plane0 + 2 * KB);
     if (d.in2.base && !takes_in2) ND_FAIL(ND_EINVAL, "%s: this kernel form has no second input source", who);
+    if ((d.add.base || d.w_kb) && !takes_add) ND_FAIL(ND_EINVAL, "%s: this kernel form takes no addend source and no K-block sub-range", who);
+    if (d.w_kb && (d.w_kb0 < 0 || d.w_kb0 + KB > d.w_kb))
+        ND_FAIL(ND_EINVAL, "%s: K blocks [%d,+%d) outside the %d of the packed weights", who, d.w_kb0, KB, d.w_kb);
+    return ND_OK;
+}
+
+int nd_check_add(const char *who, const ConvDesc &d, long reach) {
+    const QpBuf &q = d.add;
+    const int n = d.cout / 4;   // planes read
+    if (q.dt != ND_F32 || d.out.dt != ND_F32 || !d.add_origin || d.add_plane0 < 0 || d.add_plane0 + n > q.planes || d.add_origin_max < 0 ||
+        reach <= 0)
+        ND_FAIL(ND_EINVAL, "%s: addend source: planes [%d,+%d) of %d", who, d.add_plane0, n, q.planes);
+    // the last plane read ends where the buffer's slack ends; every other plane is followed by a plane
+    const long last = d.add_origin_max + reach, room = (long)(q.planes - d.add_plane0 - n + 1) * q.np() + (long)nd_buf_slack(q.Wb);
+    if (last > room) ND_FAIL(ND_EINVAL, "%s: addend source: a launch reaches element %ld of a plane, the buffer ends at %ld", who, last, room);
+    if (last * 16 >= (1L << 32)) ND_FAIL(ND_EINVAL, "%s: addend source too large for 32-bit byte offsets", who);
     return ND_OK;
 }
 
@@ -109,6 +125,7 @@ ConvParams nd_conv_params(const ConvDesc &d, int KB, int M) {
     p.pre = (f32x4 *)d.pre;
     p.pre_plane = d.pre_plane;
     p.KB = KB;
+    p.KBw = KB;
     p.M = M;
     p.cout = d.cout;
     p.Po = d.out.Hb * d.out.Wb;

@@ -87,10 +87,25 @@ struct ConvDesc {
     int in2_plane0 = 0, in2_from = 0;
     const int *in2_origin = nullptr;
     long in2_origin_max = 0;
+    // K-block sub-range of the packed weights (w_kb 0: the blob is the launch's own; conv_w2d): the launch's cin channels are K blocks
+    // [w_kb0, w_kb0 + cin / 8) of a blob packed for w_kb K blocks -- the M-tile stride of the blob is w_kb, not the launch's K extent.
+    // The fused denoise loop runs the two halves of a decoder level's first layer apart: the up-sampled half per tile, the skip half
+    // once per band
+    int w_kb = 0, w_kb0 = 0;
+    // addend source (add.base null: none; conv_w2d): the epilogue computes act(acc + addend) instead of act(acc + bias), where the
+    // addend of output pixel (y, x) of image t, channel quad q, is element add_origin[t] + (y + add.pad) * add.Wb + x + add.pad of
+    // plane add_plane0 + q of `add`.  Shaped like in2: add_origin lives in HBM, one entry per image of the launch, add_origin_max bounds
+    // its entries.  The fused denoise loop adds the skip half's product P = W_skip * skip + b, computed once per band
+    QpBuf add = {};
+    int add_plane0 = 0;
+    const int *add_origin = nullptr;
+    long add_origin_max = 0;
 };
 // the furthest element (exclusive) of a plane of d.in2 a launch may touch stays inside the buffer and its slack: `reach` = elements
 // past an image's origin (its window in the layer's bordered input, the kernel's over-read included)
 int nd_check_in2(const char *who, const ConvDesc &d, int KB, long reach);
+// the same for d.add: `reach` = elements past an image's origin of the furthest addend element the launch's valid output grid touches
+int nd_check_add(const char *who, const ConvDesc &d, long reach);
 // scratch that lets every layer split its partial round: 512 work items of 64 x 1024 accumulators
 static const size_t kSplitScratchBytes = (size_t)512 * 64 * 1024 * 4;
 int nd_launch_conv(const ConvDesc &d, hipStream_t stream);
@@ -132,8 +147,9 @@ int nd_raise_lds(int dev, const void *fn, size_t bytes);
 // runs init() once per device (the first caller on a device runs it; the others wait until it has succeeded)
 int nd_once_per_device(int dev, int (*init)());
 // checks of a conv layer; `who` is the launcher's error prefix.  Input planes [in_plane0, in_plane0 + 2 KB) exist; a launcher
-// that does not take a second input source (takes_in2) refuses a layer that has one
-int nd_check_in_planes(const char *who, const ConvDesc &d, int KB, bool takes_in2 = false);
+// that does not take a second input source (takes_in2), or an addend / a K-block sub-range of the weights (takes_add), refuses a
+// layer that has one
+int nd_check_in_planes(const char *who, const ConvDesc &d, int KB, bool takes_in2 = false, bool takes_add = false);
 // the destination holds B images of oh x ow plus its border (at_least: or more) and planes [out_plane0, out_plane0 + cout / cpp)
 int nd_check_out(const char *who, const ConvDesc &d, int oh, int ow, bool at_least);
 // the linear pixel index of `in` fits int32
@@ -141,11 +157,11 @@ int nd_check_int32(const char *who, const QpBuf &in);
 // d's region of interest (if any) lies inside the Hv x Wv grid; refused: the launcher takes no region for this layer (`why`)
 int nd_check_roi(const char *who, const ConvDesc &d, int Hv, int Wv, bool refused, const char *why);
 // the arithmetic switches every flags-taking entry point accepts (include/nind_hip.h: nd_flags); unknown bits are an error.
-// frame_loop: the frame-loop entry points (nd_utnet_frame_*, nd_utnet_denoise_frame) also take ND_FLAG_TILE_LEVEL2, which means
-// nothing anywhere else; unet_frame: nd_unet_denoise_frame also takes ND_FLAG_FIND_NOISE
+// frame_loop: the frame-loop entry points (nd_utnet_frame_*, nd_utnet_denoise_frame) also take ND_FLAG_TILE_LEVEL2 and
+// ND_FLAG_TILE_SKIPS, which mean nothing anywhere else; unet_frame: nd_unet_denoise_frame also takes ND_FLAG_FIND_NOISE
 static inline int nd_check_flags(int flags, bool frame_loop = false, bool unet_frame = false) {
     const int known = ND_FLAG_NO_SPLITK | ND_FLAG_DIRECT_CONV | ND_FLAG_W1D_REGS | ND_FLAG_FULL_TILES | ND_FLAG_UNFUSED_POOL |
-                      ND_FLAG_TILE_ENCODER | (frame_loop ? ND_FLAG_TILE_LEVEL2 : 0) | (unet_frame ? ND_FLAG_FIND_NOISE : 0);
+                      ND_FLAG_TILE_ENCODER | (frame_loop ? ND_FLAG_TILE_LEVEL2 | ND_FLAG_TILE_SKIPS : 0) | (unet_frame ? ND_FLAG_FIND_NOISE : 0);
     if (flags & ~known) ND_FAIL(ND_EINVAL, "unknown flag bits 0x%x", flags);
     return ND_OK;
 }

@@ -196,6 +196,15 @@ extern "C" int nd_utnet_frame_levels(int funit, int dtype, int flags, int width,
     return ND_OK;
 }
 
+extern "C" int nd_utnet_frame_folds(int funit, int dtype, int flags, int width, int height, int cs, int ucs, int ol, int *mask) {
+    ND_TRY(nd_check_flags(flags, true));
+    if (!mask) ND_FAIL(ND_EINVAL, "nd_utnet_frame_folds: null output");
+    FramePlan fp;
+    ND_TRY(frame_plan(funit, dtype, flags, width, height, cs, ucs, ol, 1, &fp));
+    *mask = fp.folds;
+    return ND_OK;
+}
+
 extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, const void *packed, const float *img, float *canvas,
                                       int width, int height, int cs, int ucs, int ol, int tile_begin, int tile_count, int batch,
                                       void *ws, size_t ws_bytes, void *fws, size_t fws_bytes, void *stream, nd_progress_fn progress,
@@ -217,7 +226,7 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
         for (int t0 = tile_begin; t0 < end; t0 += batch, ++n) {
             const int cnt = end - t0 < batch ? end - t0 : batch;
             if (progress) progress(progress_ctx, n, t0, cnt);
-            ND_TRY(nd_utnet_denoise_tiles(funit, act, dtype, flags & ~ND_FLAG_TILE_LEVEL2, packed, img, canvas, width, height, cs, ucs, ol, t0, cnt, batch, ws,
+            ND_TRY(nd_utnet_denoise_tiles(funit, act, dtype, flags & ~(ND_FLAG_TILE_LEVEL2 | ND_FLAG_TILE_SKIPS), packed, img, canvas, width, height, cs, ucs, ol, t0, cnt, batch, ws,
                                           ws_bytes, stream));
         }
         return ND_OK;
@@ -255,16 +264,24 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
     // The two decoder steps that read a skip half (tconvs4.0: CAT4, tconvs3.0: CAT3) take it from the band where their kernel has a
     // second input source; else the window is copied into the tile buffer as the layer expects it (k_splice)
     // (with level 2 also tconvs2.0: CAT2)
-    struct Skip { Buf cat; int planes, step, tstep; const int *win; int *table; bool in_place; } skips[3] = {
-        {CAT4, f4, -1, S, fp.win4, origins, false}, {CAT3, 2 * f4, -1, S / 2, fp.win3, origins + fp.origin_bytes / sizeof(int), false},
-        {CAT2, 4 * f4, -1, S / 4, fp.win2, origins + 2 * fp.origin_bytes / sizeof(int), false}};
+    // A step the plan folds (utnet_net.h: frame_plan_folds) reads no skip at all: its window of the band's P is its addend
+    struct Skip { Buf cat; int planes, step, tstep; const int *win; int *table; bool in_place, fold; Form form; } skips[3] = {
+        {CAT4, f4, -1, S, fp.win4, origins, false, false, FORM_DIRECT},
+        {CAT3, 2 * f4, -1, S / 2, fp.win3, origins + fp.origin_bytes / sizeof(int), false, false, FORM_DIRECT},
+        {CAT2, 4 * f4, -1, S / 4, fp.win2, origins + 2 * fp.origin_bytes / sizeof(int), false, false, FORM_DIRECT}};
+    char *const fold_wino = (char *)fws + fp.bytes - fp.fold_wino_bytes;
     const int nskips = l2 ? 3 : 2;
-    for (Skip &k : skips)
-        for (int i = kSharedSteps; i < kNumSteps; ++i)
+    for (int ki = 0; ki < 3; ++ki)
+        for (int i = kSharedSteps; i < kNumSteps; ++i) {
+            Skip &k = skips[ki];
             if (kSteps[i].layer >= 0 && kSteps[i].src == k.cat) {
+                const Form form = step_form(kSteps[i], funit, dtype, flags, pl, bl);
                 k.step = i;
-                k.in_place = form_takes_src2(kSteps[i], step_form(kSteps[i], funit, dtype, flags, pl, bl), funit, flags, pl);
+                k.in_place = form_takes_src2(kSteps[i], form, funit, flags, pl);
+                k.form = form;
+                k.fold = ki < nskips && ((fp.folds >> ki) & 1) && k.in_place;
             }
+        }
     StepSrc2 src2[3];
     dec.src2 = src2;
     // Bands are computed as the launches reach them, band b into slot b & 1 of the tensors the launches read (the P2 lines of its
@@ -287,6 +304,10 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
             bp.split = pl.split;
             ND_TRY(nd_launch_gather_band(img, width, height, cs, ucs, ol, row0, bp.buf[X0], s));
             ND_TRY(run_stack(funit, act, dtype, blob, bp, s, enc));
+            for (int ki = 0; ki < 2; ++ki)
+                if (skips[ki].fold)
+                    ND_TRY(launch_skip_fold(funit, flags, blob, bl, skips[ki].step, skips[ki].form, bp.buf[skips[ki].cat], skips[ki].planes,
+                                            rois[skips[ki].step], skips[ki].tstep, nrows, cols, pl.split, fold_wino, fp.fold_wino_bytes, s));
             // its edge images, the same steps: top / bottom rows of every tile row, left / right columns of every tile column
             Plan re = band_slot(row_edge_plan(fp, funit, dtype, nrows, rows_base), b & 1, fp.slots, P2);
             Plan ce = band_slot(col_edge_plan(fp, funit, dtype, nrows, cs, cols_base), b & 1, fp.slots, P2);
@@ -301,6 +322,9 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
                 Plan b2 = l2_scratch(l2_slot(l2_band_plan(fp, funit, dtype, nrows, cs, l2_band_base), b & 1, fp.slots));
                 b2.buf[P2] = bp.buf[P2];
                 ND_TRY(run_stack(funit, act, dtype, blob, b2, s, enc2));
+                if (skips[2].fold)
+                    ND_TRY(launch_skip_fold(funit, flags, blob, bl, skips[2].step, skips[2].form, b2.buf[CAT2], skips[2].planes, rois[skips[2].step],
+                                            skips[2].tstep, nrows, cols, pl.split, fold_wino, fp.fold_wino_bytes, s));
                 const Plan r2 = l2_scratch(l2_slot(l2_row_plan(fp, funit, dtype, nrows, l2_rows_base), b & 1, fp.slots, P3));
                 const Plan c2 = l2_scratch(l2_slot(l2_col_plan(fp, funit, dtype, nrows, cs, l2_cols_base), b & 1, fp.slots, P3));
                 const int h2 = bp.buf[P2].Hb, w2 = bp.buf[P2].Wb;
@@ -335,7 +359,7 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
         for (int ki = 0; ki < nskips; ++ki) {
             const Skip &k = skips[ki];
             const QpBuf &src = k.cat == CAT2 ? bf2.buf[k.cat] : bf.buf[k.cat];
-            if (!k.in_place) {
+            if (!k.in_place && !k.fold) {
                 SpliceMap m;
                 m.step_y = m.step_x = k.tstep;
                 ND_TRY(nd_launch_splice(src, k.planes, tp.buf[k.cat], k.planes, k.planes, t0, cnt, cols, 0, m, k.win[0], k.win[1], k.win[0],
@@ -346,6 +370,11 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
             q.step = k.step;
             q.buf = src;
             q.plane0 = q.from = k.planes;   // the skip is the upper half of the concat in the band as in the tile
+            q.addend = k.fold;
+            if (k.fold) {   // P: the lower half, an n + 2 output inside the n + 4 bordered plane
+                q.plane0 = 0;
+                q.buf.pad = 1;
+            }
             q.origin = k.table;
             ND_TRY(nd_launch_skip_origins(src, tp.buf[k.cat].pad, t0, cnt, cols, fp.R, k.tstep, slot_elems(src, fp.slots), k.table,
                                           &q.origin_max, s));

@@ -369,8 +369,12 @@ struct StepSrc2 {
     int plane0 = 0, from = 0;   // first plane of buf; input plane of the step at which buf takes over
     const int *origin = nullptr;   // per image of the launch (HBM)
     long origin_max = 0;
+    // the skip half is folded out of the step (launch_skip_fold): buf holds its product P, the step's addend source (ConvDesc::add),
+    // and the step runs on the K blocks of its input planes below `from` alone
+    bool addend = false;
 };
-// the kernel a step runs in takes a second input source: conv_w2d and the three-pass F(6x6) form
+// the kernel a step runs in takes a second input source -- and, all the same kernels, an addend source with a K-block sub-range
+// of the weights: conv_w2d and the three-pass F(6x6) form
 inline bool form_takes_src2(const Step &st, Form form, int f, int flags, const Plan &pl) {
     if (form == FORM_WINO3P) return kWinoTile == 6;
     return form == FORM_W1D4 && nd_f43_w2d(pl.buf[st.src], lcout(kLayers[st.layer], f), false, flags);
@@ -421,7 +425,8 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
             d.pre = pre[l.prelu].base;
             d.pre_plane = pre[l.prelu].np();
         }
-        d.cin = lcin(l, f);
+        const int cin = lcin(l, f);
+        d.cin = cin;
         d.cout = lcout(l, f);
         d.wpk = blob + bl.off[st.layer];
         d.bias = d.wpk + nd_bias_offset(l.kind, d.cin, d.cout, dt);
@@ -439,7 +444,14 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
             d.roi_cols = o.rois[this_step].cols;
         }
         for (int i = 0; i < o.nsrc2; ++i)
-            if (o.src2[i].step == k) {
+            if (o.src2[i].step == k && o.src2[i].addend) {
+                d.add = o.src2[i].buf;
+                d.add_plane0 = o.src2[i].plane0;
+                d.add_origin = o.src2[i].origin;
+                d.add_origin_max = o.src2[i].origin_max;
+                d.w_kb = nd_kblocks(cin, dt);
+                d.cin = o.src2[i].from * cpp;
+            } else if (o.src2[i].step == k) {
                 d.in2 = o.src2[i].buf;
                 d.in2_plane0 = o.src2[i].plane0;
                 d.in2_from = o.src2[i].from;
@@ -462,7 +474,7 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
             // narrow layer: 1-D Winograd along x inside the implicit-GEMM kernel; F(4,3), or F(2,3) on rows too wide for it
             const int T = form == FORM_W1D4 ? kW1dTile : 2;
             if (!pre) d.wpk = blob + (T == kW1dTile ? bl.w1off[st.layer] : bl.w1off2[st.layer]);
-            d.bias = d.wpk + nd_bias_offset(d.kind, d.cin, d.cout, ND_F32, T);
+            d.bias = d.wpk + nd_bias_offset(d.kind, cin, d.cout, ND_F32, T);
             ND_TRY(form == FORM_W1D4 ? nd_launch_conv_f43(d, flags, s) : nd_launch_conv_w1d(T, d, s));
             continue;
         }
@@ -484,6 +496,7 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
                     c.pool = &pv;
                 }
                 if (d.in2_origin) c.in2_origin = d.in2_origin + b0;   // (in2_origin_max bounds every chunk's entries)
+                if (d.add_origin) c.add_origin = d.add_origin + b0;
                 // (profiling: the split of a layer's time into its passes is recorded for a single-chunk layer only)
                 ND_TRY(nd_launch_conv_wino(kWinoTile, c, pl.wino, pl.wino_bytes, s, (o.ev_x && nimg <= kWinoChunk) ? o.ev_x + 2 * this_step : nullptr));
             }
@@ -592,6 +605,10 @@ struct FramePlan {
     int h2 = 0, w2 = 0;      // P2 of a full band
     int win2[2] = {0, 0};    // [lo, hi) of the CAT2 skip pixels the decoder reads
     size_t l2_band_bytes = 0, l2_row_bytes = 0, l2_col_bytes = 0, l2_corner_bytes = 0, l2_wino_bytes = 0;
+    // bit k: the skip half of tconvs(4 - k).0 is folded out of the per-tile sums (frame_plan_folds); behind everything else in the
+    // frame workspace, the Winograd scratch of the band launches of the folded three-pass steps (kFoldRows rows at a time)
+    int folds = 0;
+    size_t fold_wino_bytes = 0;
 };
 inline int band_hx(const FramePlan &fp, int nrows, int cs) { return (nrows - 1) * fp.S + cs + 4; }
 // the edge images of a band of nrows tile rows (planes sized for a full band; P2 in the band's slots) and the corner patches of a
@@ -732,6 +749,89 @@ inline void frame_plan_level2(int f, int dt, int flags, int cs, int batch, const
     fp->levels = 3;
 }
 
+// ---------------------------------------------------------------- skip halves of the decoder, once per band
+// The first layer of a decoder level is a ConvTranspose2d(3) on cat([up, skip]), linear in its input channels:
+//     act(b + W_up * up + W_skip * skip) = act(W_up * up + P),   P = W_skip * skip + b.
+// Where the skip is a band tensor, P is a band tensor too: the same values for every tile that overlaps a pixel (2.0 / 2.1 / 2.6
+// tiles on average at levels 0 / 1 / 2 of G24).  A folded step's P is computed with the band, right behind the concat tensor it
+// derives from, into that tensor's up-sampled half -- which no band launch writes, has the skip half's plane geometry, and holds
+// the n + 2 output of a ConvTranspose2d(3) inside its n + 4 bordered plane at border 1 -- restricted to the rows and columns some
+// tile's region reads; the per-tile step then runs on the K blocks of its up-sampled half alone and takes its window of P as the
+// addend of its epilogue (ConvDesc::add; the window starts where the in-place skip read starts: the same origin table).  The bias
+// is part of P.  Both launches use the layer's one packed blob, each its K-block sub-range (ConvDesc::w_kb).
+// Which steps fold: those that read a band skip and run in a kernel that takes an addend (conv_w2d, three-pass F(6x6)) -- the
+// plan's decision, a function of geometry, dtype and flags; ND_FLAG_TILE_SKIPS folds none.  A three-pass step's band launch runs
+// kFoldRows output rows at a time on Winograd scratch of its own in the frame workspace (a band is one image of any size; the tile
+// workspace's scratch is sized for the tiles of a launch).
+constexpr int kFoldRows = 48;
+inline void frame_plan_folds(int f, int dt, int flags, const Plan &tp, const BlobLayout &bl, FramePlan *fp) {
+    fp->folds = 0;
+    fp->fold_wino_bytes = 0;
+    if (!fp->D || (flags & ND_FLAG_TILE_SKIPS)) return;
+    const Buf cats[3] = {CAT4, CAT3, CAT2};
+    for (int k = 0; k < (fp->levels == 3 ? 3 : 2); ++k)
+        for (int i = kSharedSteps; i < kNumSteps; ++i) {
+            const Step &st = kSteps[i];
+            if (st.layer < 0 || st.src != cats[k] || kLayers[st.layer].kind != ND_CONVT3) continue;
+            const Form form = step_form(st, f, dt, flags, tp, bl);
+            if (!form_takes_src2(st, form, f, flags, tp)) continue;
+            fp->folds |= 1 << k;
+            if (form != FORM_WINO3P) continue;
+            QpBuf v = {};
+            v.B = 1;
+            v.Hb = kFoldRows + 2;
+            v.Wb = (k == 2 ? l2_extent(fp->w2, CAT2) : enc_extent(fp->wx, cats[k])) + 4;
+            const size_t need = nd_wino_scratch_bytes(kWinoTile, v, lcin(kLayers[st.layer], f) / 2, lcout(kLayers[st.layer], f));
+            if (need > fp->fold_wino_bytes) fp->fold_wino_bytes = need;
+        }
+    fp->fold_wino_bytes = (fp->fold_wino_bytes + 255) & ~(size_t)255;
+    fp->bytes += fp->fold_wino_bytes;
+}
+// P of decoder step `step` for a band of nrows tile rows whose concat tensor is `cat` (skip half: planes [planes, 2 * planes)):
+// roi = the step's region on a tile, tstep = the tile stride at the level; form = the step's kernel family (conv_w2d, or the
+// three-pass form on `wino`, kFoldRows rows of the band at a time)
+inline int launch_skip_fold(int f, int flags, const float *blob, const BlobLayout &bl, int step, Form form, const QpBuf &cat, int planes,
+                            const Roi &roi, int tstep, int nrows, int cols, float *split, char *wino, size_t wino_bytes, hipStream_t s) {
+    const LayerSpec &l = kLayers[kSteps[step].layer];
+    const int cin = lcin(l, f);
+    ConvDesc d;
+    d.kind = l.kind;
+    d.act = ND_ACT_NONE;
+    d.cin = planes * 4;
+    d.cout = lcout(l, f);
+    d.wpk = blob + bl.w1off[kSteps[step].layer];
+    d.bias = d.wpk + nd_bias_offset(l.kind, cin, d.cout, ND_F32, kW1dTile);
+    d.w_kb = nd_kblocks(cin);
+    d.w_kb0 = planes / 2;
+    d.in = cat;
+    d.in_plane0 = planes;
+    d.out = cat;
+    d.out.pad = 1;
+    d.out_plane0 = 0;
+    d.part = split;
+    d.part_bytes = split ? kSplitScratchBytes : 0;
+    d.nosplit = (flags & ND_FLAG_NO_SPLITK) != 0;
+    d.roi_r0 = roi.r0;
+    d.roi_c0 = roi.c0;
+    d.roi_rows = (nrows - 1) * tstep + roi.rows;
+    d.roi_cols = (cols - 1) * tstep + roi.cols;
+    if (form != FORM_WINO3P) return nd_launch_conv_w2d(d, s);
+    d.wpk = blob + bl.woff[kSteps[step].layer];
+    d.bias = nullptr;
+    const int r_end = d.roi_r0 + d.roi_rows;
+    for (int r0 = d.roi_r0; r0 < r_end; r0 += kFoldRows) {
+        // rows [r0, r0 + rows) of the region as a view of rows + 2 bordered input rows (the scratch follows the view's extent)
+        ConvDesc c = d;
+        const int rows = r_end - r0 < kFoldRows ? r_end - r0 : kFoldRows;
+        c.in.base = c.out.base = cat.base + (size_t)r0 * cat.Wb * 4;
+        c.in.Hb = c.out.Hb = rows + 2;
+        c.roi_r0 = 0;
+        c.roi_rows = rows;
+        ND_TRY(nd_launch_conv_wino(kWinoTile, c, wino, wino_bytes, s));
+    }
+    return ND_OK;
+}
+
 // the band plan: a function of the frame geometry, the dtype and the flags (batch only sizes the corner buffers and the tables)
 int frame_plan(int f, int dt, int flags, int W, int H, int cs, int ucs, int ol, int batch, FramePlan *fp) {
     *fp = FramePlan();
@@ -800,6 +900,7 @@ int frame_plan(int f, int dt, int flags, int W, int H, int cs, int ucs, int ol, 
     fp->bytes = fp->band_bytes + fp->row_edge_bytes + fp->col_edge_bytes + fp->corner_bytes + 2 * fp->origin_bytes;
     fp->D = 2;
     frame_plan_level2(f, dt, flags, cs, batch, bl, rois, fp);
+    frame_plan_folds(f, dt, flags, tp, bl, fp);
     return ND_OK;
 }
 

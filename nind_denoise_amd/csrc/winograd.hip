@@ -296,20 +296,36 @@ __global__ __launch_bounds__(NTL * (T + 2)) void k_wino_in2(const f32x4 *__restr
 //   output: pass 1 thread (column j, tile)  loads m[0..A)[j] (tile-contiguous), column transform (A -> T) -> LDS
 //           pass 2 thread (row i < T, tile) row transform, bias, activation -> LDS row image [T][32 tiles x T pixels]
 //           pass 3 all threads              pixel-contiguous stores of the T rows (+ the 2x2 max pool of the tile rows, T even)
-template <int T, int NTL>
+// ADD: the layer has an addend source (ConvDesc::add) in place of its bias -- a variant of its own; pass 2 leaves the raw sums and
+// pass 3 adds the addend, read at the stored pixel's place in its window (as contiguous as the stores), then activates.  Output
+// pixel (y, x) of image b: element origin_add[b] + y * W_add + x of plane q of `add`
+template <int T, int NTL, bool ADD = false>
 __global__ __launch_bounds__(NTL * (T + 2)) void k_wino_out2(const f32x4 *__restrict__ m, long mnp, long mbs, int B, int TY, int TX, int Hv,
                                                              int Wv, const float *__restrict__ bias, int act, float slope_imm,
                                                              const float *__restrict__ slope_dev, f32x4 *__restrict__ out, long onp,
                                                              int out_plane0, long out_img_stride, int Wo, int opad, f32x4 *__restrict__ pool, long pnp,
-                                                             int Hp, int Wp, int ppad) {
+                                                             int Hp, int Wp, int ppad, const f32x4 *__restrict__ add = nullptr, long add_np = 0,
+                                                             const int *__restrict__ origin_add = nullptr, int W_add = 0) {
     constexpr int A = Wino<T>::A, RS = T * A + 1, NTH = NTL * A;
     __shared__ f32x4 sr[NTL * RS];
     __shared__ f32x4 so[T][NTL * T];
     const long tiles = (long)B * TY * TX;
     const long t0 = (long)blockIdx.x * NTL;
     const int q = blockIdx.y;
-    const f32x4 bv = *(const f32x4 *)(bias + 4 * q);
+    const f32x4 bv = ADD ? f32x4{0.f, 0.f, 0.f, 0.f} : *(const f32x4 *)(bias + 4 * q);
     const float slope = act == ND_ACT_NONE ? 1.f : (slope_dev ? *slope_dev : slope_imm);
+    auto activate = [&](f32x4 y) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float u = y[e];
+            switch (act) {
+                case ND_ACT_ELU: y[e] = u > 0.f ? u : expm1f(u); break;
+                case ND_ACT_HARDSWISH: y[e] = u * fminf(fmaxf(u + 3.f, 0.f), 6.f) / 6.f; break;
+                default: y[e] = u > 0.f ? u : u * slope; break;   // PReLU; "none" is slope 1
+            }
+        }
+        return y;
+    };
     {
         const int j = threadIdx.x / NTL, tl = threadIdx.x % NTL;
         const long t = t0 + tl;
@@ -333,17 +349,7 @@ __global__ __launch_bounds__(NTL * (T + 2)) void k_wino_out2(const f32x4 *__rest
             Wino<T>::at(r, o);
 #pragma unroll
             for (int j = 0; j < T; ++j) {
-                f32x4 y = o[j] + bv;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float u = y[e];
-                    switch (act) {
-                        case ND_ACT_ELU: y[e] = u > 0.f ? u : expm1f(u); break;
-                        case ND_ACT_HARDSWISH: y[e] = u * fminf(fmaxf(u + 3.f, 0.f), 6.f) / 6.f; break;
-                        default: y[e] = u > 0.f ? u : u * slope; break;   // PReLU; "none" is slope 1
-                    }
-                }
-                so[i][tl * T + j] = y;
+                so[i][tl * T + j] = ADD ? o[j] : activate(o[j] + bv);
             }
         }
     }
@@ -356,9 +362,13 @@ __global__ __launch_bounds__(NTL * (T + 2)) void k_wino_out2(const f32x4 *__rest
         int tx, ty, b;
         tile_pos(tt, TX, TY, tx, ty, b);
         const int xx = T * tx + pp % T, yy = T * ty + i;
-        if (xx < Wv && yy < Hv) dst[(long)b * out_img_stride + (long)(yy + opad) * Wo + xx + opad] = so[i][pp];
+        if (xx < Wv && yy < Hv) {
+            f32x4 y = so[i][pp];
+            if constexpr (ADD) y = activate(y + add[(long)q * add_np + (long)origin_add[b] + (long)yy * W_add + xx]);
+            dst[(long)b * out_img_stride + (long)(yy + opad) * Wo + xx + opad] = y;
+        }
     }
-    if (pool) {   // fused MaxPool2d(2): tiles start on even pixels and T is even, so every 2x2 block lies inside one tile
+    if (!ADD && pool) {   // fused MaxPool2d(2): tiles start on even pixels and T is even, so every 2x2 block lies inside one tile
         f32x4 *pd = pool + (long)q * pnp;
         for (int idx = threadIdx.x; idx < (T / 2) * NTL * (T / 2); idx += NTH) {
             const int a = idx / (NTL * (T / 2)), pp = idx - a * (NTL * (T / 2));
@@ -479,6 +489,11 @@ int nd_launch_conv_wino(int T, const ConvDesc &d, void *scratch, size_t scratch_
         ND_FAIL(ND_EINVAL, "winograd: fp32 3x3 layers only");
     if (d.cin % 16 || d.cout % 4) ND_FAIL(ND_EINVAL, "winograd: Cin must be a multiple of 16, Cout of 4 (got %d, %d)", d.cin, d.cout);
     if (d.pre) ND_FAIL(ND_EINVAL, "winograd: inference only (no pre-activation copy)");
+    const bool add = d.add.base != nullptr;
+    if ((add || d.w_kb) && T != 6) ND_FAIL(ND_EINVAL, "winograd: only the F(6x6) form takes an addend source or a K-block sub-range");
+    if (add && (d.pool || d.in2.base)) ND_FAIL(ND_EINVAL, "winograd: a layer with an addend source is neither pooled nor has a second input source");
+    if (d.w_kb && (d.w_kb0 < 0 || d.w_kb0 + nd_kblocks(d.cin) > d.w_kb)) ND_FAIL(ND_EINVAL, "winograd: K blocks [%d,+%d) outside the %d of the packed weights", d.w_kb0, nd_kblocks(d.cin), d.w_kb);
+    const int cin_w = d.w_kb ? 8 * d.w_kb : d.cin;   // input channels the blob was packed for
     ND_TRY(nd_check_roi("winograd", d, d.in.Hb - 2, d.in.Wb - 2, T != 6 || d.pool, "a layer other than an unpooled F(6x6) one"));
     const bool roi = d.roi_rows > 0;
     const WinoGeo g = wino_geo(T, d.in, d.cin, d.cout, d.roi_rows, d.roi_cols);
@@ -488,6 +503,7 @@ int nd_launch_conv_wino(int T, const ConvDesc &d, void *scratch, size_t scratch_
         // (k_wino_in2 reads nothing outside the view of g.Hv + 2 rows x g.Wv + 2 pixels at the region's first pixel)
         ND_TRY(nd_check_in2("winograd", d, nd_kblocks(d.cin), (long)(d.roi_r0 + g.Hv + 1) * d.in2.Wb + d.roi_c0 + g.Wv + 2));
     }
+    if (add) ND_TRY(nd_check_add("winograd", d, (long)(d.roi_r0 + g.Hv - 1 + d.add.pad) * d.add.Wb + d.roi_c0 + g.Wv - 1 + d.add.pad + 1));
     ND_TRY(nd_check_out("winograd", d, d.in.Hb - 2, d.in.Wb - 2, false));
     // a region is the same three passes on shifted base pointers (input view: rows [r0, r0 + rows + 2) of the bordered buffer)
     const long roi_in = roi ? (long)d.roi_r0 * d.in.Wb + d.roi_c0 : 0, roi_out = roi ? (long)d.roi_r0 * d.out.Wb + d.roi_c0 : 0;
@@ -521,7 +537,9 @@ int nd_launch_conv_wino(int T, const ConvDesc &d, void *scratch, size_t scratch_
     e.cin = d.cin;
     e.cout = d.cout;
     e.wpk = d.wpk;
-    e.bias = d.wpk + nd_bias_offset(ND_CONV1, d.cin, d.cout);   // the zero bias of position 0
+    e.bias = d.wpk + nd_bias_offset(ND_CONV1, cin_w, d.cout);   // the zero bias of position 0
+    e.w_kb = d.w_kb;
+    e.w_kb0 = d.w_kb0;
     e.in = {(float *)v, in_planes, d.in.B, g.TY, g.TX, 0, g.vnp, ND_F32};
     e.out = {(float *)m, out_planes, d.in.B, g.TY, g.TX, 0, g.mnp, ND_F32};
     e.variant = nd_conv_variant_gemm(d.cin, d.cout);
@@ -531,11 +549,11 @@ int nd_launch_conv_wino(int T, const ConvDesc &d, void *scratch, size_t scratch_
     e.nbatch = P;
     e.in_bs = g.vbs;
     e.out_bs = g.mbs;
-    e.w_bs = gemm_floats(d.cin, d.cout);
+    e.w_bs = gemm_floats(cin_w, d.cout);
     ND_TRY(nd_launch_conv(e, s));
     if (ev2) ND_HIP(hipEventRecord(ev2[1], s));
 
-    const float *bias = d.wpk + (size_t)P * gemm_floats(d.cin, d.cout);
+    const float *bias = d.wpk + (size_t)P * gemm_floats(cin_w, d.cout);
     dim3 go((unsigned)((g.tiles + 127) / 128), out_planes);
     f32x4 *out = (f32x4 *)d.out.base + roi_out;
     f32x4 *pool = nullptr;
@@ -551,7 +569,14 @@ int nd_launch_conv_wino(int T, const ConvDesc &d, void *scratch, size_t scratch_
         Wp = q.Wb;
         ppad = q.pad;
     }
-    if (T == 6 && kOutNtl == 16) {
+    if (add) {
+        const f32x4 *ap = (const f32x4 *)d.add.base + (long)d.add_plane0 * d.add.np() + (long)((roi ? d.roi_r0 : 0) + d.add.pad) * d.add.Wb +
+                          (roi ? d.roi_c0 : 0) + d.add.pad;
+        dim3 go2((unsigned)((g.tiles + 31) / 32), out_planes);
+        hipLaunchKernelGGL((k_wino_out2<6, 32, true>), go2, dim3(256), 0, s, (const f32x4 *)m, g.mnp, g.mbs, d.in.B, g.TY, g.TX, g.Hv, g.Wv, bias,
+                           d.act, d.slope, d.slope_dev, out, d.out.np(), d.out_plane0, (long)d.out.Hb * d.out.Wb, d.out.Wb, d.out.pad, nullptr, 0L, 0, 0, 0,
+                           ap, d.add.np(), d.add_origin, d.add.Wb);
+    } else if (T == 6 && kOutNtl == 16) {
         dim3 go2((unsigned)((g.tiles + 15) / 16), out_planes);
         hipLaunchKernelGGL((k_wino_out2<6, 16>), go2, dim3(128), 0, s, (const f32x4 *)m, g.mnp, g.mbs, d.in.B, g.TY, g.TX, g.Hv, g.Wv, bias,
                            d.act, d.slope, d.slope_dev, out, d.out.np(), d.out_plane0, (long)d.out.Hb * d.out.Wb, d.out.Wb, d.out.pad, pool, pnp, Hp, Wp, ppad);

@@ -134,6 +134,8 @@ class UtNet(nn.Module):
     #                            once per band of tile rows (fp32 useful-region mode; same canvas up to fp32 re-association)
     #   share_level2 = False -> A/B switch: the shared loop keeps the third encoder level (convs3.x) per tile where it would run it
     #                           once per band too (nd_utnet_frame_levels: 3; same canvas up to fp32 re-association)
+    #   fold_skips = False -> A/B switch: the shared loop keeps the skip halves of tconvs4.0 / 3.0 / 2.0 in the per-tile sums where it
+    #                         would compute their products once per band (nd_utnet_frame_folds; same canvas up to fp32 re-association)
     split_k = True
     winograd = True
     w1d_regs = False
@@ -141,6 +143,7 @@ class UtNet(nn.Module):
     fused_pool = True
     share_encoder = True
     share_level2 = True
+    fold_skips = True
 
     def __init__(self, funit=64, activation='PReLU', compute_dtype='f32'):
         super().__init__()
@@ -198,8 +201,8 @@ class UtNet(nn.Module):
 
     @property
     def frame_flags(self):
-        """flags of the frame-loop entry points (nd_utnet_frame_*, nd_utnet_denoise_frame): they alone take FLAG_TILE_LEVEL2."""
-        return self.flags | (0 if self.share_level2 else _lib.FLAG_TILE_LEVEL2)
+        """flags of the frame-loop entry points (nd_utnet_frame_*, nd_utnet_denoise_frame): they alone take FLAG_TILE_LEVEL2 and FLAG_TILE_SKIPS."""
+        return self.flags | (0 if self.share_level2 else _lib.FLAG_TILE_LEVEL2) | (0 if self.fold_skips else _lib.FLAG_TILE_SKIPS)
 
     # ------------------------------------------------------------------ weights
     def _weights_key(self, device):
