@@ -82,7 +82,7 @@ typedef enum nd_flags {
                                  nd_unet_denoise_frame: the same switch for the UNet decoder (nd_unet_useful_region)             */
 } nd_flags;
 
-int nd_version(void);   /* 110 = this header */
+int nd_version(void);   /* 111 = this header */
 const char *nd_last_error(void);
 
 /* ---------------------------------------------------------------- tile geometry (host, pure integer)
@@ -358,6 +358,20 @@ int nd_mse(const float *x, const float *y, size_t count, float *out, void *works
 size_t nd_ssim_loss_workspace_bytes(int n, int c, int h, int w);
 int nd_ssim_loss_grad(const float *x, const float *y, int n, int c, int h, int w, int multiscale, float weight,
                       float *loss_acc, float *gx, int accumulate, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The SSIM the reference vendors itself (libs/pytorch_ssim/__init__.py:20-35; loss.py:29-45 gen_score writes res.txt with it).
+ * Not the piqa score above: the Gaussian (sigma 1.5, `window` taps) is applied with zero padding of window / 2, so the map is
+ * h x w and border pixels see zeros.   out[i] = mean over (c, h, w) of the map of sample i.
+ * window: odd, 3 ... 11 (ND_EINVAL otherwise: an even window makes the reference's map one row and column larger).  Any
+ * h, w >= 1: an image smaller than the window is defined by the padding.
+ * nd_ssim_padded_grad: gx = sum_i gout[i] * d out[i] / dx with y constant; gout: float32 [n] in HBM, gx: float32 [n, c, h, w],
+ * overwritten.  Both calls take the workspace of nd_ssim_padded_workspace_bytes (ND_ENOMEM if it is smaller) and are
+ * deterministic: partial sums are added in a fixed order. */
+size_t nd_ssim_padded_workspace_bytes(int n, int c, int h, int w, int window);
+int nd_ssim_padded(const float *x, const float *y, int n, int c, int h, int w, int window, float *out, void *workspace,
+                   size_t workspace_bytes, void *stream);
+int nd_ssim_padded_grad(const float *x, const float *y, int n, int c, int h, int w, int window, const float *gout, float *gx,
+                        void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- Winograd forms of a 3x3 layer, fp32 inference (same math as nd_layer_forward on a CONV3 / CONVT3 layer, re-associated).
  * tile = 2 | 4 | 6: three-pass F(tile x tile, 3 x 3) (input transform, one launch of (tile+2)^2 GEMMs, output transform;

@@ -112,6 +112,9 @@ _SIGNATURES = {
     "nd_ssim_loss_workspace_bytes": (c_size_t, [c_int] * 4),
     "nd_ssim_loss_grad": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_float, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
                                   c_void_p]),
+    "nd_ssim_padded_workspace_bytes": (c_size_t, [c_int] * 5),
+    "nd_ssim_padded": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nd_ssim_padded_grad": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nd_mse": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nd_conv_bench": (c_int, [c_int] * 9 + [c_void_p, c_size_t, c_void_p, POINTER(c_float)]),
     "nd_winograd_bench": (c_int, [c_int] * 8 + [c_void_p, c_size_t, c_void_p, POINTER(c_float)]),

@@ -22,7 +22,11 @@ def img_path_to_np_flt(fpath):
     shape: c, y, x'''
     if not os.path.isfile(fpath):
         raise FileNotFoundError(fpath)
-    img = _read_hwc(fpath)
+    return hwc_to_np_flt(_read_hwc(fpath), fpath)
+
+
+def hwc_to_np_flt(img, fpath='<array>'):
+    '''the conversion of img_path_to_np_flt on decoded samples (HW or HWC; uint8, uint16 or float32)'''
     if img.ndim == 2:
         img = img[:, :, None]
     if img.shape[2] == 1:                      # IMREAD_COLOR semantics: gray is replicated

@@ -11,8 +11,8 @@ crop -> infer -> stitch loop in this process (denoise_image.denoise_file), and M
 to <model dir>/trainres.json and testres.json under the 'test_' prefix (json_saver.JSONSaver).
 
 Known reference defects not reproduced (they make its script crash before any result is written): utilities.avg_listofdicts
-returns None; JSONSaver.add_res(key_prefix=...) iterates res.values().  The obsolete loss.gen_score tail (--no_scoring,
-needs the pytorch_ssim package) is accepted as a flag and skipped with a message.
+returns None; JSONSaver.add_res(key_prefix=...) iterates res.values().  The loss.gen_score tail (denoise_dir.py:131-132: res.txt
+beside the outputs, scored with the reference's own pytorch_ssim) runs when --gen_score is given; --no_scoring is accepted.
 '''
 import argparse
 import os
@@ -35,6 +35,7 @@ def build_parser():
     parser.add_argument('--model_parameters', default="", type=str, help='Model parameters with format "parameter1=value1,parameter2=value2" (UtNet: funit, activation, compute_dtype=f32|bf16|f16; see denoise_image --help)')
     parser.add_argument('--result_dir', default='../../results/NIND/test', type=str, help='directory where results are saved. Can also be set to "make_subdirs" to make a denoised/<model_directory_name> subdirectory')
     parser.add_argument('--no_scoring', action='store_true', help='Skip the obsolete res.txt scoring pass')
+    parser.add_argument('--gen_score', action='store_true', help='Run the res.txt scoring pass (loss.gen_score: pytorch_ssim SSIM and MSE of every output against its set\'s base ISO) at the end')
     parser.add_argument('--cs', type=str)
     parser.add_argument('--ucs', type=str)
     parser.add_argument('-ol', '--overlap', default=6, type=int, help='Merge crops with this much overlap (denoise_image default)')
@@ -155,8 +156,11 @@ def main(argv=None):
         json_res_fpath = os.path.join(model_root, 'testres.json')
         print(f'results will be dumped to {json_res_fpath}.')
         utilities.dict_to_json(losses_per_set, json_res_fpath)
-    if not args.no_scoring:
-        print('denoise_dir: the obsolete res.txt scoring pass (loss.gen_score, needs pytorch_ssim) is not run; '
+    if args.gen_score:
+        from . import loss
+        loss.gen_score(denoised_save_dir, args.noisy_dir, device=device)
+    elif not args.no_scoring:
+        print('denoise_dir: the obsolete res.txt scoring pass (loss.gen_score) is not run without --gen_score; '
               'the scores above come from pt_helpers.get_losses')
     return losses_per_set
 

@@ -114,3 +114,24 @@ def make_frame(width, height, seed=24, gradient=True):
         xx = np.linspace(0, 1, width, dtype=np.float32)[None, None, :]
         img = (np.float32(0.5) * img + np.float32(0.25) * yy + np.float32(0.25) * xx).astype(np.float32)
     return img
+
+
+def make_ssim_pair(n, c, h, w, kind, seed, sigma=0.05):
+    """Two float32 [n,c,h,w] images in [0,1] for the score tests (the fixture holds their SHA-256, not the arrays).
+    'noisy': crops of make_frame(seed + sample) vs the same + N(0, sigma) from np.random.RandomState(seed), clipped;
+    'q8': the 'noisy' pair with both images quantised to k / 255;  'indep': two uniform images;
+    'const': 0.25 everywhere vs 0.75 everywhere;  'const_near': 0.6 vs 0.61."""
+    shape = (n, c, h, w)
+    rs = np.random.RandomState(seed)
+    if kind == "indep":
+        return rs.random_sample(shape).astype(np.float32), rs.random_sample(shape).astype(np.float32)
+    if kind in ("const", "const_near"):
+        a, b = (0.25, 0.75) if kind == "const" else (0.6, 0.61)
+        return np.full(shape, a, dtype=np.float32), np.full(shape, b, dtype=np.float32)
+    if kind not in ("noisy", "q8"):
+        raise ValueError(f"unknown pair kind {kind!r}")
+    x = np.stack([make_frame(w + 8, h + 8, seed=seed + i)[:c, 4:4 + h, 4:4 + w] for i in range(n)]).astype(np.float32)
+    y = np.clip(x + np.float32(sigma) * rs.standard_normal(shape).astype(np.float32), 0, 1).astype(np.float32)
+    if kind == "q8":
+        x, y = (np.round(a * 255).astype(np.uint8).astype(np.float32) / np.float32(255) for a in (x, y))
+    return np.ascontiguousarray(x), np.ascontiguousarray(y)
