@@ -29,7 +29,8 @@ int nd_launch_channel_sum(const QpBuf &src, int plane0, int C, float *out, float
 // ------------------------------------------------------------------ elementwise kernels
 // g (interior of a bordered gradient buffer, planes [plane0, plane0+planes)) *= act'(pre), pre = conv output + bias;
 // PReLU also: partial[block] = sum g*pre over pre <= 0 (the slope's gradient).  ELU: act' = 1 | exp(pre); Hardswish: 0 | (2 pre + 3) / 6 | 1
-// (torch's derivative at the break points: ELU'(0) = 1 from the exp branch, Hardswish' = 0 at -3 and 1 at +3 are not reached by (2x+3)/6 -- see below)
+// (torch's derivative at the break points: PReLU'(0) = slope, ELU'(0) = 1 from the exp branch, Hardswish'(-3) = 0 and Hardswish'(+3) = 1:
+// the middle branch (2x+3)/6, which would give -1/2 and 3/2 there, holds on the open interval only -- see below)
 template <int ACT>
 __global__ __launch_bounds__(256) void k_act_bwd(f32x4 *__restrict__ g, long gnp, int gHb, int gWb, int gpad,
                                                  const f32x4 *__restrict__ pre, long pnp, int H, int W,
@@ -53,8 +54,8 @@ __global__ __launch_bounds__(256) void k_act_bwd(f32x4 *__restrict__ g, long gnp
             } else if (ACT == ND_ACT_ELU) {
                 if (!(pv[e] > 0.f)) gv[e] *= expf(pv[e]);                     // torch: grad * (x <= 0 ? alpha * exp(x) : 1), alpha = 1
             } else {
-                // torch hardswish_backward: x < -3 -> 0;  x <= 3 -> grad * (x / 3 + 0.5);  else grad
-                gv[e] = pv[e] < -3.f ? 0.f : (pv[e] <= 3.f ? gv[e] * (pv[e] / 3.f + 0.5f) : gv[e]);
+                // torch hardswish_backward: x <= -3 -> 0;  x < 3 -> grad * (x / 3 + 0.5);  else grad
+                gv[e] = pv[e] <= -3.f ? 0.f : (pv[e] < 3.f ? gv[e] * (pv[e] / 3.f + 0.5f) : gv[e]);
             }
         }
         *gp = gv;
