@@ -58,7 +58,9 @@ typedef enum nd_dtype {
 typedef enum nd_flags {
     ND_FLAG_NO_SPLITK = 1,    /* keep every output tile whole: no split-K tail, so a tile's bits do not depend on which other
                                  tiles share its launch (the default splits the K loop of a launch's last, partial round of
-                                 workgroups over the idle CUs: deterministic, but fp32 sums re-associate by <= 1e-5)        */
+                                 workgroups over the idle CUs: deterministic, but fp32 sums re-associate by <= 1e-5).  It also
+                                 keeps the three-pass Winograd layers on per-image tile grids: a tile's place in a mosaic
+                                 (ND_FLAG_TILE_WINO) depends on which images share its launch                                 */
     ND_FLAG_DIRECT_CONV = 2,  /* direct convolution on every 3x3 layer (default on the fp32 path: Winograd F(6x6,3x3) from
                                  128 channels up, 1-D F(4,3) inside the implicit-GEMM kernel below; ~1e-5 re-association)   */
     ND_FLAG_W1D_REGS = 4,     /* A/B switch: the 1-D F(4,3) layers through the kernel that transforms in registers (conv_w1d)
@@ -75,6 +77,10 @@ typedef enum nd_flags {
     ND_FLAG_TILE_SKIPS = 256,  /* A/B switch: nd_utnet_denoise_frame keeps the skip halves of tconvs4.0 / 3.0 / 2.0 in the per-tile sums
                                  where it would compute their products once per band (nd_utnet_frame_folds).  Taken by the
                                  frame-loop entry points only; an unknown bit everywhere else                                      */
+    ND_FLAG_TILE_WINO = 512,   /* A/B switch: every three-pass F(6x6,3x3) layer tiles each image on its own (default: the small
+                                 ConvTranspose2d(3) layers of a launch -- bottom.2, tconvs1.0 at cs 264 -- under one tile grid over a
+                                 mosaic of the launch's images, nd_wino_mosaic; fp32 re-association in the tiles that straddle a seam).  Taken by every
+                                 flags-taking entry point                                                                         */
     ND_FLAG_FULL_TILES = 8    /* nd_utnet_denoise_tiles / nd_utnet_profile_stack: compute every layer on the whole tile, as
                                  UtNet.forward does.  Default there: the last decoder levels compute only the pixels that the
                                  useful crop [pad, cs - pad) of a tile can reach (denoise_image.py:249-258 discards the rest of
@@ -82,7 +88,7 @@ typedef enum nd_flags {
                                  nd_unet_denoise_frame: the same switch for the UNet decoder (nd_unet_useful_region)             */
 } nd_flags;
 
-int nd_version(void);   /* 111 = this header */
+int nd_version(void);   /* 112 = this header */
 const char *nd_last_error(void);
 
 /* ---------------------------------------------------------------- tile geometry (host, pure integer)
@@ -378,6 +384,14 @@ int nd_ssim_padded_grad(const float *x, const float *y, int n, int c, int h, int
  *               Cin % 16 == 0; agrees with the direct kernel to ~1e-6 / ~1e-5 / ~2e-5 relative);
  * tile = 1 | 3: 1-D F(2,3) | F(4,3) along x inside the implicit-GEMM kernel, transform in registers (~1e-6 / ~5e-6);
  * tile = 5    : the same F(4,3) form with the input transform shared by the workgroup through LDS (conv_w2d). */
+/* The mosaic a three-pass F(6x6,3x3) launch of B images of a ConvTranspose2d(3) layer with p x p outputs (p = input + 2) lays its
+ * tile grid over: by rows of bx images at pitch p, whose shared zero border lines make the mosaic's transposed convolution the
+ * per-image results side by side.  Every bx in [1, B] with by = ceil(B / bx) is tried and the fewest tiles win; a count within 1 %
+ * of the fewest is a tie, and ties go to the squarer mosaic ((13, 256): 16 x 16 with 1225 tiles, not 43 x 6 with 1222).  Returns 1 and the mosaic where a launch takes one (p >= 8, B > 1, *tiles <= 0.9 *tiles_per_image;
+ * the launch must also be whole-tensor, square, unpooled, single-source and without ND_FLAG_NO_SPLITK / ND_FLAG_TILE_WINO), else 0 with
+ * *bx = *by = 0 and *tiles = *tiles_per_image = B * ceil(p / 6)^2.  Host only, pure integer; a function of (p, B) alone. */
+int nd_wino_mosaic(int p, int B, int *bx, int *by, long *tiles, long *tiles_per_image);
+
 size_t nd_winograd_packed_bytes(int tile, int cin, int cout);
 int nd_winograd_pack(int tile, int kind, int cin, int cout, const float *w, const float *bias, void *packed,
                      size_t packed_bytes);
@@ -394,6 +408,9 @@ int nd_conv_bench(int kind, int dtype, int batch, int cin, int cout, int h, int 
 
 int nd_winograd_bench(int tile, int kind, int batch, int cin, int cout, int h, int w, int iters, void *workspace,
                       size_t workspace_bytes, void *stream, float *mean_ms);
+/* the same with nd_flags (ND_FLAG_NO_SPLITK, ND_FLAG_TILE_WINO) */
+int nd_winograd_bench_flags(int tile, int kind, int batch, int cin, int cout, int h, int w, int iters, int flags, void *workspace,
+                            size_t workspace_bytes, void *stream, float *mean_ms);
 
 /* Name and average duration bookkeeping for bench.py: number of conv-kernel variants compiled in. */
 int nd_num_conv_variants(void);

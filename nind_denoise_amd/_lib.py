@@ -4,7 +4,7 @@ There is NO CPU fallback: if the shared library is missing or a call fails, an e
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libnind_hip.so")
@@ -17,6 +17,7 @@ KIND = {"conv3": 0, "convT3": 1, "convT2s2": 2, "conv1": 3, "conv2s2": 4}
 FLAG_NO_SPLITK, FLAG_DIRECT_CONV, FLAG_W1D_REGS, FLAG_FULL_TILES, FLAG_UNFUSED_POOL, FLAG_TILE_ENCODER, FLAG_TILE_LEVEL2 = 1, 2, 4, 8, 16, 32, 64
 FLAG_FIND_NOISE = 128   # nd_unet_denoise_frame only
 FLAG_TILE_SKIPS = 256   # frame-loop entry points only: the skip halves of tconvs4.0 / 3.0 / 2.0 stay in the per-tile sums
+FLAG_TILE_WINO = 512    # every three-pass Winograd layer on per-image tile grids (no mosaic of the launch's images: nd_wino_mosaic)
 # nd_progress_fn: (ctx, launch index, first tile, tile count)
 PROGRESS_FN = ctypes.CFUNCTYPE(None, c_void_p, c_int, c_int, c_int)
 
@@ -118,6 +119,8 @@ _SIGNATURES = {
     "nd_mse": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nd_conv_bench": (c_int, [c_int] * 9 + [c_void_p, c_size_t, c_void_p, POINTER(c_float)]),
     "nd_winograd_bench": (c_int, [c_int] * 8 + [c_void_p, c_size_t, c_void_p, POINTER(c_float)]),
+    "nd_winograd_bench_flags": (c_int, [c_int] * 9 + [c_void_p, c_size_t, c_void_p, POINTER(c_float)]),
+    "nd_wino_mosaic": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_long), POINTER(c_long)]),
     "nd_num_conv_variants": (c_int, []),
     "nd_conv_variant_name": (c_char_p, [c_int]),
 }

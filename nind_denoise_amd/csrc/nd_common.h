@@ -67,6 +67,7 @@ struct ConvDesc {
     float *part = nullptr;  // scratch for the split-K tail (raw accumulators of K slices); null: never split
     size_t part_bytes = 0;
     bool nosplit = false;   // ND_FLAG_NO_SPLITK of the call: keep every tile whole (bits independent of the launch composition)
+    bool tile_wino = false;  // ND_FLAG_TILE_WINO of the call: a three-pass layer tiles every image on its own (no mosaic, winograd.hip)
     int nbatch = 1;         // independent problems of this shape in one launch (Winograd positions)
     long in_bs = 0, out_bs = 0;   // 16-byte elements between consecutive problems' input / output buffers
     size_t w_bs = 0;        // floats between consecutive problems' packed weights (the bias is shared)
@@ -119,8 +120,11 @@ int nd_wino_pack(int T, int kind, int cin, int cout, const float *w, const float
 size_t nd_wino_scratch_bytes(int T, const QpBuf &in, int cin, int cout);
 // ev2 (optional, profiling): two events, recorded after the input transform pass and after the GEMM launch
 int nd_launch_conv_wino(int T, const ConvDesc &d, void *scratch, size_t scratch_bytes, hipStream_t s, hipEvent_t *ev2 = nullptr);
-// algorithmic HBM bytes of the two transform passes of a three-pass layer (X read + V written; M read + Y written)
-void nd_wino_xform_bytes(int T, const QpBuf &in, int cin, int cout, double *bytes_in, double *bytes_out);
+// F(T x T) tiles the launch of d runs: per image, or those of the mosaic where the launch takes one (nd_wino_mosaic)
+long nd_wino_launch_tiles(int T, const ConvDesc &d);
+// algorithmic HBM bytes of the two transform passes of a three-pass layer (X read + V written; M read + Y written); tiles: what its
+// launches ran (nd_wino_launch_tiles; 0: per-image grids)
+void nd_wino_xform_bytes(int T, const QpBuf &in, int cin, int cout, long tiles, double *bytes_in, double *bytes_out);
 // 1-D Winograd F(2,3) along x inside the implicit-GEMM kernel (conv_w1d.hip): fp32 inference form of the narrow 3x3 layers
 // (T = 2: F(2,3), 2/3 of the MFMAs;  T = 4: F(4,3), 1/2)
 size_t nd_w1d_packed_floats(int T, int cin, int cout);
@@ -161,7 +165,7 @@ int nd_check_roi(const char *who, const ConvDesc &d, int Hv, int Wv, bool refuse
 // ND_FLAG_TILE_SKIPS, which mean nothing anywhere else; unet_frame: nd_unet_denoise_frame also takes ND_FLAG_FIND_NOISE
 static inline int nd_check_flags(int flags, bool frame_loop = false, bool unet_frame = false) {
     const int known = ND_FLAG_NO_SPLITK | ND_FLAG_DIRECT_CONV | ND_FLAG_W1D_REGS | ND_FLAG_FULL_TILES | ND_FLAG_UNFUSED_POOL |
-                      ND_FLAG_TILE_ENCODER | (frame_loop ? ND_FLAG_TILE_LEVEL2 | ND_FLAG_TILE_SKIPS : 0) | (unet_frame ? ND_FLAG_FIND_NOISE : 0);
+                      ND_FLAG_TILE_ENCODER | ND_FLAG_TILE_WINO | (frame_loop ? ND_FLAG_TILE_LEVEL2 | ND_FLAG_TILE_SKIPS : 0) | (unet_frame ? ND_FLAG_FIND_NOISE : 0);
     if (flags & ~known) ND_FAIL(ND_EINVAL, "unknown flag bits 0x%x", flags);
     return ND_OK;
 }

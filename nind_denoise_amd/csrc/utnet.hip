@@ -496,6 +496,8 @@ extern "C" int nd_utnet_profile_stack(int funit, int act, int dtype, int flags, 
     opts.flags = flags;
     opts.ev = ev;
     opts.ev_x = evx;
+    long tiles_run[kNumSteps] = {};
+    opts.wino_tiles = tiles_run;
     if (!(flags & ND_FLAG_FULL_TILES) && plan_rois(pl, crop, crop, rois) && rois_supported(funit, dtype, flags, pl, bl, rois)) opts.rois = rois;
     int rc = run_stack(funit, act, dtype, (const float *)packed, pl, s, opts);
     if (rc == ND_OK) {
@@ -543,10 +545,16 @@ extern "C" int nd_utnet_profile_stack(int funit, int act, int dtype, int flags, 
         o.flops *= B;
         o.bytes = B * esz * (ci * hin * win + co * hout * wout) + 4.0 * ci * co * nd_taps(l.kind);
         auto cdiv = [](double a, double b) { return (double)(long)((a + b - 1) / b); };
+        long wino_tiles = 0;
         switch (form) {
             case FORM_W1D4: o.mfma_flops = 2.0 * 3 * 6 * cip * co * hout * cdiv(wout, 4) * B; break;
             case FORM_W1D2: o.mfma_flops = 2.0 * 3 * 4 * cip * co * hout * cdiv(wout, 2) * B; break;
-            case FORM_WINO3P: o.mfma_flops = 2.0 * (kWinoTile + 2) * (kWinoTile + 2) * cip * co * cdiv(hout, kWinoTile) * cdiv(wout, kWinoTile) * B; break;
+            case FORM_WINO3P: {
+                // the tiles its launches ran, as run_stack recorded them: per-image grids or a mosaic's (nd_wino_mosaic)
+                wino_tiles = tiles_run[i];
+                o.mfma_flops = 2.0 * (kWinoTile + 2) * (kWinoTile + 2) * cip * co * (double)wino_tiles;
+                break;
+            }
             default:
                 o.mfma_flops = l.kind == ND_CONVT2S2 ? 2.0 * 4 * cip * co * hin * win * B
                                                      : 2.0 * nd_taps(l.kind) * cip * co * hout * wout * B;   // (zero-border MACs of a transposed layer included)
@@ -565,7 +573,7 @@ extern "C" int nd_utnet_profile_stack(int funit, int act, int dtype, int flags, 
                 v.Hb = opts.rois[i].rows + 2;
                 v.Wb = opts.rois[i].cols + 2;
             }
-            nd_wino_xform_bytes(kWinoTile, v, (int)ci, (int)co, &o.xform_bytes_in, &o.xform_bytes_out);
+            nd_wino_xform_bytes(kWinoTile, v, (int)ci, (int)co, wino_tiles, &o.xform_bytes_in, &o.xform_bytes_out);
         }
     }
     return rc;
@@ -715,6 +723,7 @@ int layer_forward(const LayerForm &fm, int kind, int act, float slope, int dt, c
     d.slope = slope;
     d.variant = variant;
     d.nosplit = (flags & ND_FLAG_NO_SPLITK) != 0;
+    d.tile_wino = (flags & ND_FLAG_TILE_WINO) != 0;
     ND_TRY(launch_form(fm, d, (char *)ws + pl.bytes, ws_bytes - pl.bytes, s));
     return nd_launch_qp_to_nchw(pl.out, 0, y, cout, s);
 }
@@ -883,6 +892,11 @@ extern "C" const char *nd_conv_variant_name(int v) { return nd_conv_variant_labe
 // workspace: nd_layer_winograd_workspace_bytes + nd_winograd_packed_bytes + 256 B
 extern "C" int nd_winograd_bench(int tile, int kind, int batch, int cin, int cout, int h, int w, int iters, void *ws,
                                  size_t ws_bytes, void *stream, float *mean_ms) {
+    return nd_winograd_bench_flags(tile, kind, batch, cin, cout, h, w, iters, 0, ws, ws_bytes, stream, mean_ms);
+}
+extern "C" int nd_winograd_bench_flags(int tile, int kind, int batch, int cin, int cout, int h, int w, int iters, int flags, void *ws,
+                                       size_t ws_bytes, void *stream, float *mean_ms) {
+    ND_TRY(nd_check_flags(flags));
     const size_t need = nd_layer_winograd_workspace_bytes(tile, kind, batch, cin, cout, h, w);
     if (!need) ND_FAIL(ND_EINVAL, "nd_winograd_bench: bad shape / kind / tile");
     const LayerForm fm = wino_form(tile);
@@ -896,5 +910,7 @@ extern "C" int nd_winograd_bench(int tile, int kind, int batch, int cin, int cou
     ConvDesc d = layer_desc(fm, kind, cin, cout, ND_F32, wpk, pl);
     d.act = ND_ACT_PRELU;
     d.slope = 0.2f;
+    d.nosplit = (flags & ND_FLAG_NO_SPLITK) != 0;
+    d.tile_wino = (flags & ND_FLAG_TILE_WINO) != 0;
     return time_form("nd_winograd_bench", fm, d, (char *)ws + pl.bytes, need - pl.bytes, iters, s, mean_ms);
 }

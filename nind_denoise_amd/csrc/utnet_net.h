@@ -390,6 +390,8 @@ struct StackOpts {
     hipEvent_t *ev = nullptr;          // profiling: kNumSteps+1 events, ev[i] recorded before step i, ev[kNumSteps] after the last one
     hipEvent_t *ev_x = nullptr;        // profiling, with ev: 2 events per step, recorded after the input transform and after the
                                        // GEMMs of a three-pass layer
+    long *wino_tiles = nullptr;        // out (profiling), kNumSteps entries: the F(6x6) tiles the launches of a three-pass step ran
+                                       // (nd_wino_launch_tiles of every chunk: per image, or a mosaic's); the caller zeroes them
     // training forward (both set): the blob of blob_layout(f, dt, true)
     const QpBuf *pre = nullptr;                // kNumSlopes compact buffers that receive acc + bias of every activated layer
     const unsigned char *train_w1 = nullptr;   // per layer, 1 = the layer's blob region holds the fused 1-D Winograd packing
@@ -436,6 +438,7 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
         d.part = pl.split;
         d.part_bytes = kSplitScratchBytes;
         d.nosplit = (flags & ND_FLAG_NO_SPLITK) != 0;
+        d.tile_wino = (flags & ND_FLAG_TILE_WINO) != 0;
         const Form form = step_form(st, f, dt, flags, pl, bl, o.train_w1);
         if (o.rois && o.rois[this_step].rows > 0) {
             d.roi_r0 = o.rois[this_step].r0;
@@ -499,6 +502,7 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
                 if (d.add_origin) c.add_origin = d.add_origin + b0;
                 // (profiling: the split of a layer's time into its passes is recorded for a single-chunk layer only)
                 ND_TRY(nd_launch_conv_wino(kWinoTile, c, pl.wino, pl.wino_bytes, s, (o.ev_x && nimg <= kWinoChunk) ? o.ev_x + 2 * this_step : nullptr));
+                if (o.wino_tiles) o.wino_tiles[this_step] += nd_wino_launch_tiles(kWinoTile, c);
             }
             continue;
         }

@@ -247,15 +247,20 @@ __global__ __launch_bounds__(128) void k_wino_output(const f32x4 *__restrict__ m
 // float4 = 512 VGPRs).  32 tiles per workgroup, 32 * A threads.
 //   input : pass 1 thread (tile, column j)  loads d[0..A)[j] (A lanes = 16 A contiguous bytes per tile row), column transform -> LDS
 //           pass 2 thread (row i, tile)     row transform of r[i][0..A), A position stores, each 512 B contiguous per half wave
-template <int T, int NTL>
+// MOSAIC (ConvTranspose2d(3) layers, nd_wino_mosaic): ONE tile grid of TY x TX over the launch's B images laid side by side, logically
+// only, mby rows of mbx images at pitch mp = Hb - 2 = the layer's output size.  The two zero border lines behind an image are the two
+// in front of its neighbour, so logical bordered pixel (Y, X) is pixel (Y % mp, X % mp) of image (Y / mp) * mbx + X / mp's own bordered
+// plane, and zero past the last image; only the grid's far edges pad.  No second source in this form
+template <int T, int NTL, bool MOSAIC = false>
 __global__ __launch_bounds__(NTL * (T + 2)) void k_wino_in2(const f32x4 *__restrict__ x, long xnp, int Hb, int Wb, long img_stride, int row_stride, int B,
                                                             int TY, int TX, f32x4 *__restrict__ v, long vnp, long vbs, const f32x4 *__restrict__ x2,
-                                                            long x2np, int row_stride2, const int *__restrict__ origin2, int q2) {
+                                                            long x2np, int row_stride2, const int *__restrict__ origin2, int q2, int mp = 0,
+                                                            int mbx = 0, int mby = 0) {
     // Hb x Wb: extent of the (view of the) bordered input a tile may read; img_stride / row_stride: of the buffer it lives in.
     // Planes q >= q2 come from the second source (ConvDesc::in2): plane q - q2 of x2, image b at origin2[b], rows row_stride2 apart
     constexpr int A = Wino<T>::A, RS = A * A + 1;   // (+1: pass 2 reads a tile per lane, 16 (A*A+1) B apart: all banks)
     __shared__ f32x4 sm[NTL * RS];
-    const long tiles = (long)B * TY * TX;
+    const long tiles = MOSAIC ? (long)TY * TX : (long)B * TY * TX;
     const long t0 = (long)blockIdx.x * NTL;
     const int q = blockIdx.y;
     const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -265,6 +270,22 @@ __global__ __launch_bounds__(NTL * (T + 2)) void k_wino_in2(const f32x4 *__restr
         if (t < tiles) {
             int tx, ty, b;
     tile_pos(t, TX, TY, tx, ty, b);
+            if constexpr (MOSAIC) {
+                // one division for the thread's column, one for the tile's first row; mp >= A, so the A rows wrap at most once
+                const unsigned X = (unsigned)(T * tx + j), cx = X / (unsigned)mp, Y = (unsigned)(T * ty), cy = Y / (unsigned)mp;
+                const int lx = (int)(X - cx * (unsigned)mp), ly = (int)(Y - cy * (unsigned)mp);
+                const f32x4 *src = x + (long)q * xnp + lx;
+                f32x4 d[A], o[A];
+#pragma unroll
+                for (int i = 0; i < A; ++i) {
+                    const bool wrap = ly + i >= mp;
+                    const int cyi = (int)cy + (wrap ? 1 : 0), lyi = ly + i - (wrap ? mp : 0), bi = cyi * mbx + (int)cx;
+                    d[i] = ((int)cx < mbx && cyi < mby && bi < B) ? src[(long)bi * img_stride + (long)lyi * row_stride] : zero;
+                }
+                Wino<T>::bt(d, o);
+#pragma unroll
+                for (int i = 0; i < A; ++i) sm[tl * RS + i * A + j] = o[i];
+            } else {
             const bool s2 = q >= q2;   // block-uniform
             const long rs = s2 ? row_stride2 : row_stride;
             const f32x4 *src = (s2 ? x2 + (long)(q - q2) * x2np + origin2[b] : x + (long)q * xnp + (long)b * img_stride) + (long)(T * ty) * rs + T * tx + j;
@@ -275,6 +296,7 @@ __global__ __launch_bounds__(NTL * (T + 2)) void k_wino_in2(const f32x4 *__restr
             Wino<T>::bt(d, o);
 #pragma unroll
             for (int i = 0; i < A; ++i) sm[tl * RS + i * A + j] = o[i];
+            }
         }
     }
     __syncthreads();
@@ -299,17 +321,21 @@ __global__ __launch_bounds__(NTL * (T + 2)) void k_wino_in2(const f32x4 *__restr
 // ADD: the layer has an addend source (ConvDesc::add) in place of its bias -- a variant of its own; pass 2 leaves the raw sums and
 // pass 3 adds the addend, read at the stored pixel's place in its window (as contiguous as the stores), then activates.  Output
 // pixel (y, x) of image b: element origin_add[b] + y * W_add + x of plane q of `add`
-template <int T, int NTL, bool ADD = false>
+// MOSAIC (see k_wino_in2): the tiles cover mby x mbx images of Hv x Wv = mp x mp outputs side by side; pass 3 maps a stored pixel to
+// its image and its place there, and skips the slots past the last image.  Neither pooled nor with an addend
+template <int T, int NTL, bool ADD = false, bool MOSAIC = false>
 __global__ __launch_bounds__(NTL * (T + 2)) void k_wino_out2(const f32x4 *__restrict__ m, long mnp, long mbs, int B, int TY, int TX, int Hv,
                                                              int Wv, const float *__restrict__ bias, int act, float slope_imm,
                                                              const float *__restrict__ slope_dev, f32x4 *__restrict__ out, long onp,
                                                              int out_plane0, long out_img_stride, int Wo, int opad, f32x4 *__restrict__ pool, long pnp,
                                                              int Hp, int Wp, int ppad, const f32x4 *__restrict__ add = nullptr, long add_np = 0,
-                                                             const int *__restrict__ origin_add = nullptr, int W_add = 0) {
+                                                             const int *__restrict__ origin_add = nullptr, int W_add = 0, int mp = 0,
+                                                             int mbx = 0, int mby = 0) {
+    static_assert(!(MOSAIC && ADD), "the mosaic form has no addend");
     constexpr int A = Wino<T>::A, RS = T * A + 1, NTH = NTL * A;
     __shared__ f32x4 sr[NTL * RS];
     __shared__ f32x4 so[T][NTL * T];
-    const long tiles = (long)B * TY * TX;
+    const long tiles = MOSAIC ? (long)TY * TX : (long)B * TY * TX;
     const long t0 = (long)blockIdx.x * NTL;
     const int q = blockIdx.y;
     const f32x4 bv = ADD ? f32x4{0.f, 0.f, 0.f, 0.f} : *(const f32x4 *)(bias + 4 * q);
@@ -362,13 +388,17 @@ __global__ __launch_bounds__(NTL * (T + 2)) void k_wino_out2(const f32x4 *__rest
         int tx, ty, b;
         tile_pos(tt, TX, TY, tx, ty, b);
         const int xx = T * tx + pp % T, yy = T * ty + i;
-        if (xx < Wv && yy < Hv) {
+        if constexpr (MOSAIC) {
+            const unsigned cx = (unsigned)xx / (unsigned)mp, cy = (unsigned)yy / (unsigned)mp;
+            const int lx = xx - (int)cx * mp, ly = yy - (int)cy * mp, bi = (int)cy * mbx + (int)cx;
+            if ((int)cx < mbx && (int)cy < mby && bi < B) dst[(long)bi * out_img_stride + (long)(ly + opad) * Wo + lx + opad] = so[i][pp];
+        } else if (xx < Wv && yy < Hv) {
             f32x4 y = so[i][pp];
             if constexpr (ADD) y = activate(y + add[(long)q * add_np + (long)origin_add[b] + (long)yy * W_add + xx]);
             dst[(long)b * out_img_stride + (long)(yy + opad) * Wo + xx + opad] = y;
         }
     }
-    if (!ADD && pool) {   // fused MaxPool2d(2): tiles start on even pixels and T is even, so every 2x2 block lies inside one tile
+    if (!ADD && !MOSAIC && pool) {   // fused MaxPool2d(2): tiles start on even pixels and T is even, so every 2x2 block lies inside one tile
         f32x4 *pd = pool + (long)q * pnp;
         for (int idx = threadIdx.x; idx < (T / 2) * NTL * (T / 2); idx += NTH) {
             const int a = idx / (NTL * (T / 2)), pp = idx - a * (NTL * (T / 2));
@@ -396,11 +426,20 @@ size_t gemm_floats(int cin, int cout) { return nd_packed_floats(ND_CONV1, cin, c
 
 struct WinoGeo {
     int TY, TX, Hv, Wv;
-    long tiles;          // B * TY * TX
+    int mp = 0, mbx = 0, mby = 0;   // mosaic (mp > 0): TY x TX tiles over mby x mbx images at pitch mp = Hv = Wv
+    long tiles;          // B * TY * TX; a mosaic: TY * TX
     long vnp, mnp;       // plane strides (16-byte elements, with slack for the GEMM's DMA over-read)
     long vbs, mbs;       // position strides
     size_t v_bytes, m_bytes;
 };
+void wino_strides(int T, int cin, int cout, WinoGeo &g) {
+    g.vnp = g.mnp = g.tiles;
+    const long slack = 4096;
+    g.vbs = (long)(2 * nd_kblocks(cin)) * g.vnp + slack;
+    g.mbs = (long)((cout + 3) / 4) * g.mnp + slack;
+    g.v_bytes = (size_t)positions(T) * g.vbs * 16;
+    g.m_bytes = (size_t)positions(T) * g.mbs * 16;
+}
 WinoGeo wino_geo(int T, const QpBuf &in, int cin, int cout, int roi_rows = 0, int roi_cols = 0) {
     WinoGeo g;
     g.Hv = roi_rows > 0 ? roi_rows : in.Hb - 2;
@@ -408,12 +447,30 @@ WinoGeo wino_geo(int T, const QpBuf &in, int cin, int cout, int roi_rows = 0, in
     g.TY = (g.Hv + T - 1) / T;
     g.TX = (g.Wv + T - 1) / T;
     g.tiles = (long)in.B * g.TY * g.TX;
-    g.vnp = g.mnp = g.tiles;
-    const long slack = 4096;
-    g.vbs = (long)(2 * nd_kblocks(cin)) * g.vnp + slack;
-    g.mbs = (long)((cout + 3) / 4) * g.mnp + slack;
-    g.v_bytes = (size_t)positions(T) * g.vbs * 16;
-    g.m_bytes = (size_t)positions(T) * g.mbs * 16;
+    wino_strides(T, cin, cout, g);
+    return g;
+}
+// the mosaic of a launch, or none.  A function of the layer's shape and of what the launch carries -- never of its data
+bool wino_mosaic_rule(int T, const ConvDesc &d, int *bx, int *by, long *tiles) {
+    if (T != 6 || d.kind != ND_CONVT3 || d.tile_wino || d.nosplit || d.roi_rows > 0 || d.pool || d.in2.base || d.add.base || d.pre) return false;
+    if (d.in.Hb != d.in.Wb) return false;   // (a rectangular image would take two pitches)
+    if (d.in.pad != 2) return false;        // the zero lines behind an image must be the zero lines in front of the next
+    long per_image;
+    return nd_wino_mosaic(d.in.Hb - 2, d.in.B, bx, by, tiles, &per_image) == 1;
+}
+// geometry of the launch of d: the mosaic's where the rule takes it, else wino_geo's
+WinoGeo wino_geo_launch(int T, const ConvDesc &d) {
+    WinoGeo g = wino_geo(T, d.in, d.cin, d.cout, d.roi_rows, d.roi_cols);
+    int bx, by;
+    long tiles;
+    if (!wino_mosaic_rule(T, d, &bx, &by, &tiles)) return g;
+    g.mp = g.Hv;
+    g.mbx = bx;
+    g.mby = by;
+    g.TY = (by * g.mp + T - 1) / T;
+    g.TX = (bx * g.mp + T - 1) / T;
+    g.tiles = tiles;
+    wino_strides(T, d.cin, d.cout, g);
     return g;
 }
 }  // namespace
@@ -469,20 +526,61 @@ int nd_wino_pack(int T, int kind, int cin, int cout, const float *w, const float
     return ND_OK;
 }
 
+// ------------------------------------------------------------------ mosaic planner (host, no device)
+// The mosaic of B images of p x p outputs (p = input + 2 of a ConvTranspose2d(3)): by rows of bx images under ONE F(6x6) tile grid,
+// which pads only at the mosaic's edge.  Every bx in [1, B] with by = ceil(B / bx) is tried; the fewest tiles win, ties go to the
+// squarer mosaic, then to the wider one -- and a count within 1 % of the fewest is a tie (13, 256: 16 x 16 with 1225 tiles, not the
+// 43 x 6 strip with 1222: three tiles in 1225 are nothing to measure, and a square's count does not hang on how B factors).
+// Taken (returns 1) when p >= 8 (a tile's 8 input rows then cross one seam at most), B > 1 and the mosaic runs at most 0.9 of the
+// per-image tiles; else 0 with *bx = *by = 0 and *tiles = *tiles_per_image.  A function of (p, B) alone
+extern "C" int nd_wino_mosaic(int p, int B, int *bx, int *by, long *tiles, long *tiles_per_image) {
+    if (p <= 0 || B <= 0 || !bx || !by || !tiles || !tiles_per_image) ND_FAIL(ND_EINVAL, "nd_wino_mosaic: bad arguments");
+    const long T = 6, per = (long)B * ((p + T - 1) / T) * ((p + T - 1) / T);
+    *tiles_per_image = *tiles = per;
+    *bx = *by = 0;
+    if (p < 8 || B < 2) return 0;
+    auto count = [&](int x) { return (((long)x * p + T - 1) / T) * (((long)((B + x - 1) / x) * p + T - 1) / T); };
+    long fewest = count(1);
+    for (int x = 2; x <= B; ++x) fewest = std::min(fewest, count(x));
+    long best = -1;
+    int best_x = 0, best_y = 0, best_skew = 0;
+    for (int x = B; x >= 1; --x) {
+        const int y = (B + x - 1) / x, skew = x > y ? x - y : y - x;
+        const long n = count(x);
+        if (n * 100 > fewest * 101) continue;   // (a tie: within 1 % of the fewest)
+        if (best < 0 || skew < best_skew || (skew == best_skew && n < best)) {
+            best = n;
+            best_x = x;
+            best_y = y;
+            best_skew = skew;
+        }
+    }
+    if (best * 10 > per * 9) return 0;
+    *bx = best_x;
+    *by = best_y;
+    *tiles = best;
+    return 1;
+}
+
 // ------------------------------------------------------------------ launch
+// The bound of a whole layer on `in` with per-image tile grids.  A launch that takes the mosaic runs fewer tiles (nd_wino_mosaic
+// never reports more), so its V and M fit the same bound; nd_launch_conv_wino checks that
 size_t nd_wino_scratch_bytes(int T, const QpBuf &in, int cin, int cout) {
     const WinoGeo g = wino_geo(T, in, cin, cout);
     return ((g.v_bytes + 255) & ~(size_t)255) + ((g.m_bytes + 255) & ~(size_t)255);
 }
 
-// d: the layer as for nd_launch_conv (kind CONV3 / CONVT3, fp32); d.wpk = nd_wino_pack blob.  scratch: nd_wino_scratch_bytes
-void nd_wino_xform_bytes(int T, const QpBuf &in, int cin, int cout, double *bytes_in, double *bytes_out) {
-    const WinoGeo g = wino_geo(T, in, cin, cout);
+long nd_wino_launch_tiles(int T, const ConvDesc &d) { return wino_geo_launch(T, d).tiles; }
+
+void nd_wino_xform_bytes(int T, const QpBuf &in, int cin, int cout, long tiles, double *bytes_in, double *bytes_out) {
+    WinoGeo g = wino_geo(T, in, cin, cout);
+    if (tiles > 0) g.tiles = tiles;
     const double P = positions(T), px_in = (double)in.B * in.Hb * in.Wb, px_out = (double)in.B * g.Hv * g.Wv;
     *bytes_in = 4.0 * cin * px_in + 4.0 * cin * P * (double)g.tiles;
     *bytes_out = 4.0 * cout * P * (double)g.tiles + 4.0 * cout * px_out;
 }
 
+// d: the layer as for nd_launch_conv (kind CONV3 / CONVT3, fp32); d.wpk = nd_wino_pack blob.  scratch: nd_wino_scratch_bytes
 int nd_launch_conv_wino(int T, const ConvDesc &d, void *scratch, size_t scratch_bytes, hipStream_t s, hipEvent_t *ev2) {
     if (T != 2 && T != 4 && T != 6) ND_FAIL(ND_EINVAL, "winograd: tile must be 2, 4 or 6");
     if ((d.kind != ND_CONV3 && d.kind != ND_CONVT3) || d.in.dt != ND_F32 || d.out.dt != ND_F32)
@@ -496,7 +594,9 @@ int nd_launch_conv_wino(int T, const ConvDesc &d, void *scratch, size_t scratch_
     const int cin_w = d.w_kb ? 8 * d.w_kb : d.cin;   // input channels the blob was packed for
     ND_TRY(nd_check_roi("winograd", d, d.in.Hb - 2, d.in.Wb - 2, T != 6 || d.pool, "a layer other than an unpooled F(6x6) one"));
     const bool roi = d.roi_rows > 0;
-    const WinoGeo g = wino_geo(T, d.in, d.cin, d.cout, d.roi_rows, d.roi_cols);
+    const WinoGeo g = wino_geo_launch(T, d);
+    const bool mosaic = g.mp > 0;
+    const int gB = mosaic ? 1 : d.in.B;   // images of the tile grid: a mosaic is one
     const bool src2 = d.in2.base != nullptr;
     if (src2) {
         if (T != 6) ND_FAIL(ND_EINVAL, "winograd: only the F(6x6) form has a second input source");
@@ -510,6 +610,13 @@ int nd_launch_conv_wino(int T, const ConvDesc &d, void *scratch, size_t scratch_
     const int vHb = g.Hv + 2, vWb = g.Wv + 2;
     const size_t need = nd_wino_scratch_bytes(T, d.in, d.cin, d.cout);
     if (!scratch || scratch_bytes < need) ND_FAIL(ND_ENOMEM, "winograd: scratch %zu B given, %zu B needed", scratch_bytes, need);
+    if (mosaic) {
+        // what the mosaic kernels rely on: a pitch of at least a tile's 8 rows, every image inside the mosaic, V and M inside the
+        // per-image scratch bound
+        const size_t mneed = ((g.v_bytes + 255) & ~(size_t)255) + ((g.m_bytes + 255) & ~(size_t)255);
+        if (g.mp < 8 || g.mp != d.in.Wb - 2 || (long)g.mbx * g.mby < d.in.B || (long)g.TY * g.TX != g.tiles || mneed > need)
+            ND_FAIL(ND_EINVAL, "winograd: mosaic %d x %d at pitch %d does not fit %d images / the scratch bound", g.mbx, g.mby, g.mp, d.in.B);
+    }
     if (g.tiles >= (1L << 31)) ND_FAIL(ND_EINVAL, "winograd: %ld tiles exceed the 32-bit tile index", g.tiles);
     const int P = positions(T);
     f32x4 *v = (f32x4 *)scratch;
@@ -523,6 +630,9 @@ int nd_launch_conv_wino(int T, const ConvDesc &d, void *scratch, size_t scratch_
     dim3 gi2((unsigned)((g.tiles + kNtl - 1) / kNtl), in_planes);
     if (T == 2)
         hipLaunchKernelGGL(k_wino_input<2>, gi, dim3(256), 0, s, x, d.in.np(), d.in.Hb, d.in.Wb, d.in.B, g.TY, g.TX, v, g.vnp, g.vbs);
+    else if (mosaic)
+        hipLaunchKernelGGL((k_wino_in2<6, kNtl, true>), gi2, dim3(kNtl * 8), 0, s, x, d.in.np(), vHb, vWb, (long)d.in.Hb * d.in.Wb, d.in.Wb, d.in.B, g.TY, g.TX, v, g.vnp,
+                           g.vbs, nullptr, 0L, 0, nullptr, in_planes, g.mp, g.mbx, g.mby);
     else if (T == 6)
         hipLaunchKernelGGL((k_wino_in2<6, kNtl>), gi2, dim3(kNtl * 8), 0, s, x, d.in.np(), vHb, vWb, (long)d.in.Hb * d.in.Wb, d.in.Wb, d.in.B, g.TY, g.TX, v, g.vnp, g.vbs,
                            src2 ? (const f32x4 *)d.in2.base + (long)d.in2_plane0 * d.in2.np() + (roi ? (long)d.roi_r0 * d.in2.Wb + d.roi_c0 : 0) : nullptr,
@@ -540,8 +650,8 @@ int nd_launch_conv_wino(int T, const ConvDesc &d, void *scratch, size_t scratch_
     e.bias = d.wpk + nd_bias_offset(ND_CONV1, cin_w, d.cout);   // the zero bias of position 0
     e.w_kb = d.w_kb;
     e.w_kb0 = d.w_kb0;
-    e.in = {(float *)v, in_planes, d.in.B, g.TY, g.TX, 0, g.vnp, ND_F32};
-    e.out = {(float *)m, out_planes, d.in.B, g.TY, g.TX, 0, g.mnp, ND_F32};
+    e.in = {(float *)v, in_planes, gB, g.TY, g.TX, 0, g.vnp, ND_F32};
+    e.out = {(float *)m, out_planes, gB, g.TY, g.TX, 0, g.mnp, ND_F32};
     e.variant = nd_conv_variant_gemm(d.cin, d.cout);
     e.part = d.part;
     e.part_bytes = d.part_bytes;
@@ -576,6 +686,11 @@ int nd_launch_conv_wino(int T, const ConvDesc &d, void *scratch, size_t scratch_
         hipLaunchKernelGGL((k_wino_out2<6, 32, true>), go2, dim3(256), 0, s, (const f32x4 *)m, g.mnp, g.mbs, d.in.B, g.TY, g.TX, g.Hv, g.Wv, bias,
                            d.act, d.slope, d.slope_dev, out, d.out.np(), d.out_plane0, (long)d.out.Hb * d.out.Wb, d.out.Wb, d.out.pad, nullptr, 0L, 0, 0, 0,
                            ap, d.add.np(), d.add_origin, d.add.Wb);
+    } else if (mosaic) {
+        dim3 go2((unsigned)((g.tiles + 31) / 32), out_planes);
+        hipLaunchKernelGGL((k_wino_out2<6, 32, false, true>), go2, dim3(256), 0, s, (const f32x4 *)m, g.mnp, g.mbs, d.in.B, g.TY, g.TX, g.Hv, g.Wv, bias,
+                           d.act, d.slope, d.slope_dev, out, d.out.np(), d.out_plane0, (long)d.out.Hb * d.out.Wb, d.out.Wb, d.out.pad, nullptr, 0L, 0, 0, 0,
+                           nullptr, 0L, nullptr, 0, g.mp, g.mbx, g.mby);
     } else if (T == 6 && kOutNtl == 16) {
         dim3 go2((unsigned)((g.tiles + 15) / 16), out_planes);
         hipLaunchKernelGGL((k_wino_out2<6, 16>), go2, dim3(128), 0, s, (const f32x4 *)m, g.mnp, g.mbs, d.in.B, g.TY, g.TX, g.Hv, g.Wv, bias,

@@ -136,7 +136,10 @@ class UtNet(nn.Module):
     #                           once per band too (nd_utnet_frame_levels: 3; same canvas up to fp32 re-association)
     #   fold_skips = False -> A/B switch: the shared loop keeps the skip halves of tconvs4.0 / 3.0 / 2.0 in the per-tile sums where it
     #                         would compute their products once per band (nd_utnet_frame_folds; same canvas up to fp32 re-association)
+    #   mosaic_wino = False -> A/B switch: every three-pass Winograd layer tiles each image on its own where it would lay one tile grid
+    #                          over a mosaic of the launch's images (bottom.2, tconvs1.0; nd_wino_mosaic; fp32 re-association)
     split_k = True
+    mosaic_wino = True
     winograd = True
     w1d_regs = False
     useful_only = True
@@ -197,7 +200,8 @@ class UtNet(nn.Module):
     def flags(self):
         return ((0 if self.split_k else _lib.FLAG_NO_SPLITK) | (0 if self.winograd else _lib.FLAG_DIRECT_CONV) |
                 (_lib.FLAG_W1D_REGS if self.w1d_regs else 0) | (0 if self.useful_only else _lib.FLAG_FULL_TILES) |
-                (0 if self.fused_pool else _lib.FLAG_UNFUSED_POOL) | (0 if self.share_encoder else _lib.FLAG_TILE_ENCODER))
+                (0 if self.fused_pool else _lib.FLAG_UNFUSED_POOL) | (0 if self.share_encoder else _lib.FLAG_TILE_ENCODER) |
+                (0 if self.mosaic_wino else _lib.FLAG_TILE_WINO))
 
     @property
     def frame_flags(self):

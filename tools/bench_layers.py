@@ -52,6 +52,7 @@ def main():
     ap.add_argument("--layers", default="")
     ap.add_argument("--dtype", default="f32")
     ap.add_argument("--winograd", action="store_true", help="also time the Winograd F(2,3) / F(4,3) form of every eligible 3x3 layer")
+    ap.add_argument("--tile-wino", action="store_true", help="with --winograd: the three-pass forms on per-image tile grids (ND_FLAG_TILE_WINO) instead of a mosaic")
     args = ap.parse_args()
     lib = _lib.load()
     dev = torch.device("cuda:0")
@@ -88,8 +89,8 @@ def main():
                 for tile in (3, 5, 4, 6):   # 3 = 1-D F(4,3) in registers (conv_w1d), 5 = the same with the LDS-shared transform (conv_w2d), 4 | 6 = three-pass F(4x4,3x3) | F(6x6,3x3)
                     if tile % 2 == 0 and cin % 16:
                         continue
-                    rc = lib.nd_winograd_bench(tile, k, args.batch, cin, cout, h, h, args.iters, ws.data_ptr(), ws.numel(),
-                                               _lib.stream_ptr(dev), ms)
+                    rc = lib.nd_winograd_bench_flags(tile, k, args.batch, cin, cout, h, h, args.iters, _lib.FLAG_TILE_WINO if args.tile_wino else 0,
+                                                     ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev), ms)
                     if rc != 0:
                         print(f"{name:10s} F({tile},3) skipped: {lib.nd_last_error().decode()}")
                         continue

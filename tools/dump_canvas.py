@@ -1,12 +1,13 @@
 """Canvas of the flagship frame through the fused frame loop, for comparing two builds of the library bit for bit.
 
-    python3 tools/dump_canvas.py --out new.npy [--no-split-k] [--tile-level2] [--tile-skips] [--batch 256] [--compare old.npy]
+    python3 tools/dump_canvas.py --out new.npy [--no-split-k] [--tile-level2] [--tile-skips] [--tile-wino] [--batch 256] [--compare old.npy]
 
 bench.py's flagship workload (fp32 G24: 6000x4000, cs 264 / ucs 200 / ol 64, UtNet(64) seed 123, frame seed 24).  A frame of another
 seed runs first through the same net object and workspaces, so that anything a build leaves behind in them is wrong data for the
 frame that is dumped.  --no-split-k sets UtNet.split_k = False (ND_FLAG_NO_SPLITK: a tile's bits do not depend on the launch
 composition), --tile-level2 UtNet.share_level2 = False (ND_FLAG_TILE_LEVEL2: the third encoder level per tile),
---tile-skips UtNet.fold_skips = False (ND_FLAG_TILE_SKIPS: the skip halves of the decoder per tile).  --compare prints
+--tile-skips UtNet.fold_skips = False (ND_FLAG_TILE_SKIPS: the skip halves of the decoder per tile), --tile-wino UtNet.mosaic_wino =
+False (ND_FLAG_TILE_WINO: per-image Winograd tile grids).  --compare prints
 one JSON line: equal bit for bit or not, and max |difference|.  Run once per build (swap nind_denoise_amd/libnind_hip.so between
 runs, as tools/ab_builds.py does, or run the other build's own tree)."""
 import argparse
@@ -28,6 +29,7 @@ def main():
     ap.add_argument("--no-split-k", action="store_true")
     ap.add_argument("--tile-level2", action="store_true")
     ap.add_argument("--tile-skips", action="store_true")
+    ap.add_argument("--tile-wino", action="store_true")
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--compare", help="an earlier dump to compare this one with")
     a = ap.parse_args()
@@ -39,6 +41,7 @@ def main():
     net.split_k = not a.no_split_k
     net.share_level2 = not a.tile_level2
     net.fold_skips = not a.tile_skips
+    net.mosaic_wino = not a.tile_wino
     canvas = None
     for seed in (7, 24):
         img = torch.from_numpy(synth.make_frame(W, H, seed=seed)).to(dev)
@@ -47,7 +50,7 @@ def main():
     torch.cuda.synchronize()
     out = canvas.cpu().numpy()
     np.save(a.out, out)
-    res = {"out": a.out, "split_k": net.split_k, "share_level2": net.share_level2, "fold_skips": net.fold_skips, "batch": a.batch, "max_abs": float(np.abs(out).max())}
+    res = {"out": a.out, "split_k": net.split_k, "share_level2": net.share_level2, "fold_skips": net.fold_skips, "mosaic_wino": net.mosaic_wino, "batch": a.batch, "max_abs": float(np.abs(out).max())}
     if a.compare:
         old = np.load(a.compare)
         res["compare"] = a.compare
