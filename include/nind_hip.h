@@ -88,7 +88,7 @@ typedef enum nd_flags {
                                  nd_unet_denoise_frame: the same switch for the UNet decoder (nd_unet_useful_region)             */
 } nd_flags;
 
-int nd_version(void);   /* 112 = this header */
+int nd_version(void);   /* 113 = this header */
 const char *nd_last_error(void);
 
 /* ---------------------------------------------------------------- tile geometry (host, pure integer)
@@ -378,6 +378,30 @@ int nd_ssim_padded(const float *x, const float *y, int n, int c, int h, int w, i
                    size_t workspace_bytes, void *stream);
 int nd_ssim_padded_grad(const float *x, const float *y, int n, int c, int h, int w, int window, const float *gout, float *gx,
                         void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- augmented training batches from a device-resident crop pool (dataset_torch_3.py:231-276, DenoisingDataset.__getitem__) ----
+ * The pool is one byte buffer in HBM holding images as planar [3][H][W] samples in their file type, and `images`, a table in HBM of
+ * four int64 per image: {byte offset into the pool (a multiple of the sample size), H, W, nd_sample_type}.  `draws`, in HBM, holds
+ * eight int32 per sample: {clean image, noisy image, x0, y0, nrot, flip1, flip2, the bits of the float u in [0, 1)}.
+ * nd_crop_batch writes clean_nchw and noisy_nchw, [batch,3,cs,cs] fp32, from the same draws, in one launch:
+ *   samples are converted as np_imgops.img_path_to_np_flt does (u8 / 255, u16 / 65535 in fp32, f32 as it is);
+ *   a side d < cs is zero-padded, centred, (cs - d) / 2 before (np_imgops.np_pad_img_pair); a side d > cs is cut at x0 / y0
+ *   (np_crop_img_pair), so crop pixel (a, b) is source pixel (y0 + a - pad0_y, x0 + b - pad0_x) or 0 outside the image;
+ *   output pixel (y, x) is the crop pixel nd_crop_source names: np.rot90(nrot, (1, 2)), np.flip(1) if flip1, np.flip(2) if flip2.
+ * Exposure multiplier (dataset_torch_3.py:271-274): mult (nullable, HBM, [batch]) gives it per sample; without it and with
+ * exp_mult_min != 1 a first launch writes xmax[n] = the maximum of the clean crop (a maximum of the integer samples for u8 / u16, converted once: order-free) and
+ * mult_out[n] = exp_mult_min + (min(exp_mult_max, 1 / xmax[n]) - exp_mult_min) * u (xmax 0: exp_mult_max), both [batch] fp32 in HBM
+ * and needed only then.  With a multiplier m: clean = clean * m, unclipped; noisy = clip(noisy * m, 0, 1).  Without: no clip.
+ * Every read is guarded on the device: an image index outside the table, or a table row that does not lie inside the pool, gives a
+ * zero sample, and no x0 / y0 reads outside an image.  Stream-ordered; allocates nothing.  ND_EINVAL: a null pointer, n_images < 1,
+ * cs outside [1, 16384], batch outside [1, 65535].  Not built: the sigmamin / sigmamax artificial noise and the JPEG branch.
+ * nd_crop_source (host only, the kernel's own inline map): *a, *b = the crop pixel that output pixel (y, x) shows;
+ * flips: bit 0 = flip1, bit 1 = flip2. */
+typedef enum nd_sample_type { ND_SAMPLE_U8 = 0, ND_SAMPLE_U16 = 1, ND_SAMPLE_F32 = 2 } nd_sample_type;
+int nd_crop_source(int cs, int nrot, int flips, int y, int x, int *a, int *b);
+int nd_crop_batch(const void *pool, size_t pool_bytes, const int64_t *images, int n_images, const int32_t *draws, int batch, int cs,
+                  float exp_mult_min, float exp_mult_max, const float *mult, float *xmax, float *mult_out, float *clean_nchw,
+                  float *noisy_nchw, void *stream);
 
 /* ---- Winograd forms of a 3x3 layer, fp32 inference (same math as nd_layer_forward on a CONV3 / CONVT3 layer, re-associated).
  * tile = 2 | 4 | 6: three-pass F(tile x tile, 3 x 3) (input transform, one launch of (tile+2)^2 GEMMs, output transform;

@@ -29,6 +29,8 @@ class StepProfile(ctypes.Structure):
                 ("xform_bytes_in", c_double), ("xform_bytes_out", c_double)]
 
 
+SAMPLE_U8, SAMPLE_U16, SAMPLE_F32 = 0, 1, 2   # nd_sample_type
+
 FORM_NAMES = {-1: "pool", 0: "direct", 1: "w1d_f43", 2: "w1d_f23", 3: "wino3p_f6x6"}
 
 
@@ -121,6 +123,8 @@ _SIGNATURES = {
     "nd_winograd_bench": (c_int, [c_int] * 8 + [c_void_p, c_size_t, c_void_p, POINTER(c_float)]),
     "nd_winograd_bench_flags": (c_int, [c_int] * 9 + [c_void_p, c_size_t, c_void_p, POINTER(c_float)]),
     "nd_wino_mosaic": (c_int, [c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_long), POINTER(c_long)]),
+    "nd_crop_source": (c_int, [c_int] * 5 + [POINTER(c_int)] * 2),
+    "nd_crop_batch": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_float] + [c_void_p] * 6),
     "nd_num_conv_variants": (c_int, []),
     "nd_conv_variant_name": (c_char_p, [c_int]),
 }

@@ -25,8 +25,8 @@ def img_path_to_np_flt(fpath):
     return hwc_to_np_flt(_read_hwc(fpath), fpath)
 
 
-def hwc_to_np_flt(img, fpath='<array>'):
-    '''the conversion of img_path_to_np_flt on decoded samples (HW or HWC; uint8, uint16 or float32)'''
+def hwc_to_rgb(img):
+    '''decoded samples (HW or HWC, any sample type) -> three channels, HWC'''
     if img.ndim == 2:
         img = img[:, :, None]
     if img.shape[2] == 1:                      # IMREAD_COLOR semantics: gray is replicated
@@ -35,7 +35,19 @@ def hwc_to_np_flt(img, fpath='<array>'):
         img = np.repeat(img[:, :, :1], 3, axis=2)
     elif img.shape[2] > 3:                     # alpha is dropped
         img = img[:, :, :3]
-    rgb_img = np.ascontiguousarray(img.transpose(2, 0, 1))
+    return img
+
+
+def img_path_to_np_samples(fpath):
+    '''the samples img_path_to_np_flt converts, as the file stores them (uint8, uint16 or float32): RGB, shape c, y, x'''
+    if not os.path.isfile(fpath):
+        raise FileNotFoundError(fpath)
+    return np.ascontiguousarray(hwc_to_rgb(_read_hwc(fpath)).transpose(2, 0, 1))
+
+
+def hwc_to_np_flt(img, fpath='<array>'):
+    '''the conversion of img_path_to_np_flt on decoded samples (HW or HWC; uint8, uint16 or float32)'''
+    rgb_img = np.ascontiguousarray(hwc_to_rgb(img).transpose(2, 0, 1))
     if rgb_img.dtype == np.float32:
         return rgb_img
     if rgb_img.dtype == np.ubyte:

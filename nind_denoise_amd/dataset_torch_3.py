@@ -1,6 +1,6 @@
 """The two dataset helpers the eval harness needs: which file of an image set is the clean baseline.
 Interface of /root/reference/src/nind_denoise/dataset_torch_3.py:37-96 (``sortISOs``, ``get_baseline_fpath``); the training
-dataset classes of that file are out of scope (they need the NIND dataset)."""
+dataset classes of that file (DenoisingDataset, CleanCleanDataset) are served from HBM by crop_pool.CropPool."""
 import os
 from typing import List
 
