@@ -88,7 +88,7 @@ typedef enum nd_flags {
                                  nd_unet_denoise_frame: the same switch for the UNet decoder (nd_unet_useful_region)             */
 } nd_flags;
 
-int nd_version(void);   /* 113 = this header */
+int nd_version(void);   /* 114 = this header */
 const char *nd_last_error(void);
 
 /* ---------------------------------------------------------------- tile geometry (host, pure integer)
@@ -311,6 +311,9 @@ int nd_layer_wgrad(int kind, const float *x_nchw, const float *dy_nchw, int batc
  * x0 = (w - loss_cs) / 2 of output and target (pt_ops.pt_crop_batch, nn_train.py:319-323; --loss_cs), and the gradient is zero
  * outside it; 0: the whole output.
  *
+ * nd_utnet_train_step_act_hw is the same step for any activation the network takes (act as in the two halves below);
+ * nd_utnet_train_step_hw is its ND_ACT_PRELU form.
+ *
  * The two halves of the step for torch.autograd, so that the reference's own training statements
  * (nn_common.py:198-218: `self.model(noisy_batch).clip(0,1)`, `loss.backward()`) run unchanged on the module:
  * nd_utnet_train_forward_hw = device-side weight packing + forward with the pre-activations kept in `workspace`;
@@ -331,6 +334,10 @@ int nd_utnet_train_step_hw(int funit, int flags, const float *params, float *gra
                            const float *target_nchw, float *y_out_nchw, float w_l1, float w_mse, float w_ssim, float w_msssim,
                            float *loss_out, int batch, int h, int w, int loss_cs, void *workspace, size_t workspace_bytes,
                            void *stream, void *const *bucket_events, int n_events);
+int nd_utnet_train_step_act_hw(int funit, int act, int flags, const float *params, float *grads, void *blobs, const float *x_nchw,
+                               const float *target_nchw, float *y_out_nchw, float w_l1, float w_mse, float w_ssim, float w_msssim,
+                               float *loss_out, int batch, int h, int w, int loss_cs, void *workspace, size_t workspace_bytes,
+                               void *stream, void *const *bucket_events, int n_events);
 int nd_utnet_train_forward_hw(int funit, int act, int flags, const float *params, void *blobs, const float *x_nchw,
                               float *y_out_nchw, int batch, int h, int w, void *workspace, size_t workspace_bytes, void *stream);
 int nd_utnet_train_backward_hw(int funit, int act, int flags, const float *params, float *grads, void *blobs, const float *gy_nchw,
@@ -364,6 +371,19 @@ int nd_mse(const float *x, const float *y, size_t count, float *out, void *works
 size_t nd_ssim_loss_workspace_bytes(int n, int c, int h, int w);
 int nd_ssim_loss_grad(const float *x, const float *y, int n, int c, int h, int w, int multiscale, float weight,
                       float *loss_acc, float *gx, int accumulate, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Per-sample criteria of a batch: what the validation pass of training averages (nn_train.py:51-71, nn_common.py:198-199, 226-241).
+ * y = the raw network output, target = the clean batch, both [n,3,h,w] fp32 in HBM.  g = clip(y, 0, 1); with loss_cs > 0 both g and
+ * target are cut to the centre loss_cs x loss_cs window at y0 = (h - loss_cs) / 2, x0 = (w - loss_cs) / 2 (pt_ops.pt_crop_batch);
+ * 0: the whole image.  out: [n][5] fp32, per sample { mean|g - t|, mean (g - t)^2, 1 - SSIM (nd_ssim), 1 - MS-SSIM (nd_ms_ssim),
+ * weighted = sum_k w_k * column_k over the computed columns with a non-zero weight }.  A column is computed iff its weight != 0 or its
+ * bit is set in `also` (bit k = column k); the others are written as 0.  ND_EINVAL as nd_utnet_train_step_hw: an SSIM window below
+ * 11, an MS-SSIM window below 161, loss_cs above h or w, a null pointer, n < 1 (also: n > 65535, a side above 16384);
+ * ND_ENOMEM: a workspace below nd_criteria_workspace_bytes.  Stream-ordered, allocates nothing, deterministic (no atomics; partial
+ * sums are added in a fixed order). */
+size_t nd_criteria_workspace_bytes(int n, int h, int w, int loss_cs);
+int nd_criteria(const float *y_nchw, const float *target_nchw, int n, int h, int w, int loss_cs, float w_l1, float w_mse,
+                float w_ssim, float w_msssim, int also, float *out, void *workspace, size_t workspace_bytes, void *stream);
 
 /* The SSIM the reference vendors itself (libs/pytorch_ssim/__init__.py:20-35; loss.py:29-45 gen_score writes res.txt with it).
  * Not the piqa score above: the Gaussian (sigma 1.5, `window` taps) is applied with zero padding of window / 2, so the map is

@@ -108,6 +108,9 @@ _SIGNATURES = {
     "nd_utnet_train_step_hw": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                        c_float, c_float, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
                                        POINTER(c_void_p), c_int]),
+    "nd_utnet_train_step_act_hw": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                           c_float, c_float, c_float, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
+                                           POINTER(c_void_p), c_int]),
     "nd_adam_step": (c_int, [c_void_p] * 5 + [c_size_t, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p]),
     "nd_ssim_workspace_bytes": (c_size_t, [c_int] * 4),
     "nd_ssim": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -119,6 +122,8 @@ _SIGNATURES = {
     "nd_ssim_padded": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_size_t, c_void_p]),
     "nd_ssim_padded_grad": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nd_mse": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nd_criteria_workspace_bytes": (c_size_t, [c_int] * 4),
+    "nd_criteria": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_float] * 4 + [c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nd_conv_bench": (c_int, [c_int] * 9 + [c_void_p, c_size_t, c_void_p, POINTER(c_float)]),
     "nd_winograd_bench": (c_int, [c_int] * 8 + [c_void_p, c_size_t, c_void_p, POINTER(c_float)]),
     "nd_winograd_bench_flags": (c_int, [c_int] * 9 + [c_void_p, c_size_t, c_void_p, POINTER(c_float)]),

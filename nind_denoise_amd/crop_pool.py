@@ -99,6 +99,28 @@ class CropPool:
         self._gt = None
         return len(self._groups) - 1
 
+    def keep_groups(self, count):
+        """Drops every group past the first `count` (debug option short_run: DDataset.dataset[:3 * batch_size], nn_train.py:225-226),
+        and with them the images no remaining group names.  Only before the first upload."""
+        if self._pool is not None:
+            raise RuntimeError("CropPool: the pool was uploaded by its first batch; drop groups before that")
+        if count < 0:
+            raise ValueError(f"CropPool.keep_groups: count {count}")
+        if count >= len(self._groups):
+            return
+        groups, staged = self._groups[:count], dict(self._staged)
+        arrays = [staged[off] for off, _, _, _ in self._images]
+        self.sets = self.sets[:count]
+        self._staged, self._images, self._groups, self._bytes, self._gt = [], [], [], 0, None
+        moved = {}
+        for c0, nc, n0, nn, h, w in groups:        # images of a group are consecutive: re-add each run once, in the old order
+            first = []
+            for i0, cnt in ((c0, nc), (n0, nn)):
+                if i0 not in moved:
+                    moved[i0] = [self._add_image(arrays[i]) for i in range(i0, i0 + cnt)][0]
+                first.append(moved[i0])
+            self._groups.append((first[0], nc, first[1], nn, h, w))
+
     @classmethod
     def from_directories(cls, datadirs, test_reserve=(), exact_reserve=False, min_crop_size=None, device=None, seed=0, cs=None):
         """The scan of DenoisingDataset.__init__ (dataset_torch_3.py:166-192) over <datadir>/<set>/ISO*/<crop files>: one group per

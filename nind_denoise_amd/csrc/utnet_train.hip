@@ -782,17 +782,18 @@ static int train_backward(TrainCtx &c, const float *params, float *grads, const 
     return ND_OK;
 }
 
-// One training step without the optimizer: packs the weights on the device, runs forward (PReLU only), the loss
+// One training step without the optimizer: packs the weights on the device, runs forward (act: ND_ACT_PRELU | ND_ACT_ELU |
+// ND_ACT_HARDSWISH, as in the two halves below; nd_utnet_train_step_hw is the PReLU form), the loss
 //   loss = w_l1 * mean|g - target| + w_mse * mean (g - target)^2 + w_ssim * mean_n(1 - SSIM_n(g, target))
 //          + w_msssim * mean_n(1 - MS-SSIM_n(g, target)),      g = clip(y, 0, 1)          (nn_common.py:198-199, 226-241)
 // and the backward pass.  params / grads: flat fp32 buffers in state-dict order (nd_utnet_param_range);
 // x, target, y_out: [batch,3,h,w] NCHW fp32 (each side 16k+56); loss_out: one float in HBM; blobs: nd_utnet_train_blob_bytes
 // scratch.  bucket_events (nullable, else nd_utnet_grad_buckets of them): bucket_events[k] (hipEvent_t) is recorded on `stream` as soon as
 // every gradient of bucket k is final -- a data-parallel run overlaps the gradient reduction with the backward pass.
-extern "C" int nd_utnet_train_step_hw(int funit, int flags, const float *params, float *grads, void *blobs, const float *x,
-                                      const float *target, float *y_out, float w_l1, float w_mse, float w_ssim, float w_msssim,
-                                      float *loss_out, int batch, int h, int w, int loss_cs, void *ws, size_t ws_bytes, void *stream,
-                                      void *const *bucket_events, int n_events) {
+extern "C" int nd_utnet_train_step_act_hw(int funit, int act, int flags, const float *params, float *grads, void *blobs, const float *x,
+                                          const float *target, float *y_out, float w_l1, float w_mse, float w_ssim, float w_msssim,
+                                          float *loss_out, int batch, int h, int w, int loss_cs, void *ws, size_t ws_bytes, void *stream,
+                                          void *const *bucket_events, int n_events) {
     if (bucket_events && n_events != kNumBuckets) ND_FAIL(ND_EINVAL, "train step: %d bucket events expected", kNumBuckets);
     // the criteria see the centre loss_cs x loss_cs crop (nn_train.py:319-323, pt_ops.pt_crop_batch), or the whole output
     const int Lh = loss_cs > 0 ? loss_cs : h, Lw = loss_cs > 0 ? loss_cs : w, L = Lh < Lw ? Lh : Lw;
@@ -803,7 +804,7 @@ extern "C" int nd_utnet_train_step_hw(int funit, int flags, const float *params,
     if (w_ssim != 0.f && L < 11) ND_FAIL(ND_EINVAL, "UtNet training: the SSIM loss needs at least 11 pixels, got %d", L);
     if (!grads || !x || !target || !y_out || !loss_out) ND_FAIL(ND_EINVAL, "train step: null pointer");
     TrainCtx c;
-    ND_TRY(train_ctx(c, funit, flags, ND_ACT_PRELU, params, blobs, batch, h, w, ws, ws_bytes, stream));
+    ND_TRY(train_ctx(c, funit, flags, act, params, blobs, batch, h, w, ws, ws_bytes, stream));
     ND_TRY(train_forward(c, params, x, y_out));
     TrainPlan &t = c.t;
     hipStream_t s = c.s;
@@ -842,6 +843,13 @@ extern "C" int nd_utnet_train_step_hw(int funit, int flags, const float *params,
     }
 
     return train_backward(c, params, grads, t.gy, nullptr, bucket_events);
+}
+extern "C" int nd_utnet_train_step_hw(int funit, int flags, const float *params, float *grads, void *blobs, const float *x,
+                                      const float *target, float *y_out, float w_l1, float w_mse, float w_ssim, float w_msssim,
+                                      float *loss_out, int batch, int h, int w, int loss_cs, void *ws, size_t ws_bytes, void *stream,
+                                      void *const *bucket_events, int n_events) {
+    return nd_utnet_train_step_act_hw(funit, ND_ACT_PRELU, flags, params, grads, blobs, x, target, y_out, w_l1, w_mse, w_ssim, w_msssim,
+                                      loss_out, batch, h, w, loss_cs, ws, ws_bytes, stream, bucket_events, n_events);
 }
 // Buckets of the flat gradient buffer in the order the backward pass completes them (one per decoder / encoder level):
 // offsets / counts in floats.  Returns the number of buckets (9); fills at most `max` entries.

@@ -1,0 +1,422 @@
+'''
+Train a denoising UtNet with the NIND (or any dataset of clean-noisy crops) -- MI355X native.
+
+The generator-only reading of the reference's training script (nn_train.py:118-448): option names, defaults, the order of
+events of an epoch, the files of a run directory (train.log, config.yaml, trainres.json, generator_<epoch>.pt) and the
+learning-rate rule are the reference's; the data side is a device-resident crop pool (crop_pool.CropPool), the update is the
+fused HIP step (train.UtNetTrainer) and validation runs in batches from HBM (validation.validate).
+
+egrun:
+    python -m nind_denoise_amd.nn_train --config configs/train_conf_utnet_std.yaml --debug_options short_run --epochs 6
+then
+    python -m nind_denoise_amd.nn_train --config configs/train_conf_utnet_std.yaml
+
+Not built, and refused by name: discriminators (--weight_D1 / --weight_D2 and the options that need them), generators other than
+UtNet, the CPU whole-image test pass (--test_interval) and clean-clean mixing (--clean_data_ratio).
+'''
+import argparse
+import collections
+import datetime
+import os
+import shutil
+import sys
+import time
+
+import torch
+import yaml
+
+from . import nn_common
+from .common.libs import json_saver
+
+DEFAULT_CONFIG_FPATH = os.path.join('configs', 'train_conf_defaults.yaml')
+DEBUG_OPTIONS = ('short_run', 'check_dataset', 'output_val_images', 'output_test_images', 'keep_all_output_images')
+
+
+class Printer:
+    '''print, and append to a file (nn_common.py:364-378)'''
+    def __init__(self, tostdout=True, tofile=True, file_path='log'):
+        self.tostdout, self.tofile, self.file_path = tostdout, tofile, file_path
+
+    def print(self, msg):
+        if self.tostdout:
+            print(msg)
+        if self.tofile:
+            try:
+                with open(self.file_path, 'a') as f:
+                    f.write(str(msg) + '\n')
+            except Exception as e:
+                print('Warning: could not write to log: %s' % e)
+
+
+def get_test_reserve_list(test_reserve):
+    '''test_reserve argument (a list, ["0"] for none, or [yaml path]) -> list of set names (nn_common.py:149-160)'''
+    if test_reserve is not None and len(test_reserve) == 1:
+        if test_reserve[0].endswith('.yaml'):
+            with open(test_reserve[0], 'r') as fp:
+                return yaml.safe_load(fp)
+        elif test_reserve[0] == '0':
+            return []
+    return test_reserve
+
+
+# ------------------------------------------------------------------ command line
+def build_parser():
+    parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    parser.add_argument('-c', '--config', help='(yaml) config file path')
+    parser.add_argument('-c2', '--config2', help='extra (yaml) config file path')
+    parser.add_argument('--batch_size', type=int, help='Training batch size')
+    parser.add_argument('--time_limit', type=int, help='Time limit in seconds (ends training)')
+    parser.add_argument('--g_activation', type=str, default='PReLU', help='Final activation function for generator')
+    parser.add_argument('--g_funit', type=int, default=32, help='Filter unit size for generator')
+    parser.add_argument('--g_model_path', help='Generator pretrained model path (.pt state dict, or a run directory: its best epoch)')
+    parser.add_argument('--models_dpath', help='Directory where all models are saved')
+    parser.add_argument('--beta1', type=float, help='beta1 for adam')
+    parser.add_argument('--g_lr', type=float, help='Initial learning rate for adam (generator)')
+    parser.add_argument('--weight_SSIM', type=float, help='Weight on SSIM term in objective')
+    parser.add_argument('--weight_MSSSIM', type=float, help='Weight on MSSSIM term in objective')
+    parser.add_argument('--weight_L1', type=float, help='Weight on L1 term in objective')
+    parser.add_argument('--weight_MSE', type=float, help='Weight on MSE term in objective')
+    parser.add_argument('--test_reserve', nargs='*', help='Space separated list of image sets to be reserved for testing, or yaml file path containing a list. Set to "0" to use all available data. Required (here or in a config file)')
+    parser.add_argument('--train_data', nargs='*', help='(space-separated) Path(s) to the pre-cropped training data')
+    parser.add_argument('--cs', '--crop_size', type=int, help='Crop size fed to NN. default: no additional cropping')
+    parser.add_argument('--min_crop_size', type=int, help='Minimum crop size. Dataset will be checked if this value is set.')
+    parser.add_argument('--loss_cs', '--loss_crop_size', type=int, help='Center crop size used in loss function. default: use stride size from dataset directory name')
+    parser.add_argument('--debug_options', '--debug', nargs='*', default=[], help=f'(space-separated) Debug options (available: {DEBUG_OPTIONS})')
+    parser.add_argument('--g_network', type=str, help='Generator network (UtNet)')
+    parser.add_argument('--threads', type=int, default=6, help='Accepted for the reference\'s config files; the crop pool has no loader threads')
+    parser.add_argument('--min_lr', type=float, help='Minimum learning rate (ends training)')
+    parser.add_argument('--epochs', type=int, default=9001, help='Number of epochs (ends training)')
+    parser.add_argument('--compute_SSIM_anyway', action='store_true', help='Compute and display SSIM loss even if not used')
+    parser.add_argument('--freeze_generator', action='store_true', help='Freeze generator until discriminator is useful (refused: no discriminator)')
+    parser.add_argument('--start_epoch', default=1, type=int, help='Starting epoch (cosmetics)')
+    parser.add_argument('--patience', type=int, help='Number of epochs without improvements before the learning rate is updated')
+    parser.add_argument('--reduce_lr_factor', type=float, help='LR is multiplied by this factor when model performs poorly for <patience> epochs')
+    parser.add_argument('--validation_interval', default=1, type=int, help='Validation interval in # of epochs. Affects learning rate update and helps to keep the best model in the end. 0 = no validation, default=1')
+    parser.add_argument('--test_interval', default=0, type=int, help='Refused when > 0: the CPU whole-image test pass is not built (use denoise_dir on a checkpoint)')
+    parser.add_argument('--orig_data', help='Location of the originally downloaded train data (before cropping); used when test_interval is set')
+    parser.add_argument('--validation_set_yaml', help='Yaml file containing a list of clean/noisy images used for validation.')
+    parser.add_argument('--exp_mult_min', type=float, help='Minimum exposure multiplicator (data augmentation)')
+    parser.add_argument('--exp_mult_max', type=float, help='Maximum exposure multiplicator (data augmentation)')
+    parser.add_argument('--clean_data_dpath', help='Location of the high quality (pre-cropped) clean data which can be used in training')
+    parser.add_argument('--clean_data_ratio', type=float, help='Refused when > 0: ratio of clean-clean to clean-noisy training data')
+    # discriminator options: parsed so that the reference's command lines and config files load, refused when they ask for one
+    parser.add_argument('--d_activation', type=str, default='PReLU')
+    parser.add_argument('--d2_activation', type=str, default='PReLU')
+    parser.add_argument('--d_funit', type=int, default=32)
+    parser.add_argument('--d2_funit', type=int, default=32)
+    parser.add_argument('--d_model_path')
+    parser.add_argument('--d2_model_path')
+    parser.add_argument('--d_loss_function', type=str, default='MSE')
+    parser.add_argument('--d2_loss_function', type=str, default='MSE')
+    parser.add_argument('--d_lr', type=float)
+    parser.add_argument('--d2_lr', type=float)
+    parser.add_argument('--weight_D1', type=float, help='Refused when > 0')
+    parser.add_argument('--weight_D2', type=float, help='Refused when > 0')
+    parser.add_argument('--d_network', type=str)
+    parser.add_argument('--d2_network', type=str)
+    parser.add_argument('--not_conditional', action='store_true')
+    parser.add_argument('--not_conditional_2', action='store_true')
+    parser.add_argument('--discriminator_advantage', type=float, default=0.0)
+    parser.add_argument('--discriminator2_advantage', type=float, default=0.0)
+    # additions
+    parser.add_argument('--seed', type=int, default=0, help='Seed of the crop pool\'s draws and of torch\'s generator')
+    parser.add_argument('--expname', help='Name of the run directory under models_dpath (default: date and command line)')
+    parser.add_argument('--log_interval', type=int, default=50, help='Print an iteration line every N steps (0: never)')
+    parser.add_argument('--val_batch_size', type=int, default=32, help='Validation pairs per launch of the network')
+    return parser
+
+
+def _convert(action, value):
+    '''a yaml value as the option would have parsed it: nargs options take lists, typed options their type'''
+    if isinstance(action, (argparse._StoreTrueAction, argparse._StoreFalseAction)):
+        return bool(value)
+    conv = (lambda v: v) if action.type is None or value is None else (lambda v: v if v is None else action.type(v))
+    if action.nargs in ('*', '+'):
+        if value is None:
+            return None
+        return [conv(v) for v in (value if isinstance(value, (list, tuple)) else [value])]
+    return conv(value)
+
+
+def parse_args(argv=None):
+    '''Precedence, lowest first: argparse defaults, configs/common_conf_default.yaml, configs/train_conf_defaults.yaml (both
+    relative to the working directory, if they exist), -c/--config, -c2/--config2, the command line.  Yaml keys are option names
+    without their dashes (any alias); unknown keys are ignored.'''
+    argv = sys.argv[1:] if argv is None else list(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    explicit = build_parser()
+    for action in explicit._actions:
+        action.default = argparse.SUPPRESS
+    given = vars(explicit.parse_args(argv))
+    by_key = {}
+    for action in parser._actions:
+        for opt in action.option_strings:
+            by_key[opt.lstrip('-')] = action
+    for path, required in ((nn_common.COMMON_CONFIG_FPATH, False), (DEFAULT_CONFIG_FPATH, False), (args.config, True),
+                           (args.config2, True)):
+        if path is None or (not required and not os.path.isfile(path)):
+            continue
+        with open(path, 'r') as f:
+            conf = yaml.safe_load(f) or {}
+        for key, value in conf.items():
+            action = by_key.get(key)
+            if action is None or action.dest in ('help', 'config', 'config2'):
+                continue
+            try:
+                setattr(args, action.dest, _convert(action, value))
+            except (TypeError, ValueError) as e:
+                parser.error(f'{path}: {key}: {e}')
+    for dest, value in given.items():
+        setattr(args, dest, value)
+    if args.test_reserve is None:
+        parser.error('the following arguments are required: --test_reserve (on the command line or in a config file)')
+    return args
+
+
+def check_supported(args):
+    '''NotImplementedError naming the first option that asks for something that is not built'''
+    if args.g_network is not None and args.g_network != 'UtNet':
+        raise NotImplementedError(f'--g_network {args.g_network}: only UtNet trains on the HIP path')
+    for name in ('weight_D1', 'weight_D2'):
+        if (getattr(args, name) or 0) > 0:
+            raise NotImplementedError(f'--{name} > 0: discriminators are not built (generator losses: L1, MSE, SSIM, MSSSIM)')
+    for name in ('d_model_path', 'd2_model_path', 'd_network', 'd2_network', 'freeze_generator', 'not_conditional',
+                 'not_conditional_2', 'discriminator_advantage', 'discriminator2_advantage'):
+        if getattr(args, name):
+            raise NotImplementedError(f'--{name} needs a discriminator (--weight_D1 / --weight_D2), and discriminators are not built')
+    if (args.test_interval or 0) > 0:
+        raise NotImplementedError('--test_interval > 0: the CPU whole-image test pass is not built; run denoise_dir on a checkpoint')
+    if (args.clean_data_ratio or 0) > 0:
+        raise NotImplementedError('--clean_data_ratio > 0: clean-clean mixing is not built')
+    unknown = set(args.debug_options) - set(DEBUG_OPTIONS)
+    if unknown:
+        raise ValueError(f'unknown debug options {sorted(unknown)} (available: {DEBUG_OPTIONS})')
+
+
+def get_weights(args):
+    '''Loss weights from the weight_* options, as nn_common.py:423-452 means them (its last branches raise as written): a missing
+    weight counts as 0, no weight at all means MS-SSIM alone, and weights that do not sum to 1 are divided by their total.'''
+    weights = {'MSSSIM': 0, 'L1': 0, 'MSE': 0, 'SSIM': 0, 'D1': 0, 'D2': 0}
+    for key in weights:
+        weights[key] = getattr(args, 'weight_' + key, None) or 0
+    total = sum(weights.values())
+    if total == 0:
+        weights['MSSSIM'] = 1
+        print('Using default weights')
+    elif total != 1:
+        for key in weights:
+            weights[key] /= total
+    print(f'Loss weights: {weights}')
+    return weights
+
+
+# ------------------------------------------------------------------ the pieces of an epoch
+def delete_outperformed_models(dpath, keepers, model_t='generator', keep_all_output_images=False):
+    '''Removes the <model_t>_<epoch>.pt files, and the val/<epoch> and testimages/<epoch> directories unless
+    keep_all_output_images, whose epoch is not in keepers (nn_train.py:95-116).  Returns what it removed.'''
+    removed = []
+    for fn in sorted(os.listdir(dpath)):
+        fpath = os.path.join(dpath, fn)
+        if fn in ('val', 'testimages') and os.path.isdir(fpath):
+            if not keep_all_output_images:
+                for subdir in sorted(os.listdir(fpath)):
+                    if int(subdir) not in keepers:
+                        shutil.rmtree(os.path.join(fpath, subdir))
+                        removed.append(os.path.join(fpath, subdir))
+            continue
+        if not fn.startswith(f'{model_t}_'):
+            continue
+        epoch = int(fn.split('_')[1].split('.')[0])
+        if epoch not in keepers:
+            os.remove(fpath)
+            removed.append(fpath)
+    return removed
+
+
+def update_lr_on_plateau(history, lr_loss, trainer, reduce_lr_factor):
+    '''The reference's learning-rate rule (nn_train.py:412-417): when the loss of this epoch is above every loss of the last
+    `history.maxlen` epochs, the rate is multiplied by reduce_lr_factor; then the loss joins the history.  Returns the new rate,
+    or None when it stays.'''
+    decayed = None
+    if len(history) > 0 and max(history) < lr_loss:
+        decayed = trainer.update_learning_rate(reduce_lr_factor)
+    history.append(lr_loss)
+    return decayed
+
+
+def train_epoch(pool, trainer, batch_size, losses, ssim_losses=None, exp_mult_min=1, exp_mult_max=1, rank=0, world=1,
+                log_interval=0, log=None):
+    '''One pass over the pool (nn_train.py:308-380 without the discriminators): a batch from the pool, one generator update, the
+    step's loss kept on the device in losses[k] (and, with ssim_losses, the mean SSIM loss of the step's output in ssim_losses[k]).
+    Nothing here waits for the GPU except an iteration line, every log_interval steps.  Returns the number of steps.'''
+    from .validation import criteria
+    iteration = 0
+    for iteration, draws in enumerate(pool.epoch(batch_size, rank=rank, world=world), 1):
+        clean, noisy = pool.batch(draws, exp_mult_min=exp_mult_min, exp_mult_max=exp_mult_max)
+        if ssim_losses is not None:
+            generated, loss = trainer.forward_backward(noisy, clean)
+            trainer.optimizer_step()
+            ssim_losses[iteration - 1] = criteria(generated, clean, {}, trainer.loss_cs, also=('SSIM',))['SSIM'].mean()
+        else:
+            loss = trainer.learn(noisy, clean)
+        losses[iteration - 1] = loss[0]        # stays on the device: the epoch's mean is read once
+        if log is not None and log_interval > 0 and iteration % log_interval == 0:
+            log(iteration, loss.item())
+    return iteration
+
+
+def save_model(model, model_dir, epoch, name='generator'):
+    '''<name>_<epoch>.pt = the module's state dict (Model.save_model, nn_common.py:68-73), as plain CPU tensors: the trainer's
+    parameters are views of one flat buffer, which torch.save would otherwise write whole behind every tensor'''
+    path = os.path.join(model_dir, '%s_%u.pt' % (name, epoch))
+    torch.save({k: v.detach().to('cpu', copy=True).contiguous() for k, v in model.state_dict().items()}, path)
+    return path
+
+
+def make_expname(argv):
+    return (datetime.datetime.now().isoformat()[:-10] + '_' + '_'.join(argv).replace('/', '-'))[0:255]
+
+
+# ------------------------------------------------------------------ the run
+def run(args, process_group=None, argv=None):
+    '''The training run, in the reference's order of events.  Returns the run directory.'''
+    from .crop_pool import CropPool
+    from .train import UtNetTrainer
+    from .validation import ValidationSet, validate
+
+    check_supported(args)
+    if not torch.cuda.is_available():
+        raise RuntimeError('nn_train: no GPU visible; nind_denoise_amd has no CPU fallback')
+    device = nn_common.default_device()
+    argv = ['nn_train.py'] + sys.argv[1:] if argv is None else list(argv)
+    for name in ('models_dpath', 'train_data', 'batch_size', 'g_lr', 'beta1', 'patience', 'reduce_lr_factor'):
+        if getattr(args, name) is None:
+            raise ValueError(f'nn_train: --{name} is not set (on the command line or in a config file)')
+    weights = get_weights(args)
+    rank, world = 0, 1
+    if process_group is not None:
+        import torch.distributed as tdist
+        rank, world = tdist.get_rank(process_group), tdist.get_world_size(process_group)
+
+    expname = args.expname if args.expname else make_expname(argv)
+    model_dir = os.path.join(args.models_dpath, expname)
+    os.makedirs(model_dir, exist_ok=True)
+    jsonsaver = json_saver.JSONSaver(os.path.join(model_dir, 'trainres.json'), step_type='epoch')
+    p = Printer(file_path=os.path.join(model_dir, 'train.log'))
+    p.print(args)
+    p.print('cmd: python3 ' + ' '.join(argv))
+    args.test_reserve = get_test_reserve_list(args.test_reserve)
+    p.print(f'test_reserve: {args.test_reserve}')
+    torch.manual_seed(args.seed)
+
+    # Train data
+    if not args.min_crop_size and 'check_dataset' in args.debug_options:
+        args.min_crop_size = args.cs
+    pool = CropPool.from_directories(args.train_data, test_reserve=args.test_reserve, min_crop_size=args.min_crop_size or None,
+                                     cs=args.cs, device=device, seed=args.seed)
+    if args.loss_cs is None:      # the <UCS> of a directory named <DSNAME>_<CS>_<UCS> (nn_train.py:220-222)
+        parts = os.path.basename(os.path.normpath(os.fspath(args.train_data[0]))).split('_')
+        if len(parts) < 3 or not parts[-1].isdigit():
+            raise ValueError(f'nn_train: --loss_cs is not set and {args.train_data[0]} is not named <DSNAME>_<CS>_<UCS>')
+        args.loss_cs = int(parts[-1])
+    if args.cs is None:
+        args.cs = pool.cs
+    if 'short_run' in args.debug_options:
+        pool.keep_groups(3 * args.batch_size)
+    steps = pool.n_groups // args.batch_size // world
+    p.print(f'Crop pool: {pool.n_groups} groups, {pool.n_images} images, {pool.nbytes / 1e6:.1f} MB in HBM; {steps} steps per epoch')
+
+    # init models
+    model = nn_common.Model.instantiate_model(models_dpath=args.models_dpath, model_path=args.g_model_path, network='UtNet',
+                                              device=device, pfun=p.print, keyword='generator', funit=args.g_funit,
+                                              activation=args.g_activation)
+    trainer = UtNetTrainer(model, lr=args.g_lr, beta1=args.beta1, weights={k: v for k, v in weights.items() if k[0] != 'D'},
+                           device=device, process_group=process_group, loss_cs=args.loss_cs)
+    model.train()
+    want_ssim = weights['SSIM'] > 0 or args.compute_SSIM_anyway
+    exp_mult_min = 1 if args.exp_mult_min is None else args.exp_mult_min
+    exp_mult_max = 1 if args.exp_mult_max is None else args.exp_mult_max
+
+    # Validation data
+    validation_loss = None
+    if args.validation_interval > 0:
+        if args.validation_set_yaml is None:
+            raise ValueError('nn_train: --validation_set_yaml is not set (or give --validation_interval 0)')
+        validation_set = ValidationSet(args.validation_set_yaml, device=device, cs=args.cs)
+
+        def get_validation_dpath(epoch):
+            return os.path.join(model_dir, 'val', str(epoch)) if 'output_val_images' in args.debug_options else None
+        validation_loss, _ = validate(model, validation_set, trainer.weights, args.loss_cs, batch_size=args.val_batch_size,
+                                      output_to_dir=get_validation_dpath(0))
+        jsonsaver.add_res(0, {'validation_loss': validation_loss}, write=True)
+        p.print(f'Validation loss: {validation_loss}')
+
+    with open(os.path.join(model_dir, 'config.yaml'), 'w') as fp:
+        yaml.dump(vars(args), fp)
+
+    start_time = time.time()
+    generator_loss_hist = collections.deque(maxlen=args.patience)
+    generator_learning_rate = trainer.lr
+    losses = torch.zeros(max(steps, 1), dtype=torch.float32, device=device)
+    ssim_losses = torch.zeros_like(losses)
+
+    # Train
+    for epoch in range(args.start_epoch, args.epochs):
+        epoch_start_time = time.time()
+        iteration = train_epoch(pool, trainer, args.batch_size, losses, ssim_losses if want_ssim else None, exp_mult_min,
+                                exp_mult_max, rank, world, args.log_interval,
+                                lambda it, loss: p.print('Epoch %u batch %u/%u: loss G: weighted: %.3f' % (epoch, it, steps, loss)))
+
+        # cleanup previous epochs
+        removed = delete_outperformed_models(dpath=model_dir, keepers=jsonsaver.get_best_steps(), model_t='generator',
+                                             keep_all_output_images='keep_all_output_images' in args.debug_options)
+        p.print(f'delete_outperformed_models removed {removed}')
+
+        # Do validation
+        if args.validation_interval > 0 and epoch % args.validation_interval == 0:
+            validation_loss, _ = validate(model, validation_set, trainer.weights, args.loss_cs, batch_size=args.val_batch_size,
+                                          output_to_dir=get_validation_dpath(epoch))
+            jsonsaver.add_res(epoch, {'validation_loss': validation_loss}, write=False)
+            p.print(f'Validation loss: {validation_loss}')
+
+        p.print('Epoch %u summary:' % epoch)
+        p.print('Time elapsed (s): %u (epoch), %u (total)' % (time.time() - epoch_start_time, time.time() - start_time))
+        p.print('Generator:')
+        if iteration > 0:
+            means = torch.stack((losses[:iteration].double().mean(), ssim_losses[:iteration].double().mean())).tolist()
+            if want_ssim:
+                p.print('Average SSIM loss: %f' % means[1])
+                jsonsaver.add_res(epoch, {'train_SSIM_loss': means[1]}, write=False)
+            average_g_weighted_loss = means[0]
+            p.print('Average weighted loss: %f' % average_g_weighted_loss)
+            jsonsaver.add_res(epoch, {'train_weighted_loss': average_g_weighted_loss}, write=False)
+            lr_loss = validation_loss if validation_loss is not None else average_g_weighted_loss
+            hist = list(generator_loss_hist)
+            if update_lr_on_plateau(generator_loss_hist, lr_loss, trainer, args.reduce_lr_factor) is not None:
+                # (the rate the optimizer now uses; the reference reports it multiplied by the factor once more, nn_common.py:252-255)
+                generator_learning_rate = trainer.lr
+                p.print(f'Generator learning rate updated to {generator_learning_rate} because generator_loss_hist={hist} < lr_loss={lr_loss}')
+            jsonsaver.add_res(epoch, {'gen_lr': generator_learning_rate}, write=True)
+        else:
+            p.print('Generator learned nothing')
+        if rank == 0:
+            save_model(model, model_dir, epoch, 'generator')
+        if args.time_limit and args.time_limit < time.time() - start_time:
+            p.print('Time is up')
+            break
+        if args.min_lr is not None and generator_learning_rate < args.min_lr:
+            p.print('Minimum learning rate reached')
+            break
+    return model_dir
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    args = parse_args(argv)
+    run(args, argv=['nn_train.py'] + argv)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

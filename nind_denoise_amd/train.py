@@ -1,7 +1,7 @@
 """UtNet training step on MI355X (BASELINE config 5): forward + loss + backward in libnind_hip.so, Adam(amsgrad) on flat
 buffers, data parallel over RCCL.
 
-Mirrors the reference's generator update (/root/reference/src/nind_denoise/nn_common.py:163-218 and the loop body of
+Mirrors the reference's generator update for any activation the network takes (/root/reference/src/nind_denoise/nn_common.py:163-218 and the loop body of
 nn_train.py:308-380):  generated = model(noisy).clip(0,1);  loss = sum_k weight_k * criterion_k(generated, clean);
 loss.backward();  Adam(lr, betas=(beta1, .999), amsgrad=True).step().   Criteria: L1, MSE, SSIM and MSSSIM (the
 reference's SSIM / MS-SSIM criteria come from piqa, which is not installed here: csrc/ssim.hip restates its published
@@ -25,8 +25,6 @@ from .networks.UtNet import UtNet, valid_cs
 class UtNetTrainer:
     def __init__(self, model: UtNet, lr=1e-4, beta1=0.75, beta2=0.999, eps=1e-8, amsgrad=True,
                  weights=None, device=None, process_group=None, loss_cs=None):
-        if model.activation != "PReLU":
-            raise NotImplementedError("the HIP training step implements PReLU networks")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.device.type != "cuda":
             raise RuntimeError("UtNetTrainer needs a GPU (no CPU fallback)")
@@ -50,6 +48,8 @@ class UtNetTrainer:
         for i, name in enumerate(_lib.utnet_tensor_names()):
             off, cnt = ctypes.c_size_t(), ctypes.c_size_t()
             _lib.check(self.lib.nd_utnet_param_range(self.funit, i, off, cnt))
+            if name not in sd:                 # a PReLU slope of a network with another activation: the step ignores its slot
+                continue
             p = sd[name]
             assert p.numel() == cnt.value, (name, p.numel(), cnt.value)
             view = self.flat[off.value:off.value + cnt.value].view_as(p)
@@ -96,16 +96,24 @@ class UtNetTrainer:
         with torch.cuda.device(self.device):
             ws = self.workspace(h, batch, w)
             # loss_cs: an L x L centre crop of the H x W output (pt_ops.pt_crop_batch), 0 = the whole output
-            _lib.check(self.lib.nd_utnet_train_step_hw(self.funit, self.model.flags, self.flat.data_ptr(), self.grads.data_ptr(),
-                                                       self.blobs.data_ptr(), noisy.data_ptr(), clean.data_ptr(), y.data_ptr(),
-                                                       float(self.weights.get("L1", 0.0)), float(self.weights.get("MSE", 0.0)),
-                                                       float(self.weights.get("SSIM", 0.0)), float(self.weights.get("MSSSIM", 0.0)),
-                                                       self.loss.data_ptr(), batch, h, w, int(self.loss_cs or 0), ws.data_ptr(),
-                                                       ws.numel(), _lib.stream_ptr(self.device), self.averager.event_ptrs,
-                                                       len(self.averager.buckets)), "nd_utnet_train_step_hw")
+            _lib.check(self.lib.nd_utnet_train_step_act_hw(
+                self.funit, _lib.ACT[self.model.activation], self.model.flags, self.flat.data_ptr(), self.grads.data_ptr(),
+                self.blobs.data_ptr(), noisy.data_ptr(), clean.data_ptr(), y.data_ptr(),
+                float(self.weights.get("L1", 0.0)), float(self.weights.get("MSE", 0.0)),
+                float(self.weights.get("SSIM", 0.0)), float(self.weights.get("MSSSIM", 0.0)),
+                self.loss.data_ptr(), batch, h, w, int(self.loss_cs or 0), ws.data_ptr(),
+                ws.numel(), _lib.stream_ptr(self.device), self.averager.event_ptrs,
+                len(self.averager.buckets)), "nd_utnet_train_step_act_hw")
             # RCCL: nine all-reduces (0.6 ... 57 MB for UtNet(64)), each behind its bucket's event on a side stream
             self.averager.reduce()
         return y, self.loss
+
+    def evaluate(self, validation_set, batch_size=32, output_to_dir=None, also=()):
+        """The validation pass on this trainer's network, weights and loss crop (validation.validate): (mean weighted loss as a
+        float, the per-sample weighted losses on the device)."""
+        from .validation import validate
+        return validate(self.model, validation_set, self.weights, self.loss_cs, batch_size=batch_size, output_to_dir=output_to_dir,
+                        also=also)
 
     def optimizer_step(self):
         self.steps += 1

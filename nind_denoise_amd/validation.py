@@ -1,0 +1,145 @@
+"""The validation pass of UtNet training on MI355X: the validation set in HBM, the network on the inference executor in batches,
+per-sample criteria from one launch sequence (csrc/criteria.hip, nd_criteria).
+
+Restates validate_generator (nn_train.py:51-71) and ValidationDataset (dataset_torch_3.py:403-428) of the reference, which
+validate one image at a time and read every file again every epoch: the loss of a validation pass is the mean over the images of
+each image's own weighted loss (Generator.compute_loss on a batch of one, nn_common.py:226-241), so the batched pass needs the
+criteria per sample, not per batch.
+"""
+import os
+
+import numpy as np
+import torch
+import yaml
+
+from . import _lib
+from .common.libs import np_imgops
+
+COLUMNS = ("L1", "MSE", "SSIM", "MSSSIM")     # columns 0..3 of nd_criteria; column 4 is the weighted sum
+_workspaces = {}                               # device -> uint8 tensor, grown on demand (nothing is carried between two calls)
+
+
+def _workspace(device, nbytes):
+    ws = _workspaces.get(str(device))
+    if ws is None or ws.numel() < nbytes:
+        ws = _workspaces[str(device)] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+def criteria(generated, target, weights, loss_cs=None, also=()):
+    """Per-sample criteria of a batch: a dict of [B] float32 device tensors with keys L1, MSE, SSIM, MSSSIM and weighted.
+    generated: the raw network output (it is clipped to [0, 1] here, Generator.denoise_batch); target: the clean batch; both
+    [B,3,H,W] on the GPU.  weights: {name: weight}; a criterion is computed when its weight is not zero or `also` names it
+    (--compute_SSIM_anyway), else its entry is zero.  loss_cs: the centre window the criteria see (None or 0: the whole image)."""
+    if generated.shape != target.shape or generated.dim() != 4 or generated.size(1) != 3:
+        raise ValueError(f"expected two [B,3,H,W] batches, got {tuple(generated.shape)} and {tuple(target.shape)}")
+    if generated.device.type != "cuda" or target.device != generated.device:
+        raise RuntimeError("criteria run on the GPU only (no CPU fallback): move both batches to the device")
+    unknown = (set(k for k, v in weights.items() if v) | set(also)) - set(COLUMNS)
+    if unknown:
+        raise NotImplementedError(f"criteria {sorted(unknown)} are not available (L1, MSE, SSIM, MSSSIM)")
+    y = generated.detach().to(torch.float32).contiguous()
+    t = target.detach().to(torch.float32).contiguous()
+    n, _, h, w = y.shape
+    loss_cs = int(loss_cs or 0)
+    bits = sum(1 << COLUMNS.index(k) for k in set(also))
+    lib = _lib.load()
+    out = torch.empty(n, 5, dtype=torch.float32, device=y.device)
+    with torch.cuda.device(y.device):
+        nbytes = lib.nd_criteria_workspace_bytes(n, h, w, loss_cs)
+        if nbytes == 0:      # let the library name what is wrong with the shape
+            _lib.check(lib.nd_criteria(None, None, n, h, w, loss_cs, 0.0, 0.0, 0.0, 0.0, 0, None, None, 0, None), "nd_criteria")
+        ws = _workspace(y.device, nbytes)
+        _lib.check(lib.nd_criteria(y.data_ptr(), t.data_ptr(), n, h, w, loss_cs, *[float(weights.get(k) or 0.0) for k in COLUMNS],
+                                   bits, out.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(y.device)), "nd_criteria")
+    res = {k: out[:, i] for i, k in enumerate(COLUMNS)}
+    res["weighted"] = out[:, 4]
+    return res
+
+
+def center_crop_pair(ximg, yimg, cs, names=("<clean>", "<noisy>")):
+    """np_imgops.np_crop_img_pair(ximg, yimg, cs, CropMethod.CENTER) on two [3,H,W] arrays: x0 = (W - cs) // 2, y0 = (H - cs) // 2.
+    ValueError naming the file for differing shapes or a side shorter than cs (the reference fails later, inside the network)."""
+    if ximg.shape != yimg.shape:
+        raise ValueError(f"ValidationSet: {names[0]} is {ximg.shape[2]}x{ximg.shape[1]} but {names[1]} is {yimg.shape[2]}x{yimg.shape[1]}")
+    _, h, w = ximg.shape
+    if h < cs or w < cs:
+        raise ValueError(f"ValidationSet: {names[0]} is {w}x{h}, smaller than the crop size {cs}")
+    x0, y0 = (w - cs) // 2, (h - cs) // 2
+    return ximg[:, y0:y0 + cs, x0:x0 + cs], yimg[:, y0:y0 + cs, x0:x0 + cs]
+
+
+class ValidationSet:
+    """The reference's ValidationDataset, read once and kept in HBM: .clean and .noisy, two [N,3,cs,cs] float32 tensors.
+    val_tuples: a list of [clean_path, noisy_path] pairs, or the path of a yaml file holding one.  Iterating gives the
+    reference's items, (clean, noisy) per pair."""
+
+    def __init__(self, val_tuples, device, cs):
+        if isinstance(val_tuples, (str, os.PathLike)):
+            with open(val_tuples, 'r') as fp:
+                val_tuples = yaml.safe_load(fp)
+        if not val_tuples:
+            raise ValueError("ValidationSet: no validation pair")
+        self.val_tuples = [list(pair) for pair in val_tuples]
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.cs = int(cs)
+        clean = np.empty((len(self.val_tuples), 3, self.cs, self.cs), dtype=np.float32)
+        noisy = np.empty_like(clean)
+        for i, (xpath, ypath) in enumerate(self.val_tuples):
+            ximg = np_imgops.img_path_to_np_flt(xpath)
+            yimg = np_imgops.img_path_to_np_flt(ypath)
+            clean[i], noisy[i] = center_crop_pair(ximg, yimg, self.cs, (xpath, ypath))
+        self.clean = torch.from_numpy(clean).to(self.device)
+        self.noisy = torch.from_numpy(noisy).to(self.device)
+
+    @classmethod
+    def from_tensors(cls, clean, noisy, device=None):
+        """A set from two [N,3,cs,cs] batches that are already cropped (no file is read)."""
+        if clean.shape != noisy.shape or clean.dim() != 4 or clean.size(1) != 3 or clean.size(2) != clean.size(3) or not len(clean):
+            raise ValueError(f"ValidationSet.from_tensors: expected two [N,3,cs,cs] batches, got {tuple(clean.shape)} and {tuple(noisy.shape)}")
+        self = cls.__new__(cls)
+        self.val_tuples = None
+        self.device = torch.device(device) if device is not None else clean.device
+        self.cs = clean.size(2)
+        self.clean = clean.to(self.device, torch.float32).contiguous()
+        self.noisy = noisy.to(self.device, torch.float32).contiguous()
+        return self
+
+    def __len__(self):
+        return self.clean.shape[0]
+
+    def __getitem__(self, i):
+        return self.clean[i], self.noisy[i]
+
+
+def validate(model, validation_set, weights, loss_cs, batch_size=32, output_to_dir=None, also=()):
+    """validate_generator (nn_train.py:51-71) with its batch-1 loop batched: the module in eval() mode under no_grad -- the
+    inference executor, the arithmetic denoise_image runs on the checkpoint -- over the set in batches (the last one partial), the
+    per-sample criteria of each batch, and the mean over all samples of the weighted loss.  Returns (that mean as a Python float,
+    the per-sample weighted losses as an [N] device tensor); one host synchronisation per call.  The module is left in train()
+    mode, as the reference leaves it.
+    output_to_dir (debug option output_val_images): <dir>/<i>.tif, 8-bit, the clipped output with its borders."""
+    if batch_size < 1:
+        raise ValueError(f"validate: batch_size {batch_size}")
+    n = len(validation_set)
+    per_sample = torch.empty(n, dtype=torch.float32, device=validation_set.clean.device)
+    outputs = []
+    model.eval()
+    try:
+        with torch.no_grad():
+            for b0 in range(0, n, batch_size):
+                noisy, clean = validation_set.noisy[b0:b0 + batch_size], validation_set.clean[b0:b0 + batch_size]
+                y = model(noisy)
+                per_sample[b0:b0 + noisy.shape[0]] = criteria(y, clean, weights, loss_cs, also)["weighted"]
+                if output_to_dir is not None:
+                    outputs.append(y)
+    finally:
+        model.train()
+    # the mean in float64 over the fp32 per-sample values, as statistics.mean of the reference's Python floats; one synchronisation
+    avgloss = per_sample.double().mean().item()
+    if output_to_dir is not None:
+        from .denoise_image import _save_dbg_jpg      # torchvision.utils.save_image's conversion: clamp, * 255 + 0.5, uint8
+        os.makedirs(output_to_dir, exist_ok=True)
+        for i, img in enumerate(torch.cat(outputs)):
+            _save_dbg_jpg(img, os.path.join(output_to_dir, str(i) + '.tif'))
+    return avgloss, per_sample

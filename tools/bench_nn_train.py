@@ -1,0 +1,151 @@
+#!/usr/bin/env python3
+"""nn_train benchmark: what the epoch loop, the validation pass and the per-sample criteria cost on one GPU.
+
+    python tools/bench_nn_train.py [--groups 1024] [--cs 184] [--batch 30] [--pairs 300] [--out profiles/nn_train.json]
+
+One process measures:
+  (a) crops/s of nn_train.train_epoch (pool epoch + batch + learn + the loss kept on the device) for UtNet(64) on a synthetic
+      pool, against UtNetTrainer.learn on one resident batch, in alternating windows;
+  (b) validation.validate over `pairs` pairs at cs^2 in batches, against the pass the parent revision could run: one image at a
+      time through the module, torch / pt_losses criteria on the clipped output, one .item() per image;
+  (c) ms per nd_criteria call at batch x 3 x cs^2, with and without MS-SSIM (device events around `iters` calls).
+Images are seeded noise: none of the kernels' traffic depends on the picture."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from nind_denoise_amd import nn_train, synth  # noqa: E402
+from nind_denoise_amd.common.libs import pt_losses  # noqa: E402
+from nind_denoise_amd.crop_pool import CropPool  # noqa: E402
+from nind_denoise_amd.networks.UtNet import UtNet  # noqa: E402
+from nind_denoise_amd.train import UtNetTrainer  # noqa: E402
+from nind_denoise_amd.validation import ValidationSet, criteria, validate  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--groups", type=int, default=1024)
+    ap.add_argument("--side", type=int, default=256)
+    ap.add_argument("--cs", type=int, default=184)
+    ap.add_argument("--batch", type=int, default=30)
+    ap.add_argument("--pairs", type=int, default=300)
+    ap.add_argument("--val_batch", type=int, default=32)
+    ap.add_argument("--iters", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--funit", type=int, default=64)
+    ap.add_argument("--out", default=os.path.join("profiles", "nn_train.json"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_nn_train needs a GPU")
+    dev = torch.device("cuda", 0)
+    rng = np.random.default_rng(0)
+    pool = CropPool(dev, seed=1, cs=args.cs)
+    for _ in range(args.groups):
+        clean = rng.integers(0, 256, (3, args.side, args.side), dtype=np.uint8)
+        pool.add_group([clean], [clean ^ rng.integers(0, 16, clean.shape, dtype=np.uint8)])
+    pool.device_buffers()
+    steps = args.groups // args.batch
+
+    # ---- (a) the epoch loop against the resident step
+    net = UtNet(funit=args.funit)
+    net.load_state_dict(synth.make_utnet_state_dict(args.funit, seed=123))
+    weights = {"MSSSIM": 1.0}
+    tr = UtNetTrainer(net, lr=1e-4, beta1=0.75, device=dev, weights=weights, loss_cs=args.cs)
+    clean0, noisy0 = pool.batch(pool.draw(args.batch))
+    losses = torch.zeros(steps, device=dev)
+
+    def window(loop):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        if loop:
+            n = nn_train.train_epoch(pool, tr, args.batch, losses, None, 0.85, 1.15, log_interval=50, log=lambda it, loss: None)
+            mean = losses[:n].double().mean().item()            # the epoch's one synchronisation
+        else:
+            for k in range(steps):
+                losses[k] = tr.learn(noisy0, clean0)[0]
+            n, mean = steps, losses.double().mean().item()
+        return time.perf_counter() - t0, n, mean
+
+    for _ in range(args.warmup):
+        tr.learn(noisy0, clean0)
+        tr.learn(*reversed(pool.batch(pool.draw(args.batch), exp_mult_min=0.85, exp_mult_max=1.15)))
+    rates = {"resident": [], "epoch_loop": []}
+    for _ in range(args.rounds):                                 # alternating windows: both see the same machine
+        for name, loop in (("resident", False), ("epoch_loop", True)):
+            dt, n, mean = window(loop)
+            rates[name].append(round(args.batch * n / dt, 2))
+    mean_rate = {k: sum(v) / len(v) for k, v in rates.items()}
+
+    # ---- (b) validation: batched against one image at a time
+    vclean = torch.rand(args.pairs, 3, args.cs, args.cs, generator=torch.Generator().manual_seed(2))
+    vs = ValidationSet.from_tensors(vclean, (vclean + 0.05 * torch.randn(vclean.shape, generator=torch.Generator().manual_seed(3))).clip(0, 1), dev)
+    msssim = pt_losses.MS_SSIM_loss()
+
+    def one_by_one():
+        net.eval()
+        vals = []
+        with torch.no_grad():
+            for i in range(len(vs)):
+                clean, noisy = vs[i]
+                denoised = net(noisy.unsqueeze(0)).clip(0, 1)
+                vals.append(msssim(denoised, clean.unsqueeze(0)).mean().item())
+        net.train()
+        return sum(vals) / len(vals)
+
+    val = {"batched_s": [], "one_by_one_s": []}
+    for r in range(args.rounds + 1):
+        for name, fn in (("batched_s", lambda: validate(net, vs, weights, args.cs, batch_size=args.val_batch)[0]), ("one_by_one_s", one_by_one)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            loss = fn()
+            torch.cuda.synchronize()
+            if r:                                                # round 0 warms both up
+                val[name].append(round(time.perf_counter() - t0, 4))
+            val[name.replace("_s", "_loss")] = loss
+    vmean = {k: sum(v) / len(v) for k, v in val.items() if k.endswith("_s")}
+
+    # ---- (c) the criteria launches alone
+    y = torch.rand(args.batch, 3, args.cs, args.cs, device=dev) * 1.4 - 0.2
+    t = torch.rand(args.batch, 3, args.cs, args.cs, device=dev)
+    crit = {}
+    for name, w in (("l1_mse", {"L1": 0.5, "MSE": 0.5}), ("ssim", {"SSIM": 1.0}), ("msssim", {"MSSSIM": 1.0}),
+                    ("all_four", {"L1": 0.25, "MSE": 0.25, "SSIM": 0.25, "MSSSIM": 0.25})):
+        for _ in range(10):
+            criteria(y, t, w)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        torch.cuda.synchronize()
+        ev[0].record()
+        for _ in range(args.iters):
+            criteria(y, t, w)
+        ev[1].record()
+        torch.cuda.synchronize()
+        crit[name] = round(ev[0].elapsed_time(ev[1]) / args.iters, 5)
+
+    result = {
+        "device": torch.cuda.get_device_name(0),
+        "config": {"groups": args.groups, "source": f"{args.side}x{args.side} u8 pairs", "cs": args.cs, "batch": args.batch,
+                   "steps_per_epoch": steps, "rounds": args.rounds, "funit": args.funit, "weights": weights, "exp_mult": [0.85, 1.15],
+                   "pairs": args.pairs, "val_batch": args.val_batch, "iters": args.iters},
+        "a_epoch": {"crops_per_s_windows": rates, "crops_per_s_mean": {k: round(v, 2) for k, v in mean_rate.items()},
+                    "epoch_loop_over_resident": round(mean_rate["epoch_loop"] / mean_rate["resident"], 4),
+                    "crop_pool_record": 0.9948, "last_epoch_mean_loss": mean},
+        "b_validation": dict(val, mean_s={k: round(v, 4) for k, v in vmean.items()},
+                             one_by_one_over_batched=round(vmean["one_by_one_s"] / vmean["batched_s"], 2)),
+        "c_criteria_ms_per_call": dict(crit, bytes_read=2 * args.batch * 3 * args.cs * args.cs * 4),
+    }
+    print(json.dumps(result))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
