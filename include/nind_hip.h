@@ -88,7 +88,7 @@ typedef enum nd_flags {
                                  nd_unet_denoise_frame: the same switch for the UNet decoder (nd_unet_useful_region)             */
 } nd_flags;
 
-int nd_version(void);   /* 114 = this header */
+int nd_version(void);   /* 115 = this header */
 const char *nd_last_error(void);
 
 /* ---------------------------------------------------------------- tile geometry (host, pure integer)
@@ -303,16 +303,14 @@ int nd_layer_wgrad(int kind, const float *x_nchw, const float *dy_nchw, int batc
  * [batch,3,h,w] NCHW fp32 in HBM.  The workspace holds one (h, w, batch) geometry; nd_utnet_train_workspace_init_hw zero-fills
  * it once before its first use.  blobs: nd_utnet_train_blob_bytes of packed weights.
  *
- * nd_utnet_train_step_hw = device-side weight packing + forward + loss + backward of a PReLU network:
+ * nd_utnet_train_step_act_hw = device-side weight packing + forward + loss + backward, for any activation the network takes
+ * (act as in the two halves below):
  *     loss = w_l1 * mean|g - t| + w_mse * mean (g - t)^2 + w_ssim * mean_n(1 - SSIM_n(g, t))
  *            + w_msssim * mean_n(1 - MS-SSIM_n(g, t)),        g = clip(net(x), 0, 1), t = target   (nn_common.py:198-241;
  *     the SSIM terms as in nd_ssim_loss_grad; MS-SSIM needs a loss crop of at least 161 pixels)
  * loss_out: one float in HBM.  loss_cs > 0: the criteria see the centre loss_cs x loss_cs crop at y0 = (h - loss_cs) / 2,
  * x0 = (w - loss_cs) / 2 of output and target (pt_ops.pt_crop_batch, nn_train.py:319-323; --loss_cs), and the gradient is zero
- * outside it; 0: the whole output.
- *
- * nd_utnet_train_step_act_hw is the same step for any activation the network takes (act as in the two halves below);
- * nd_utnet_train_step_hw is its ND_ACT_PRELU form.
+ * outside it; 0: the whole output.  The loss and its gradient are nd_criteria_grad's, below.
  *
  * The two halves of the step for torch.autograd, so that the reference's own training statements
  * (nn_common.py:198-218: `self.model(noisy_batch).clip(0,1)`, `loss.backward()`) run unchanged on the module:
@@ -330,10 +328,6 @@ int nd_utnet_param_range(int funit, int tensor_idx, size_t *offset, size_t *coun
 size_t nd_utnet_train_blob_bytes(int funit);
 size_t nd_utnet_train_workspace_bytes_hw(int funit, int h, int w, int batch);
 int nd_utnet_train_workspace_init_hw(void *workspace, size_t workspace_bytes, int funit, int h, int w, int batch, void *stream);
-int nd_utnet_train_step_hw(int funit, int flags, const float *params, float *grads, void *blobs, const float *x_nchw,
-                           const float *target_nchw, float *y_out_nchw, float w_l1, float w_mse, float w_ssim, float w_msssim,
-                           float *loss_out, int batch, int h, int w, int loss_cs, void *workspace, size_t workspace_bytes,
-                           void *stream, void *const *bucket_events, int n_events);
 int nd_utnet_train_step_act_hw(int funit, int act, int flags, const float *params, float *grads, void *blobs, const float *x_nchw,
                                const float *target_nchw, float *y_out_nchw, float w_l1, float w_mse, float w_ssim, float w_msssim,
                                float *loss_out, int batch, int h, int w, int loss_cs, void *workspace, size_t workspace_bytes,
@@ -345,7 +339,7 @@ int nd_utnet_train_backward_hw(int funit, int act, int flags, const float *param
                                void *const *bucket_events, int n_events);
 /* Data-parallel training that overlaps the gradient reduction with the backward pass (BASELINE configs[4]): the flat gradient
  * buffer is cut into nd_utnet_grad_buckets = 9 contiguous ranges, one per decoder / encoder level, numbered in the order the
- * backward pass completes them.  bucket_events of nd_utnet_train_step_hw / nd_utnet_train_backward_hw: null, or n_events = 9
+ * backward pass completes them.  bucket_events of nd_utnet_train_step_act_hw / nd_utnet_train_backward_hw: null, or n_events = 9
  * hipEvent_t; bucket_events[k] is recorded on `stream` when bucket k is final, so a reducer on another stream can all-reduce it
  * under the backward of the shallower levels. */
 int nd_utnet_grad_buckets(int funit, size_t *offsets, size_t *counts, int max);
@@ -377,13 +371,24 @@ int nd_ssim_loss_grad(const float *x, const float *y, int n, int c, int h, int w
  * target are cut to the centre loss_cs x loss_cs window at y0 = (h - loss_cs) / 2, x0 = (w - loss_cs) / 2 (pt_ops.pt_crop_batch);
  * 0: the whole image.  out: [n][5] fp32, per sample { mean|g - t|, mean (g - t)^2, 1 - SSIM (nd_ssim), 1 - MS-SSIM (nd_ms_ssim),
  * weighted = sum_k w_k * column_k over the computed columns with a non-zero weight }.  A column is computed iff its weight != 0 or its
- * bit is set in `also` (bit k = column k); the others are written as 0.  ND_EINVAL as nd_utnet_train_step_hw: an SSIM window below
+ * bit is set in `also` (bit k = column k); the others are written as 0.  ND_EINVAL as nd_utnet_train_step_act_hw: an SSIM window below
  * 11, an MS-SSIM window below 161, loss_cs above h or w, a null pointer, n < 1 (also: n > 65535, a side above 16384);
  * ND_ENOMEM: a workspace below nd_criteria_workspace_bytes.  Stream-ordered, allocates nothing, deterministic (no atomics; partial
  * sums are added in a fixed order). */
 size_t nd_criteria_workspace_bytes(int n, int h, int w, int loss_cs);
 int nd_criteria(const float *y_nchw, const float *target_nchw, int n, int h, int w, int loss_cs, float w_l1, float w_mse,
                 float w_ssim, float w_msssim, int also, float *out, void *workspace, size_t workspace_bytes, void *stream);
+/* The same criteria as the training loss and its gradient (Generator.compute_loss, loss.backward(); nn_common.py:201-255) -- the
+ * loss section of nd_utnet_train_step_act_hw:   loss_out[0] = w_l1 * mean|g - t| + w_mse * mean (g - t)^2
+ *     + w_ssim * mean_n(1 - SSIM_n(g, t)) + w_msssim * mean_n(1 - MS-SSIM_n(g, t))     (written, not accumulated; means over the
+ * window), g = clip(y, 0, 1) on the centre window as above.  gy_nchw: [n,3,h,w] = d loss_out / d y, written in full: clip passes the
+ * gradient on the closed interval [0, 1], d|x|/dx = 0 at 0, and the gradient is exactly 0 outside the window.  Refusals as
+ * nd_criteria (n is not limited to 65535).  The workspace size for loss_cs = 0 serves every loss_cs of the same (n, h, w).
+ * Stream-ordered, allocates nothing, deterministic (no atomics). */
+size_t nd_criteria_grad_workspace_bytes(int n, int h, int w, int loss_cs);
+int nd_criteria_grad(const float *y_nchw, const float *target_nchw, int n, int h, int w, int loss_cs, float w_l1, float w_mse,
+                     float w_ssim, float w_msssim, float *loss_out, float *gy_nchw, void *workspace, size_t workspace_bytes,
+                     void *stream);
 
 /* The SSIM the reference vendors itself (libs/pytorch_ssim/__init__.py:20-35; loss.py:29-45 gen_score writes res.txt with it).
  * Not the piqa score above: the Gaussian (sigma 1.5, `window` taps) is applied with zero padding of window / 2, so the map is

@@ -105,9 +105,6 @@ _SIGNATURES = {
                                           c_size_t, c_void_p]),
     "nd_utnet_train_backward_hw": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                            c_void_p, c_size_t, c_void_p, POINTER(c_void_p), c_int]),
-    "nd_utnet_train_step_hw": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
-                                       c_float, c_float, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
-                                       POINTER(c_void_p), c_int]),
     "nd_utnet_train_step_act_hw": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                            c_float, c_float, c_float, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
                                            POINTER(c_void_p), c_int]),
@@ -124,6 +121,8 @@ _SIGNATURES = {
     "nd_mse": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nd_criteria_workspace_bytes": (c_size_t, [c_int] * 4),
     "nd_criteria": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_float] * 4 + [c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nd_criteria_grad_workspace_bytes": (c_size_t, [c_int] * 4),
+    "nd_criteria_grad": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_float] * 4 + [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "nd_conv_bench": (c_int, [c_int] * 9 + [c_void_p, c_size_t, c_void_p, POINTER(c_float)]),
     "nd_winograd_bench": (c_int, [c_int] * 8 + [c_void_p, c_size_t, c_void_p, POINTER(c_float)]),
     "nd_winograd_bench_flags": (c_int, [c_int] * 9 + [c_void_p, c_size_t, c_void_p, POINTER(c_float)]),

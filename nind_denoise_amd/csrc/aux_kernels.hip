@@ -658,3 +658,17 @@ int nd_launch_final1x1_stitch(const QpBuf &src, int cin, const float *w, const f
     ND_HIP(hipGetLastError());
     return ND_OK;
 }
+
+// ------------------------------------------------------------------ final sum of per-workgroup partials
+__global__ __launch_bounds__(256) void k_sum(const float *__restrict__ partial, int n, float scale, float *__restrict__ out) {
+    __shared__ float red[256];
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
+    acc = nd_block_sum(acc, red);
+    if (threadIdx.x == 0) out[0] = acc * scale;
+}
+int nd_launch_sum(const float *partial, int n, float scale, float *out, hipStream_t s) {
+    hipLaunchKernelGGL(k_sum, dim3(1), dim3(256), 0, s, partial, n, scale, out);
+    ND_HIP(hipGetLastError());
+    return ND_OK;
+}

@@ -26,6 +26,33 @@ void nd_set_error(const char *fmt, ...);
         if (r_ != 0) return r_; \
     } while (0)
 
+// ------------------------------------------------------------------ deterministic sums
+// Sum of v over the 256 threads of a workgroup through `red` (256 elements of LDS): a fixed tree, the same bits on every run.
+// T: float, double, or a vector of them (added component by component).  Every thread gets the total; `red` is free again
+// after the next __syncthreads().
+template <typename T>
+__device__ inline T nd_block_sum(T v, T *red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
+        __syncthreads();
+    }
+    return red[0];
+}
+// out[0] = scale * sum partial[0..n): one workgroup, fixed order (aux_kernels.hip)
+int nd_launch_sum(const float *partial, int n, float scale, float *out, hipStream_t s);
+
+// ------------------------------------------------------------------ the window the criteria see (criteria.hip)
+// The centre Lh x Lw window of an h x w image at (oy, ox): loss_cs x loss_cs at ((h - loss_cs) / 2, (w - loss_cs) / 2), or the
+// whole image for loss_cs = 0 (pt_ops.pt_crop_batch, nn_train.py:319-323).
+struct LossWindow {
+    int Lh, Lw, oy, ox;
+};
+// The one argument check of the criteria entry points and of the training step (`who`: the error prefix): n and the sides in
+// range, loss_cs within the image, a window of at least 11 pixels for SSIM and 161 for MS-SSIM.  Fills *win on success.
+int nd_loss_window(const char *who, int n, int h, int w, int loss_cs, bool ssim, bool msssim, LossWindow *win);
+
 // ------------------------------------------------------------------ quad-planar activation buffers
 // An activation tensor [B, C, H, W] lives in HBM as C/4 planes of float4 "channel quads":
 //     plane q, image b, row y, col x  ->  float4 at  ((q * B + b) * Hb + y + pad) * Wb + x + pad

@@ -80,16 +80,8 @@ __global__ __launch_bounds__(256) void k_ssim_tile(const float *__restrict__ x, 
         sum_ss += ss;
         sum_cs += cs;
     }
-    red[threadIdx.x] = make_float2(sum_ss, sum_cs);
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) {
-            red[threadIdx.x].x += red[threadIdx.x + k].x;
-            red[threadIdx.x].y += red[threadIdx.x + k].y;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[((size_t)plane * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = red[0];
+    const float2 sum = nd_block_sum(make_float2(sum_ss, sum_cs), red);
+    if (threadIdx.x == 0) partial[((size_t)plane * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = sum;
 }
 
 // stats[plane] = (mean ss, mean cs): one workgroup per plane, fixed summation order
@@ -102,16 +94,8 @@ __global__ __launch_bounds__(256) void k_ssim_reduce(const float2 *__restrict__ 
         a += p[i].x;
         b += p[i].y;
     }
-    red[threadIdx.x] = make_float2(a, b);
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) {
-            red[threadIdx.x].x += red[threadIdx.x + k].x;
-            red[threadIdx.x].y += red[threadIdx.x + k].y;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) stats[blockIdx.x] = make_float2(red[0].x * inv_count, red[0].y * inv_count);
+    const float2 sum = nd_block_sum(make_float2(a, b), red);
+    if (threadIdx.x == 0) stats[blockIdx.x] = make_float2(sum.x * inv_count, sum.y * inv_count);
 }
 
 // avg_pool2d(kernel 2, ceil_mode=True): a window hanging over the edge averages the pixels it has.  grid (.., H2, planes*2)
@@ -167,25 +151,8 @@ __global__ __launch_bounds__(256) void k_sqdiff_partial(const float *__restrict_
         const float d = x[i] - y[i];
         acc += d * d;
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-__global__ __launch_bounds__(256) void k_sum_scale(const float *__restrict__ partial, int n, float scale, float *__restrict__ out) {
-    __shared__ float red[256];
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = red[0] * scale;
+    acc = nd_block_sum(acc, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
 // ------------------------------------------------------------------ backward (SSIM / MS-SSIM as training losses)
@@ -475,9 +442,8 @@ extern "C" int nd_mse(const float *x, const float *y, size_t count, float *out, 
     if (!ws || ws_bytes < 4096) ND_FAIL(ND_ENOMEM, "nd_mse: workspace %zu B given, 4096 B needed", ws_bytes);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(k_sqdiff_partial, dim3(1024), dim3(256), 0, s, x, y, count, (float *)ws);
-    hipLaunchKernelGGL(k_sum_scale, dim3(1), dim3(256), 0, s, (const float *)ws, 1024, 1.f / (float)count, out);
     ND_HIP(hipGetLastError());
-    return ND_OK;
+    return nd_launch_sum((const float *)ws, 1024, 1.f / (float)count, out, s);
 }
 
 // ------------------------------------------------------------------ SSIM / MS-SSIM as differentiable losses

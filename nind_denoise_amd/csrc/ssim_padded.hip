@@ -80,13 +80,8 @@ __global__ __launch_bounds__(256) void k_ssimp_tile(const float *__restrict__ x,
         const float sxx = m[2] - mxx, syy = m[3] - myy, sxy = m[4] - mxy;
         sum += ((2.f * mxy + c1) * (2.f * sxy + c2)) / ((mxx + myy + c1) * (sxx + syy + c2));
     }
-    red[threadIdx.x] = sum;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[((size_t)plane * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = red[0];
+    sum = nd_block_sum(sum, red);
+    if (threadIdx.x == 0) partial[((size_t)plane * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = sum;
 }
 
 // out[sample] = sum of the sample's `count` partials (its c planes are contiguous) * inv_pixels: one workgroup per sample
@@ -96,13 +91,8 @@ __global__ __launch_bounds__(256) void k_ssimp_reduce(const float *__restrict__ 
     const float *p = partial + (size_t)blockIdx.x * count;
     double a = 0.;
     for (size_t i = threadIdx.x; i < count; i += 256) a += (double)p[i];
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = (float)(red[0] * inv_pixels);
+    a = nd_block_sum(a, red);
+    if (threadIdx.x == 0) out[blockIdx.x] = (float)(a * inv_pixels);
 }
 
 // grid (tiles_x, tiles_y, planes) of 16 x 16 gradient pixels; gx[plane] = gout[plane / C] * inv_pixels * d(sum of the plane's map)/dx

@@ -22,13 +22,8 @@ __global__ __launch_bounds__(256) void k_channel_sum1(const f32x4 *__restrict__ 
         const int y = i / W, x = i - y * W;
         acc += s[(long)(y + pad) * Wb + x + pad];
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[(long)q * gridDim.y + b] = red[0];
+    acc = nd_block_sum(acc, red);
+    if (threadIdx.x == 0) partial[(long)q * gridDim.y + b] = acc;
 }
 __global__ __launch_bounds__(64) void k_channel_sum2(const f32x4 *__restrict__ partial, int B, int C, float *__restrict__ out) {
     const int q = blockIdx.x;

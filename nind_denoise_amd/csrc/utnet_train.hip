@@ -7,8 +7,8 @@
 //   data gradient  the SAME conv kernel on the weight tensor read in its transposed role:
 //                  dgrad(Conv2d) = ConvTranspose2d, dgrad(ConvTranspose2d) = Conv2d, dgrad(ConvT 2x2 s2) = Conv 2x2 s2
 //   weight gradient k_wgrad (wgrad.hip): MFMA contraction over pixels on a common grid (k_repitch)
-// Small HBM-bound kernels below: PReLU backward (+ slope gradient), max-pool backward, final 1x1 backward, loss, bias
-// sums, device-side weight packing, Adam(amsgrad).
+// Small HBM-bound kernels below: PReLU backward (+ slope gradient), max-pool backward, final 1x1 backward, bias
+// sums, device-side weight packing, Adam(amsgrad).  The loss and its gradient: nd_criteria_grad (criteria.hip).
 // Gradients come out in ONE flat fp32 buffer in state-dict order, so the data-parallel all-reduce (RCCL) and the
 // optimizer are single flat operations.
 #include <math.h>
@@ -61,27 +61,8 @@ __global__ __launch_bounds__(256) void k_act_bwd(f32x4 *__restrict__ g, long gnp
         *gp = gv;
     }
     if (ACT != ND_ACT_PRELU) return;
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[(long)q * gridDim.x + b] = red[0];
-}
-
-// out[0] = scale * sum partial[0..n)   (one workgroup, fixed order)
-__global__ __launch_bounds__(256) void k_sum_partials(const float *__restrict__ partial, int n, float scale, float *__restrict__ out) {
-    __shared__ float red[256];
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = red[0] * scale;
+    acc = nd_block_sum(acc, red);
+    if (threadIdx.x == 0) partial[(long)q * gridDim.x + b] = acc;
 }
 
 // gfine[argmax of each 2x2 window] += gpool   (fwd: the forward values that were pooled; first maximum in row-major order)
@@ -115,62 +96,6 @@ __global__ void k_maxpool_bwd_add(const f32x4 *__restrict__ gpool, long pnp, int
     g[1] = o[1];
     g[gWb] = o[2];
     g[gWb + 1] = o[3];
-}
-
-// loss = w_l1 * mean|clip(y) - t| + w_mse * mean (clip(y) - t)^2 ;  gy = d loss / d y   (nn_common.py:198-199, 236-255)
-__global__ __launch_bounds__(256) void k_loss_grad(const float *__restrict__ y, const float *__restrict__ t, long n, float w_l1,
-                                                   float w_mse, float *__restrict__ gy, float *__restrict__ partial) {
-    __shared__ float red[256];
-    float acc = 0.f;
-    const float inv = 1.f / (float)n;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const float v = y[i];
-        const float c = fminf(fmaxf(v, 0.f), 1.f);
-        const float d = c - t[i];
-        acc += w_l1 * fabsf(d) + w_mse * d * d;
-        const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
-        const float pass = (v >= 0.f && v <= 1.f) ? 1.f : 0.f;   // clamp passes the gradient on [min, max]
-        gy[i] = pass * (w_l1 * sgn + w_mse * 2.f * d) * inv;
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) red[threadIdx.x] += red[threadIdx.x + k];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-
-// SSIM / MS-SSIM act on clip(y, 0, 1) (nn_common.py:198-199): yc = clip(y);  later gy += [0 <= y <= 1] * g(yc)
-__global__ void k_clip01(const float *__restrict__ y, long n, float *__restrict__ yc) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-        yc[i] = fminf(fmaxf(y[i], 0.f), 1.f);
-}
-__global__ void k_add_clip_grad(const float *__restrict__ y, const float *__restrict__ gc, long n, float *__restrict__ gy) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float v = y[i];
-        if (v >= 0.f && v <= 1.f) gy[i] += gc[i];
-    }
-}
-
-// pt_ops.pt_crop_batch (common/libs/pt_ops.py:1-8; nn_train.py:319-323): centre crop [N,H,W] -> [N,Lh,Lw],
-// y0 = (H - Lh) / 2, x0 = (W - Lw) / 2
-__global__ void k_center_crop(const float *__restrict__ src, int H, int W, int Lh, int Lw, long n_out, float *__restrict__ dst) {
-    const int oy = (H - Lh) / 2, ox = (W - Lw) / 2;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_out; i += (long)gridDim.x * blockDim.x) {
-        const int x = (int)(i % Lw), y = (int)((i / Lw) % Lh);
-        const long img = i / ((long)Lh * Lw);
-        dst[i] = src[(img * H + y + oy) * W + x + ox];
-    }
-}
-// the gradient on the crop back onto the full output: zero outside the crop
-__global__ void k_center_uncrop(const float *__restrict__ g, int H, int W, int Lh, int Lw, long n_full, float *__restrict__ dst) {
-    const int oy = (H - Lh) / 2, ox = (W - Lw) / 2;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_full; i += (long)gridDim.x * blockDim.x) {
-        const int x = (int)(i % W) - ox, y = (int)((i / W) % H) - oy;
-        const long img = i / ((long)H * W);
-        dst[i] = (x >= 0 && x < Lw && y >= 0 && y < Lh) ? g[(img * Lh + y) * Lw + x] : 0.f;
-    }
 }
 
 // data gradient of the final Conv2d(f,3,1) + crop: g[c][b][Y][X] = sum_co gy[co][b][Y-crop][X-crop] * w[co][c] (0 outside)
@@ -208,20 +133,12 @@ __global__ __launch_bounds__(256) void k_final_wgrad1(const float *__restrict__ 
         acc += act[(long)q * anp + ((long)b * Hb + y + crop) * Wb + x + crop] * gv;
         accb += gv;
     }
-    red[threadIdx.x] = acc;
-    redb[threadIdx.x] = accb;
-    __syncthreads();
-    for (int k = 128; k > 0; k >>= 1) {
-        if ((int)threadIdx.x < k) {
-            red[threadIdx.x] += red[threadIdx.x + k];
-            redb[threadIdx.x] += redb[threadIdx.x + k];
-        }
-        __syncthreads();
-    }
+    acc = nd_block_sum(acc, red);
+    accb = nd_block_sum(accb, redb);
     if (threadIdx.x == 0) {
         const long o = ((long)co * gridDim.y + q) * gridDim.z + b;
-        pw[o] = red[0];
-        pb[o] = redb[0];
+        pw[o] = acc;
+        pb[o] = accb;
     }
 }
 __global__ __launch_bounds__(64) void k_final_wgrad2(const f32x4 *__restrict__ pw, const float *__restrict__ pb, int planes, int B,
@@ -404,10 +321,8 @@ struct TrainPlan {
     size_t partial_floats;
     float *red;             // reduction scratch
     float *gy;              // d loss / d output  [B,3,H,W]
-    float *yclip, *gssim;   // SSIM / MS-SSIM terms: clip(y, 0, 1) and the gradient with respect to it  [B,3,H,W]
-    float *ycrop, *tcrop, *gcrop;   // a loss crop smaller than the output: centre crops of output / target and the gradient on the crop
-    char *ssim_ws;          // nd_ssim_loss_workspace_bytes(B, 3, H, W)
-    size_t ssim_ws_bytes;
+    char *crit_ws;          // nd_criteria_grad_workspace_bytes(B, H, W, 0): serves every loss_cs
+    size_t crit_ws_bytes;
     size_t bytes;
 };
 constexpr int kRedFloats = 1 << 19;   // reduction scratch: >= 4 floats x planes x batch
@@ -492,17 +407,9 @@ TrainPlan make_train_plan(int f, int h, int w, int B, char *base) {
     t.gy = (float *)(base ? base + off : nullptr);
     off += (size_t)B * 3 * h * w * 4;
     off = (off + 255) & ~(size_t)255;
-    t.yclip = (float *)(base ? base + off : nullptr);
-    off += ((size_t)B * 3 * h * w * 4 + 255) & ~(size_t)255;
-    t.gssim = (float *)(base ? base + off : nullptr);
-    off += ((size_t)B * 3 * h * w * 4 + 255) & ~(size_t)255;
-    for (float **pp : {&t.ycrop, &t.tcrop, &t.gcrop}) {
-        *pp = (float *)(base ? base + off : nullptr);
-        off += ((size_t)B * 3 * h * w * 4 + 255) & ~(size_t)255;
-    }
-    t.ssim_ws = base ? base + off : nullptr;
-    t.ssim_ws_bytes = nd_ssim_loss_workspace_bytes(B, 3, h, w);
-    off += (t.ssim_ws_bytes + 255) & ~(size_t)255;
+    t.crit_ws = base ? base + off : nullptr;
+    t.crit_ws_bytes = nd_criteria_grad_workspace_bytes(B, h, w, 0);
+    off += (t.crit_ws_bytes + 255) & ~(size_t)255;
     t.bytes = off;
     return t;
 }
@@ -556,7 +463,7 @@ extern "C" int nd_utnet_train_workspace_init_hw(void *ws, size_t ws_bytes, int f
 }
 
 // ---- the step in two halves: (1) weight packing + forward with the pre-activations kept, (2) backward from d loss / d output.
-// nd_utnet_train_step_hw runs both with the loss between them; nd_utnet_train_forward_hw / nd_utnet_train_backward_hw expose the halves
+// nd_utnet_train_step_act_hw runs both with the loss (nd_criteria_grad) between them; nd_utnet_train_forward_hw / nd_utnet_train_backward_hw expose the halves
 // to torch.autograd (networks/UtNet.py: model(x).clip(0, 1), loss.backward() of nn_common.py:198-218 then work unchanged).
 struct TrainCtx {
     int f, B, H, W, flags, act;
@@ -721,9 +628,7 @@ static int train_backward(TrainCtx &c, const float *params, float *grads, const 
             if (c.act == ND_ACT_PRELU) {
                 hipLaunchKernelGGL(k_act_bwd<ND_ACT_PRELU>, dim3(B, oplanes), dim3(256), 0, s, gq, go.np(), go.Hb, go.Wb, go.pad,
                                    (const f32x4 *)pr.base, pr.np(), oh, ow, slopes[l.prelu], t.red);
-                if (grads)
-                    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, (const float *)t.red, B * oplanes, 1.f,
-                                       G(prelu_name(l.key)));
+                if (grads) ND_TRY(nd_launch_sum(t.red, B * oplanes, 1.f, G(prelu_name(l.key)), s));
             } else if (c.act == ND_ACT_ELU) {
                 hipLaunchKernelGGL(k_act_bwd<ND_ACT_ELU>, dim3(B, oplanes), dim3(256), 0, s, gq, go.np(), go.Hb, go.Wb, go.pad,
                                    (const f32x4 *)pr.base, pr.np(), oh, ow, (const float *)nullptr, t.red);
@@ -783,7 +688,7 @@ static int train_backward(TrainCtx &c, const float *params, float *grads, const 
 }
 
 // One training step without the optimizer: packs the weights on the device, runs forward (act: ND_ACT_PRELU | ND_ACT_ELU |
-// ND_ACT_HARDSWISH, as in the two halves below; nd_utnet_train_step_hw is the PReLU form), the loss
+// ND_ACT_HARDSWISH, as in the two halves below), the loss (nd_criteria_grad, criteria.hip)
 //   loss = w_l1 * mean|g - target| + w_mse * mean (g - target)^2 + w_ssim * mean_n(1 - SSIM_n(g, target))
 //          + w_msssim * mean_n(1 - MS-SSIM_n(g, target)),      g = clip(y, 0, 1)          (nn_common.py:198-199, 226-241)
 // and the backward pass.  params / grads: flat fp32 buffers in state-dict order (nd_utnet_param_range);
@@ -795,61 +700,17 @@ extern "C" int nd_utnet_train_step_act_hw(int funit, int act, int flags, const f
                                           float *loss_out, int batch, int h, int w, int loss_cs, void *ws, size_t ws_bytes, void *stream,
                                           void *const *bucket_events, int n_events) {
     if (bucket_events && n_events != kNumBuckets) ND_FAIL(ND_EINVAL, "train step: %d bucket events expected", kNumBuckets);
-    // the criteria see the centre loss_cs x loss_cs crop (nn_train.py:319-323, pt_ops.pt_crop_batch), or the whole output
-    const int Lh = loss_cs > 0 ? loss_cs : h, Lw = loss_cs > 0 ? loss_cs : w, L = Lh < Lw ? Lh : Lw;
-    if (Lh > h || Lw > w) ND_FAIL(ND_EINVAL, "UtNet training: loss_cs=%d exceeds the crop size %dx%d", loss_cs, h, w);
-    if (w_msssim != 0.f && L < 161)
-        ND_FAIL(ND_EINVAL, "UtNet training: the MS-SSIM loss needs crops of at least 161 pixels (five scales of an 11-tap window), "
-                           "got %d; the reference fails on them too (pt_losses.py:20-28)", L);
-    if (w_ssim != 0.f && L < 11) ND_FAIL(ND_EINVAL, "UtNet training: the SSIM loss needs at least 11 pixels, got %d", L);
+    LossWindow win;   // refused before anything is launched
+    ND_TRY(nd_loss_window("UtNet training", batch, h, w, loss_cs, w_ssim != 0.f, w_msssim != 0.f, &win));
     if (!grads || !x || !target || !y_out || !loss_out) ND_FAIL(ND_EINVAL, "train step: null pointer");
     TrainCtx c;
     ND_TRY(train_ctx(c, funit, flags, act, params, blobs, batch, h, w, ws, ws_bytes, stream));
     ND_TRY(train_forward(c, params, x, y_out));
     TrainPlan &t = c.t;
-    hipStream_t s = c.s;
-    const int B = batch;
-    const bool crop = Lh != h || Lw != w;
-    // ---- 3. loss and its gradient, on the centre crop (the whole output when there is none)
-    const long nfull = (long)B * 3 * h * w, nout = (long)B * 3 * Lh * Lw;
-    const int lblocks = 1024;
-    const float *yl = y_out, *tl = target;
-    float *gl = t.gy;
-    if (crop) {
-        hipLaunchKernelGGL(k_center_crop, dim3(1024), dim3(256), 0, s, (const float *)y_out, h, w, Lh, Lw, nout, t.ycrop);
-        hipLaunchKernelGGL(k_center_crop, dim3(1024), dim3(256), 0, s, target, h, w, Lh, Lw, nout, t.tcrop);
-        yl = t.ycrop;
-        tl = t.tcrop;
-        gl = t.gcrop;
-    }
-    hipLaunchKernelGGL(k_loss_grad, dim3(lblocks), dim3(256), 0, s, yl, tl, nout, w_l1, w_mse, gl, t.red);
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, (const float *)t.red, lblocks, 1.f / (float)nout, loss_out);
-    ND_HIP(hipGetLastError());
-    if (w_ssim != 0.f || w_msssim != 0.f) {
-        hipLaunchKernelGGL(k_clip01, dim3(1024), dim3(256), 0, s, yl, nout, t.yclip);
-        int acc = 0;
-        if (w_ssim != 0.f) {
-            ND_TRY(nd_ssim_loss_grad(t.yclip, tl, B, 3, Lh, Lw, 0, w_ssim, loss_out, t.gssim, acc, t.ssim_ws, t.ssim_ws_bytes, s));
-            acc = 1;
-        }
-        if (w_msssim != 0.f)
-            ND_TRY(nd_ssim_loss_grad(t.yclip, tl, B, 3, Lh, Lw, 1, w_msssim, loss_out, t.gssim, acc, t.ssim_ws, t.ssim_ws_bytes, s));
-        hipLaunchKernelGGL(k_add_clip_grad, dim3(1024), dim3(256), 0, s, yl, (const float *)t.gssim, nout, gl);
-        ND_HIP(hipGetLastError());
-    }
-    if (crop) {
-        hipLaunchKernelGGL(k_center_uncrop, dim3(1024), dim3(256), 0, s, (const float *)t.gcrop, h, w, Lh, Lw, nfull, t.gy);
-        ND_HIP(hipGetLastError());
-    }
-
+    // ---- 3. loss and its gradient, on the centre window (the whole output when there is none)
+    ND_TRY(nd_criteria_grad(y_out, target, batch, h, w, loss_cs, w_l1, w_mse, w_ssim, w_msssim, loss_out, t.gy, t.crit_ws,
+                            t.crit_ws_bytes, stream));
     return train_backward(c, params, grads, t.gy, nullptr, bucket_events);
-}
-extern "C" int nd_utnet_train_step_hw(int funit, int flags, const float *params, float *grads, void *blobs, const float *x,
-                                      const float *target, float *y_out, float w_l1, float w_mse, float w_ssim, float w_msssim,
-                                      float *loss_out, int batch, int h, int w, int loss_cs, void *ws, size_t ws_bytes, void *stream,
-                                      void *const *bucket_events, int n_events) {
-    return nd_utnet_train_step_act_hw(funit, ND_ACT_PRELU, flags, params, grads, blobs, x, target, y_out, w_l1, w_mse, w_ssim, w_msssim,
-                                      loss_out, batch, h, w, loss_cs, ws, ws_bytes, stream, bucket_events, n_events);
 }
 // Buckets of the flat gradient buffer in the order the backward pass completes them (one per decoder / encoder level):
 // offsets / counts in floats.  Returns the number of buckets (9); fills at most `max` entries.

@@ -368,7 +368,7 @@ class BucketedGradientAverager:
 
     The flat state-dict-order gradient buffer is cut into the library's level buckets (nd_utnet_grad_buckets: up4 + tconvs4, ...,
     convs1 -- the order in which the backward pass completes them).  The training step records one HIP event per bucket on the
-    compute stream as soon as the bucket is final (nd_utnet_train_step_hw / nd_utnet_train_backward_hw); `reduce()` all-reduces
+    compute stream as soon as the bucket is final (nd_utnet_train_step_act_hw / nd_utnet_train_backward_hw); `reduce()` all-reduces
     bucket k on a side stream behind event k, i.e. under the backward of the shallower levels, and the compute stream only waits
     for the last (smallest) buckets.  On a gloo group (tests, the one-GPU rehearsal) the buckets are reduced one by one through
     host memory after the step; with CPU tensors there are no events at all.  No-op without an initialised process group."""

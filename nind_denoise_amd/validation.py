@@ -1,5 +1,6 @@
 """The validation pass of UtNet training on MI355X: the validation set in HBM, the network on the inference executor in batches,
-per-sample criteria from one launch sequence (csrc/criteria.hip, nd_criteria).
+per-sample criteria from one launch sequence (csrc/criteria.hip, nd_criteria), and the training form of the same criteria, the batch
+loss with its gradient (nd_criteria_grad).
 
 Restates validate_generator (nn_train.py:51-71) and ValidationDataset (dataset_torch_3.py:403-428) of the reference, which
 validate one image at a time and read every file again every epoch: the loss of a validation pass is the mean over the images of
@@ -26,11 +27,8 @@ def _workspace(device, nbytes):
     return ws
 
 
-def criteria(generated, target, weights, loss_cs=None, also=()):
-    """Per-sample criteria of a batch: a dict of [B] float32 device tensors with keys L1, MSE, SSIM, MSSSIM and weighted.
-    generated: the raw network output (it is clipped to [0, 1] here, Generator.denoise_batch); target: the clean batch; both
-    [B,3,H,W] on the GPU.  weights: {name: weight}; a criterion is computed when its weight is not zero or `also` names it
-    (--compute_SSIM_anyway), else its entry is zero.  loss_cs: the centre window the criteria see (None or 0: the whole image)."""
+def _checked(generated, target, weights, also=()):
+    """The argument checks of criteria and criteria_grad; returns the two batches as contiguous float32 tensors."""
     if generated.shape != target.shape or generated.dim() != 4 or generated.size(1) != 3:
         raise ValueError(f"expected two [B,3,H,W] batches, got {tuple(generated.shape)} and {tuple(target.shape)}")
     if generated.device.type != "cuda" or target.device != generated.device:
@@ -38,8 +36,15 @@ def criteria(generated, target, weights, loss_cs=None, also=()):
     unknown = (set(k for k, v in weights.items() if v) | set(also)) - set(COLUMNS)
     if unknown:
         raise NotImplementedError(f"criteria {sorted(unknown)} are not available (L1, MSE, SSIM, MSSSIM)")
-    y = generated.detach().to(torch.float32).contiguous()
-    t = target.detach().to(torch.float32).contiguous()
+    return generated.detach().to(torch.float32).contiguous(), target.detach().to(torch.float32).contiguous()
+
+
+def criteria(generated, target, weights, loss_cs=None, also=()):
+    """Per-sample criteria of a batch: a dict of [B] float32 device tensors with keys L1, MSE, SSIM, MSSSIM and weighted.
+    generated: the raw network output (it is clipped to [0, 1] here, Generator.denoise_batch); target: the clean batch; both
+    [B,3,H,W] on the GPU.  weights: {name: weight}; a criterion is computed when its weight is not zero or `also` names it
+    (--compute_SSIM_anyway), else its entry is zero.  loss_cs: the centre window the criteria see (None or 0: the whole image)."""
+    y, t = _checked(generated, target, weights, also)
     n, _, h, w = y.shape
     loss_cs = int(loss_cs or 0)
     bits = sum(1 << COLUMNS.index(k) for k in set(also))
@@ -55,6 +60,27 @@ def criteria(generated, target, weights, loss_cs=None, also=()):
     res = {k: out[:, i] for i, k in enumerate(COLUMNS)}
     res["weighted"] = out[:, 4]
     return res
+
+
+def criteria_grad(generated, target, weights, loss_cs=None):
+    """The training loss of a batch and its gradient (nd_criteria_grad, the loss section of the fused step): (loss, gy), a float32
+    device scalar -- the weighted sum of the batch means of the criteria with a non-zero weight -- and d loss / d generated,
+    [B,3,H,W], zero outside the loss_cs window.  Arguments as criteria."""
+    y, t = _checked(generated, target, weights)
+    n, _, h, w = y.shape
+    loss_cs = int(loss_cs or 0)
+    lib = _lib.load()
+    loss = torch.empty((), dtype=torch.float32, device=y.device)
+    gy = torch.empty_like(y)
+    with torch.cuda.device(y.device):
+        nbytes = lib.nd_criteria_grad_workspace_bytes(n, h, w, loss_cs)
+        if nbytes == 0:      # let the library name what is wrong with the shape
+            _lib.check(lib.nd_criteria_grad(None, None, n, h, w, loss_cs, 0.0, 0.0, 0.0, 0.0, None, None, None, 0, None), "nd_criteria_grad")
+        ws = _workspace(y.device, nbytes)
+        _lib.check(lib.nd_criteria_grad(y.data_ptr(), t.data_ptr(), n, h, w, loss_cs, *[float(weights.get(k) or 0.0) for k in COLUMNS],
+                                        loss.data_ptr(), gy.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(y.device)),
+                   "nd_criteria_grad")
+    return loss, gy
 
 
 def center_crop_pair(ximg, yimg, cs, names=("<clean>", "<noisy>")):

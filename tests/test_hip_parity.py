@@ -1290,7 +1290,7 @@ def _ddp_worker(port, outq):
 
 def test_bucketed_gradient_reduce_over_rccl(dev):
     """BASELINE configs[4] building block: the training step records one event per level bucket while the backward pass runs
-    (nd_utnet_train_step_hw) and the reducer all-reduces each bucket behind its event on a side stream (RCCL, world size 1 here:
+    (nd_utnet_train_step_act_hw) and the reducer all-reduces each bucket behind its event on a side stream (RCCL, world size 1 here:
     the transport and the event / stream ordering run, the sum is over one rank): two updates give the same parameters and
     gradients as without the reducer, bit for bit."""
     import socket

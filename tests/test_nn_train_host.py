@@ -253,9 +253,11 @@ def test_keep_groups_drops_the_tail_before_the_upload():
 # ------------------------------------------------------------------ the library
 def test_library_exports_the_new_entry_points():
     lib = _lib.load()
-    assert lib.nd_version() >= 114
-    assert {'nd_criteria', 'nd_criteria_workspace_bytes', 'nd_utnet_train_step_act_hw'} <= set(_lib.EXPORTS)
-    for name in ('nd_criteria', 'nd_utnet_train_step_act_hw'):
+    assert lib.nd_version() >= 115
+    assert {'nd_criteria', 'nd_criteria_workspace_bytes', 'nd_criteria_grad', 'nd_criteria_grad_workspace_bytes',
+            'nd_utnet_train_step_act_hw'} <= set(_lib.EXPORTS)
+    assert 'nd_utnet_train_step_hw' not in _lib.EXPORTS           # 115: nd_utnet_train_step_act_hw with ND_ACT_PRELU is that call
+    for name in ('nd_criteria', 'nd_criteria_grad', 'nd_criteria_grad_workspace_bytes', 'nd_utnet_train_step_act_hw'):
         assert hasattr(lib, name)
     hdr = open(os.path.join(ROOT, 'include', 'nind_hip.h')).read()
     code = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
@@ -283,3 +285,28 @@ def test_criteria_checks_its_arguments_before_any_launch():
         _lib.check(lib.nd_criteria(*dict(ok, ws_bytes=need - 1).values()))
     assert lib.nd_criteria_workspace_bytes(2, 184, 168, 185) == 0 and lib.nd_criteria_workspace_bytes(0, 184, 168, 0) == 0
     assert lib.nd_criteria_workspace_bytes(2, 184, 168, 161) < need
+
+
+def test_criteria_grad_checks_its_arguments_before_any_launch():
+    lib = _lib.load()
+    p = ctypes.c_void_p(256)          # never dereferenced: every call below fails its host checks
+    ok = dict(y=p, t=p, n=2, h=184, w=168, loss_cs=0, w_l1=0.0, w_mse=1.0, w_ssim=0.0, w_msssim=0.0, loss=p, gy=p, ws=p,
+              ws_bytes=1 << 40, stream=None)
+    bads = [dict(y=None), dict(t=None), dict(loss=None), dict(gy=None), dict(ws=None), dict(n=0), dict(loss_cs=185),
+            dict(loss_cs=169), dict(loss_cs=-1),
+            dict(w_msssim=1.0, loss_cs=160), dict(w_msssim=0.5, h=160, w=184),
+            dict(w_ssim=1.0, loss_cs=10), dict(w_ssim=0.5, h=184, w=10)]
+    for bad in bads:
+        args = dict(ok, **bad)
+        rc = lib.nd_criteria_grad(*args.values())
+        assert rc == -1, (bad, rc)
+        with pytest.raises(ValueError):
+            _lib.check(rc, 'nd_criteria_grad')
+    need = lib.nd_criteria_grad_workspace_bytes(2, 184, 168, 0)
+    assert need > 2 * 2 * 3 * 184 * 168 * 4
+    with pytest.raises(MemoryError):
+        _lib.check(lib.nd_criteria_grad(*dict(ok, ws_bytes=need - 1).values()))
+    assert lib.nd_criteria_grad_workspace_bytes(2, 184, 168, 185) == 0 and lib.nd_criteria_grad_workspace_bytes(0, 184, 168, 0) == 0
+    # one workspace serves a trainer that changes loss_cs between calls: the size for the whole image covers every window
+    for cs in (1, 11, 100, 161, 167, 168):
+        assert 0 < lib.nd_criteria_grad_workspace_bytes(2, 184, 168, cs) <= need, cs

@@ -405,7 +405,7 @@ def _check(what, bars, y, y_ref, loss, loss_ref, grads, grads_ref, dx=None, dx_r
 @pytest.mark.gpu
 @pytest.mark.parametrize("case,cs,weights", [("A", 184, {"MSSSIM": 1.0}), ("B", 136, {"MSE": 1.0})], ids=["A-184-MSSSIM", "B-136-MSE"])
 def test_fused_step_batch30_vs_float64(dev, case, cs, weights):
-    """UtNetTrainer.forward_backward (nd_utnet_train_step_hw) on 30 crops: A the reference's UtNet config (184, MS-SSIM),
+    """UtNetTrainer.forward_backward (nd_utnet_train_step_act_hw) on 30 crops: A the reference's UtNet config (184, MS-SSIM),
     B the bench shape (136, MSE)."""
     from nind_denoise_amd.networks.UtNet import UtNet
     from nind_denoise_amd.train import UtNetTrainer
