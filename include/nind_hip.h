@@ -88,7 +88,7 @@ typedef enum nd_flags {
                                  nd_unet_denoise_frame: the same switch for the UNet decoder (nd_unet_useful_region)             */
 } nd_flags;
 
-int nd_version(void);   /* 115 = this header */
+int nd_version(void);   /* 116 = this header */
 const char *nd_last_error(void);
 
 /* ---------------------------------------------------------------- tile geometry (host, pure integer)
@@ -110,6 +110,30 @@ int nd_tile_gather(const float *img_chw, int width, int height, int cs, int ucs,
                    int tile_begin, int tile_count, float *tiles_nchw, void *stream);
 int nd_stitch_add(float *canvas_chw, int width, int height, int cs, int ucs, int ol,
                   const float *tiles_nchw, int tile_begin, int tile_count, void *stream);
+
+/* The two index maps behind these kernels, as host functions (pure integer; the kernels run the same inline functions).
+ * nd_tile_source: pixel (y, x) of tile i shows frame pixel (*Y, *X) -- the symmetric mirror of OneImageDS.__getitem__: with
+ *   u = x0 + x,  X = u inside [0, W),  -1 - u left of it,  2W - 1 - u right of it; the same in y.
+ * nd_stitch_weight: pixel (y, x) of tile i is added to canvas pixel (*Y, *X) with weight *w: 0 outside the useful crop of
+ *   nd_tile_geom (*Y, *X then name no pixel), else 1, halved once for every condition of make_seamless_edges that holds.
+ * ND_EINVAL: a geometry nd_tile_grid refuses, a tile or pixel outside its range, a null output pointer.
+ *
+ * The adjoints of the two linear operators, for gradients through a tiled frame (frame_grad.py).  Stream-ordered, no atomics,
+ * deterministic; a result does not depend on how a tile range is cut into launches, except for the fp32 order of the += of
+ * nd_tile_gather_grad across launches.  tile_count = 0 is a no-op.
+ * nd_stitch_grad: gtiles_nchw[t, c, y, x] = w * gcanvas_chw[c, Y, X] over nd_stitch_weight, for tiles [tile_begin,
+ *   tile_begin + tile_count); every element of [tile_count,3,cs,cs] is written, 0 where w = 0.
+ * nd_tile_gather_grad: gimg_chw[c, Y, X] += the sum of gtiles_nchw over the tile pixels of the launch that nd_tile_source sends
+ *   to (Y, X) -- summed from 0 in ascending tile index, within a tile in ascending y * cs + x over its at most 3 x 3 pre-images
+ *   (direct and folded, per axis), then added to what gimg holds.  Its work is the launch's footprint -- the frame rows and
+ *   columns its tiles and their folds reach -- not the frame.
+ * ND_EINVAL: a null pointer, tiles outside the grid, cs above 16384, more than 65535 tiles in one launch. */
+int nd_tile_source(int i, int width, int height, int cs, int ucs, int ol, int y, int x, int *Y, int *X);
+int nd_stitch_weight(int i, int width, int height, int cs, int ucs, int ol, int y, int x, int *Y, int *X, float *w);
+int nd_stitch_grad(const float *gcanvas_chw, int width, int height, int cs, int ucs, int ol, int tile_begin, int tile_count,
+                   float *gtiles_nchw, void *stream);
+int nd_tile_gather_grad(const float *gtiles_nchw, int width, int height, int cs, int ucs, int ol, int tile_begin, int tile_count,
+                        float *gimg_chw, void *stream);
 
 /* ---------------------------------------------------------------- UtNet (UtNet.py:13-109)
  * Weight contract: the reference state-dict.  nd_utnet_num_tensors / nd_utnet_tensor_name

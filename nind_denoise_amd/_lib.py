@@ -51,6 +51,10 @@ _SIGNATURES = {
     "nd_tile_geom": (c_int, [c_int] * 6 + [POINTER(c_int)] * 4),
     "nd_tile_gather": (c_int, [c_void_p] + [c_int] * 7 + [c_void_p, c_void_p]),
     "nd_stitch_add": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p, c_int, c_int, c_void_p]),
+    "nd_tile_source": (c_int, [c_int] * 8 + [POINTER(c_int)] * 2),
+    "nd_stitch_weight": (c_int, [c_int] * 8 + [POINTER(c_int)] * 2 + [POINTER(c_float)]),
+    "nd_stitch_grad": (c_int, [c_void_p] + [c_int] * 7 + [c_void_p, c_void_p]),
+    "nd_tile_gather_grad": (c_int, [c_void_p] + [c_int] * 7 + [c_void_p, c_void_p]),
     "nd_utnet_num_tensors": (c_int, []),
     "nd_utnet_tensor_name": (c_char_p, [c_int]),
     "nd_utnet_packed_bytes": (c_size_t, [c_int, c_int]),

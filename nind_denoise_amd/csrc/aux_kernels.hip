@@ -20,14 +20,7 @@ template <> struct Elem<ND_F16> { typedef f16x8 vec; static constexpr int N = 8;
     }
 
 // ------------------------------------------------------------------ tile geometry (OneImageDS, denoise_image.py:100-143)
-struct TileGeo {
-    int W, H, cs, ucs, ol, pad, stride, cols, rows;
-};
-
-static __host__ __device__ inline int ceil_div_py(int a, int b) {  // math.ceil(a / b) for b > 0, any sign of a
-    return a >= 0 ? (a + b - 1) / b : -((-a) / b);
-}
-
+// TileGeo and the two index maps over it (nd_tile_source_map, nd_stitch_weight_map): nd_common.h
 static int make_geo(int W, int H, int cs, int ucs, int ol, TileGeo *g) {
     if (W <= 0 || H <= 0 || cs <= 0 || ucs <= 0 || ol < 0) ND_FAIL(ND_EINVAL, "tile grid: non-positive size");
     if (ucs - ol <= 0) ND_FAIL(ND_EINVAL, "tile grid: ucs (%d) must exceed the overlap (%d)", ucs, ol);
@@ -78,9 +71,6 @@ extern "C" int nd_tile_geom(int i, int W, int H, int cs, int ucs, int ol, int *x
     return ND_OK;
 }
 
-__device__ __forceinline__ int mirror_sym(int v, int n) {  // edge pixel repeated (np.flip of the adjacent band)
-    return v < 0 ? -1 - v : (v >= n ? 2 * n - 1 - v : v);
-}
 __device__ __forceinline__ int reflect_nr(int v, int n) {  // nn.ReflectionPad2d: edge pixel NOT repeated
     return v < 0 ? -v : (v >= n ? 2 * (n - 1) - v : v);
 }
@@ -91,10 +81,8 @@ __global__ void k_tile_gather(const float *__restrict__ img, TileGeo g, int tile
     const int yy = blockIdx.y;
     const int t = blockIdx.z;
     if (xx >= g.cs) return;
-    const int i = tile_begin + t;
-    const int yi = i / g.cols, xi = i - yi * g.cols;
-    const int sx = mirror_sym(xi * g.stride - g.pad + xx, g.W);
-    const int sy = mirror_sym(yi * g.stride - g.pad + yy, g.H);
+    int sy, sx;
+    nd_tile_source_map(g, tile_begin + t, yy, xx, &sy, &sx);
     const size_t plane = (size_t)g.W * g.H;
     const size_t tplane = (size_t)g.cs * g.cs;
     const float *s = img + (size_t)sy * g.W + sx;
@@ -430,6 +418,189 @@ extern "C" int nd_stitch_add(float *canvas, int W, int H, int cs, int ucs, int o
     if (yr <= 0) return ND_OK;
     dim3 grid((W + 255) / 256, yr);
     hipLaunchKernelGGL(k_stitch_add, grid, dim3(256), 0, (hipStream_t)stream, canvas, g, tiles, tile_begin, tile_count, yf);
+    ND_HIP(hipGetLastError());
+    return ND_OK;
+}
+
+// ------------------------------------------------------------------ adjoints of gather and stitch (gradients through a tiled frame)
+// Both operators are linear, so their adjoints are the transposed index maps: the stitch's is a gather from the canvas gradient,
+// the gather's a sum over the tile pixels that read a frame pixel.  Neither uses atomics: every output element has one thread,
+// which adds its terms in a fixed order.
+extern "C" int nd_tile_source(int i, int W, int H, int cs, int ucs, int ol, int y, int x, int *Y, int *X) {
+    TileGeo g;
+    ND_TRY(make_geo(W, H, cs, ucs, ol, &g));
+    if (!Y || !X) ND_FAIL(ND_EINVAL, "nd_tile_source: null output pointer");
+    if (i < 0 || i >= g.cols * g.rows || y < 0 || y >= cs || x < 0 || x >= cs)
+        ND_FAIL(ND_EINVAL, "nd_tile_source: tile %d of %d, pixel (%d, %d) of a %d-pixel tile", i, g.cols * g.rows, y, x, cs);
+    nd_tile_source_map(g, i, y, x, Y, X);
+    return ND_OK;
+}
+
+extern "C" int nd_stitch_weight(int i, int W, int H, int cs, int ucs, int ol, int y, int x, int *Y, int *X, float *w) {
+    TileGeo g;
+    ND_TRY(make_geo(W, H, cs, ucs, ol, &g));
+    if (!Y || !X || !w) ND_FAIL(ND_EINVAL, "nd_stitch_weight: null output pointer");
+    if (i < 0 || i >= g.cols * g.rows || y < 0 || y >= cs || x < 0 || x >= cs)
+        ND_FAIL(ND_EINVAL, "nd_stitch_weight: tile %d of %d, pixel (%d, %d) of a %d-pixel tile", i, g.cols * g.rows, y, x, cs);
+    *w = nd_stitch_weight_map(g, i, y, x, Y, X);
+    return ND_OK;
+}
+
+// the checks the two adjoint entry points share; *run = false: nothing to launch (tile_count 0)
+static int check_tile_range(const char *who, const void *a, const void *b, int W, int H, int cs, int ucs, int ol, int tile_begin,
+                            int tile_count, TileGeo *g, bool *run) {
+    ND_TRY(make_geo(W, H, cs, ucs, ol, g));
+    *run = false;
+    if (tile_begin < 0 || tile_count < 0 || tile_begin > g->cols * g->rows - tile_count)
+        ND_FAIL(ND_EINVAL, "%s: tiles [%d,%d) outside the grid of %d", who, tile_begin, tile_begin + tile_count, g->cols * g->rows);
+    if (tile_count == 0) return ND_OK;
+    if (!a || !b) ND_FAIL(ND_EINVAL, "%s: null pointer", who);
+    if (cs > 16384 || tile_count > 65535) ND_FAIL(ND_EINVAL, "%s: cs %d above 16384 or %d tiles above 65535 in one launch", who, cs, tile_count);
+    *run = true;
+    return ND_OK;
+}
+
+// gtiles[t, c, y, x] = w * gcanvas[c, Y, X] over nd_stitch_weight_map; every element of the launch's tiles is written (0 where w = 0)
+__global__ void k_stitch_grad(const float *__restrict__ gcanvas, TileGeo g, int tile_begin, int tile_count, float *__restrict__ gtiles) {
+    const int x = blockIdx.x * blockDim.x + threadIdx.x;
+    const int y = blockIdx.y;
+    const int t = blockIdx.z;
+    if (x >= g.cs || y >= g.cs || t >= tile_count) return;
+    const int i = tile_begin + t;
+    const size_t plane = (size_t)g.W * g.H;
+    const size_t tplane = (size_t)g.cs * g.cs;
+    float v0 = 0.f, v1 = 0.f, v2 = 0.f;
+    if (i >= 0 && i < g.cols * g.rows) {
+        int Y, X;
+        const float w = nd_stitch_weight_map(g, i, y, x, &Y, &X);
+        if (w != 0.f && X >= 0 && X < g.W && Y >= 0 && Y < g.H) {
+            const float *s = gcanvas + (size_t)Y * g.W + X;
+            v0 = w * s[0];
+            v1 = w * s[plane];
+            v2 = w * s[2 * plane];
+        }
+    }
+    float *d = gtiles + (size_t)t * 3 * tplane + (size_t)y * g.cs + x;
+    d[0] = v0;
+    d[tplane] = v1;
+    d[2 * tplane] = v2;
+}
+
+extern "C" int nd_stitch_grad(const float *gcanvas, int W, int H, int cs, int ucs, int ol, int tile_begin, int tile_count,
+                              float *gtiles, void *stream) {
+    TileGeo g;
+    bool run;
+    ND_TRY(check_tile_range("nd_stitch_grad", gcanvas, gtiles, W, H, cs, ucs, ol, tile_begin, tile_count, &g, &run));
+    if (!run) return ND_OK;
+    dim3 grid((cs + 255) / 256, cs, tile_count);
+    hipLaunchKernelGGL(k_stitch_grad, grid, dim3(256), 0, (hipStream_t)stream, gcanvas, g, tile_begin, tile_count, gtiles);
+    ND_HIP(hipGetLastError());
+    return ND_OK;
+}
+
+// The tile rows (columns) k in [0, count) whose window [k * stride - pad, k * stride - pad + cs) holds a pre-image of frame
+// coordinate V under mirror_sym: the hull of the three ranges of u = -1 - V (fold over the first edge), V (direct) and
+// 2n - 1 - V (fold over the last edge).  Tiles inside the hull that hold none are skipped by the caller's per-tile test.
+__host__ __device__ static inline void preimage_tiles(const TileGeo &g, int V, int n, int count, int *lo, int *hi) {
+    const int us[3] = {-1 - V, V, 2 * n - 1 - V};
+    int l = count, h = -1;
+    for (int k = 0; k < 3; ++k) {
+        const int top = us[k] + g.pad;                              // k * stride <= top  and  k * stride > top - cs
+        if (top < 0) continue;
+        int a = ceil_div_py(top - g.cs + 1, g.stride), b = top / g.stride;
+        if (a < 0) a = 0;
+        if (b > count - 1) b = count - 1;
+        if (a > b) continue;
+        if (a < l) l = a;
+        if (b > h) h = b;
+    }
+    *lo = l;
+    *hi = h;
+}
+
+// gimg[c, Y, X] += sum of gtiles over the tile pixels of the launch that nd_tile_source_map sends to (Y, X): one thread per frame
+// pixel of the launch's footprint box.  Order of the sum: ascending tile index; within a tile ascending y * cs + x over its at most
+// 3 x 3 pre-images (fold over the first edge, direct, fold over the last edge, per axis -- ascending u is ascending tile coordinate).
+__global__ void k_tile_gather_grad(const float *__restrict__ gtiles, TileGeo g, int tile_begin, int tile_count, int bx0, int by0,
+                                   int bw, int bh, float *__restrict__ gimg) {
+    const int X = bx0 + blockIdx.x * blockDim.x + threadIdx.x;
+    if (X >= bx0 + bw || X < 0 || X >= g.W) return;
+    const size_t plane = (size_t)g.W * g.H;
+    const size_t tplane = (size_t)g.cs * g.cs;
+    const int yi_first = tile_begin / g.cols, yi_last = (tile_begin + tile_count - 1) / g.cols;
+    int xi_lo, xi_hi;
+    preimage_tiles(g, X, g.W, g.cols, &xi_lo, &xi_hi);
+    const int ux[3] = {-1 - X, X, 2 * g.W - 1 - X};
+    for (int Y = by0 + blockIdx.y; Y < by0 + bh; Y += gridDim.y) {
+        if (Y < 0 || Y >= g.H) continue;
+        int yi_lo, yi_hi;
+        preimage_tiles(g, Y, g.H, g.rows, &yi_lo, &yi_hi);
+        if (yi_lo < yi_first) yi_lo = yi_first;
+        if (yi_hi > yi_last) yi_hi = yi_last;
+        const int uy[3] = {-1 - Y, Y, 2 * g.H - 1 - Y};
+        float v0 = 0.f, v1 = 0.f, v2 = 0.f;
+        bool any = false;
+        for (int yi = yi_lo; yi <= yi_hi; ++yi) {
+            for (int xi = xi_lo; xi <= xi_hi; ++xi) {
+                const int t = yi * g.cols + xi - tile_begin;
+                if (t < 0 || t >= tile_count) continue;
+                const float *tile = gtiles + (size_t)t * 3 * tplane;
+                for (int a = 0; a < 3; ++a) {
+                    const int y = uy[a] - (yi * g.stride - g.pad);
+                    if (y < 0 || y >= g.cs) continue;
+                    for (int b = 0; b < 3; ++b) {
+                        const int x = ux[b] - (xi * g.stride - g.pad);
+                        if (x < 0 || x >= g.cs) continue;
+                        const float *s = tile + (size_t)y * g.cs + x;
+                        v0 += s[0];
+                        v1 += s[tplane];
+                        v2 += s[2 * tplane];
+                        any = true;
+                    }
+                }
+            }
+        }
+        if (any) {
+            float *d = gimg + (size_t)Y * g.W + X;
+            d[0] += v0;
+            d[plane] += v1;
+            d[2 * plane] += v2;
+        }
+    }
+}
+
+// the frame rows (columns) that tiles k0 .. k1 of an axis and their folds reach: [*lo, *hi)
+static void footprint_axis(const TileGeo &g, int k0, int k1, int n, int *lo, int *hi) {
+    int l = n, h = 0;
+    for (int k = k0; k <= k1; ++k) {
+        const int u0 = k * g.stride - g.pad, u1 = u0 + g.cs;
+        int a = u0 < 0 ? 0 : u0, b = u1 > n ? n : u1;               // direct part; the fold over the first edge, [0, -u0), lies inside it
+        if (u1 > n && 2 * n - u1 < a) a = 2 * n - u1;               // fold over the last edge: [2n - u1, n)
+        if (a < 0) a = 0;
+        if (a < l) l = a;
+        if (b > h) h = b;
+    }
+    *lo = l;
+    *hi = h;
+}
+
+extern "C" int nd_tile_gather_grad(const float *gtiles, int W, int H, int cs, int ucs, int ol, int tile_begin, int tile_count,
+                                   float *gimg, void *stream) {
+    TileGeo g;
+    bool run;
+    ND_TRY(check_tile_range("nd_tile_gather_grad", gtiles, gimg, W, H, cs, ucs, ol, tile_begin, tile_count, &g, &run));
+    if (!run) return ND_OK;
+    // footprint box: the rows of the launch's tile rows; the columns of its tiles where they lie in one tile row, else of every column
+    const int yi0 = tile_begin / g.cols, yi1 = (tile_begin + tile_count - 1) / g.cols;
+    const int xi0 = yi0 == yi1 ? tile_begin - yi0 * g.cols : 0, xi1 = yi0 == yi1 ? tile_begin + tile_count - 1 - yi0 * g.cols : g.cols - 1;
+    int bx0, bx1, by0, by1;
+    footprint_axis(g, xi0, xi1, W, &bx0, &bx1);
+    footprint_axis(g, yi0, yi1, H, &by0, &by1);
+    if (bx1 <= bx0 || by1 <= by0) return ND_OK;
+    const int bh = by1 - by0;
+    dim3 grid((bx1 - bx0 + 255) / 256, bh < 65535 ? bh : 65535);
+    hipLaunchKernelGGL(k_tile_gather_grad, grid, dim3(256), 0, (hipStream_t)stream, gtiles, g, tile_begin, tile_count, bx0, by0, bx1 - bx0,
+                       bh, gimg);
     ND_HIP(hipGetLastError());
     return ND_OK;
 }

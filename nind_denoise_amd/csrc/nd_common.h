@@ -26,6 +26,48 @@ void nd_set_error(const char *fmt, ...);
         if (r_ != 0) return r_; \
     } while (0)
 
+// ------------------------------------------------------------------ tile geometry and its two index maps (aux_kernels.hip)
+// Grid constants of OneImageDS (denoise_image.py:100-104), filled and checked by make_geo: a geometry that passes folds a tile
+// coordinate over a frame edge at most once.
+struct TileGeo {
+    int W, H, cs, ucs, ol, pad, stride, cols, rows;
+};
+__host__ __device__ static inline int ceil_div_py(int a, int b) {  // math.ceil(a / b) for b > 0, any sign of a
+    return a >= 0 ? (a + b - 1) / b : -((-a) / b);
+}
+__host__ __device__ static inline int mirror_sym(int v, int n) {  // edge pixel repeated (np.flip of the adjacent band)
+    return v < 0 ? -1 - v : (v >= n ? 2 * n - 1 - v : v);
+}
+// Gather map (OneImageDS.__getitem__, denoise_image.py:138-170): pixel (y, x) of tile i shows frame pixel (*Y, *X).  The gather
+// kernel, its adjoint and nd_tile_source are this one function.
+__host__ __device__ static inline void nd_tile_source_map(const TileGeo &g, int i, int y, int x, int *Y, int *X) {
+    const int yi = i / g.cols, xi = i - yi * g.cols;
+    *X = mirror_sym(xi * g.stride - g.pad + x, g.W);
+    *Y = mirror_sym(yi * g.stride - g.pad + y, g.H);
+}
+// Stitch map (useful crop of nd_tile_geom + make_seamless_edges, denoise_image.py:204-213, 249-267): pixel (y, x) of tile i is added
+// to canvas pixel (*Y, *X) with the returned weight -- 0 outside the useful crop (then *Y, *X name no pixel), else halved once per
+// condition of make_seamless_edges that holds: 1, 1/2 or 1/4 wherever the two strips of an axis do not meet.  The adjoint of the
+// stitch and nd_stitch_weight are this function; k_stitch_add walks the same map from the canvas pixel's side (for_each_cover).
+__host__ __device__ static inline float nd_stitch_weight_map(const TileGeo &g, int i, int y, int x, int *Y, int *X) {
+    const int yi = i / g.cols, xi = i - yi * g.cols;
+    const int ax = xi * g.stride, ay = yi * g.stride;              // usefulstart
+    const int x1pad = ax - g.pad + g.cs - g.W > 0 ? ax - g.pad + g.cs - g.W : 0;
+    const int y1pad = ay - g.pad + g.cs - g.H > 0 ? ay - g.pad + g.cs - g.H : 0;
+    const int uw = g.cs - (g.pad > x1pad ? g.pad : x1pad) - g.pad;
+    const int uh = g.cs - (g.pad > y1pad ? g.pad : y1pad) - g.pad;
+    const int dx = x - g.pad, dy = y - g.pad;
+    *X = ax + dx;
+    *Y = ay + dy;
+    if (dx < 0 || dx >= uw || dy < 0 || dy >= uh) return 0.f;
+    float f = 1.f;
+    if (ax != 0 && dx < g.ol) f *= 0.5f;
+    if (ay != 0 && dy < g.ol) f *= 0.5f;
+    if (ax + g.ucs < g.W && g.ol && dx >= uw - g.ol) f *= 0.5f;
+    if (ay + g.ucs < g.H && g.ol && dy >= uh - g.ol) f *= 0.5f;
+    return f;
+}
+
 // ------------------------------------------------------------------ deterministic sums
 // Sum of v over the 256 threads of a workgroup through `red` (256 elements of LDS): a fixed tree, the same bits on every run.
 // T: float, double, or a vector of them (added component by component).  Every thread gets the total; `red` is free again
