@@ -288,13 +288,15 @@ def test_every_conv_variant(dev):
 
 def test_maxpool(dev):
     lib = _lib.load()
-    x = rnd((2, 24, 26, 30), 4)
-    y = torch.empty((2, 24, 13, 15), dtype=torch.float32, device=dev)
     ws = torch.empty(1 << 22, dtype=torch.uint8, device=dev)
-    xd = x.to(dev)
-    _lib.check(lib.nd_maxpool2_forward(xd.data_ptr(), 2, 24, 26, 30, y.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
-    torch.cuda.synchronize()
-    assert torch.equal(y.cpu(), F.max_pool2d(x, 2))
+    # even; odd in both (the UNet executor pools odd tensors: the last row / column is dropped); the smallest odd tensor (1x1 out)
+    for seed, (b, c, h, w) in enumerate([(2, 24, 26, 30), (2, 24, 27, 31), (1, 8, 3, 2)], start=4):
+        x = rnd((b, c, h, w), seed)
+        y = torch.full((b, c, h // 2, w // 2), float("nan"), dtype=torch.float32, device=dev)
+        xd = x.to(dev)
+        _lib.check(lib.nd_maxpool2_forward(xd.data_ptr(), b, c, h, w, y.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)))
+        torch.cuda.synchronize()
+        assert torch.equal(y.cpu(), F.max_pool2d(x, 2)), (b, c, h, w)
 
 
 # ---------------------------------------------------------------------------- tiler
