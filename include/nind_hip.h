@@ -88,7 +88,7 @@ typedef enum nd_flags {
                                  nd_unet_denoise_frame: the same switch for the UNet decoder (nd_unet_useful_region)             */
 } nd_flags;
 
-int nd_version(void);   /* 116 = this header */
+int nd_version(void);   /* 117 = this header */
 const char *nd_last_error(void);
 
 /* ---------------------------------------------------------------- tile geometry (host, pure integer)
@@ -294,6 +294,42 @@ int nd_unet_useful_region(int cs, int crop, int step, int *rect);
 int nd_unet_denoise_frame(int dtype, int flags, const void *packed_dev, const float *img_chw, float *canvas_chw, int width,
                           int height, int cs, int ucs, int ol, int tile_begin, int tile_count, int batch, void *workspace,
                           size_t workspace_bytes, void *stream, nd_progress_fn progress, void *progress_ctx);
+
+/* UNet under torch.autograd in EVAL mode (BatchNorm on its running statistics; train-mode batch statistics are not implemented), fp32,
+ * any h, w >= 16, batch <= 256.  The two halves mirror nd_utnet_train_forward_hw / nd_utnet_train_backward_hw.
+ *
+ * Parameters and gradients are ONE flat float layout in nd_unet_tensor_name order, for parameters and buffers alike: conv / transpose
+ * weights and biases, BatchNorm weight, bias, running_mean, running_var (nd_unet_param_range: offset and count of tensor
+ * `tensor_idx`; nd_unet_param_count: the total).  Buffers have a slot so that the fold reads one array; their slots in `grads`
+ * are never written.
+ *
+ * nd_unet_grad_forward: folds BatchNorm and packs on the device, into `blobs` (nd_unet_grad_blob_bytes), in the forward role (the
+ * blob of nd_unet_pack_weights_device, bit for bit) and in the transposed role the data gradients read; runs every layer on the
+ * whole tile with its output kept in `workspace`; final 1x1 + Sigmoid.  y = sigmoid(outc(...)), or x - sigmoid with
+ * ND_FLAG_FIND_NOISE.  flags: ND_FLAG_NO_SPLITK and ND_FLAG_FIND_NOISE switch something; the other known bits are accepted and ignored.
+ *
+ * nd_unet_grad_backward: the whole backward from gy = d loss / d y.  grads (nullable): every parameter gradient into the flat
+ * layout -- null launches no weight-gradient, bias-sum or fold-adjoint kernel (a frozen network costs forward + data gradients);
+ * dx_nchw (nullable): d loss / d x; at least one of the two.  Same flags as the forward call.  Data gradients: the conv kernel
+ * on the transposed-role blob (a padding-1 3x3 layer on a gradient buffer with a 1-pixel zero border; a 2x2 stride-2 transpose as a
+ * 2x2 stride-2 conv over rows / columns [0, 2 h_in) only: the gradient on the F.pad fix-up lines is dropped); ReLU from the kept
+ * output (ReLU'(0) = 0); max-pool to the first maximum, added to the skip half's gradient in a fixed order; weight gradients on
+ * the matrix cores for the FOLDED weights W' = W s, b' = (b - mean) s + beta, s = gamma / sqrt(var + 1e-5), then the fold's adjoint:
+ * dW = dW' s, db = db' s, dbeta = db', dgamma = (sum dW' W + db' (b - mean)) / sqrt(var + 1e-5).  No atomics: two calls give the
+ * same bits.
+ *
+ * `workspace` (nd_unet_grad_workspace_bytes(h, w, batch), zero-filled once per geometry by nd_unet_grad_workspace_init) and `blobs`
+ * carry the forward's state to the backward call: nothing else may use them in between.  A workspace of (h, w, batch) also serves
+ * (h, w, fewer) after another nd_unet_grad_workspace_init for that count.  x, y, gy, dx: [batch,3,h,w] NCHW fp32 in HBM. */
+size_t nd_unet_param_count(void);
+int nd_unet_param_range(int tensor_idx, size_t *offset, size_t *count);
+size_t nd_unet_grad_blob_bytes(void);
+size_t nd_unet_grad_workspace_bytes(int h, int w, int batch);
+int nd_unet_grad_workspace_init(void *workspace, size_t workspace_bytes, int h, int w, int batch, void *stream);
+int nd_unet_grad_forward(int flags, const float *params, void *blobs, const float *x_nchw, float *y_nchw, int batch, int h, int w,
+                         void *workspace, size_t workspace_bytes, void *stream);
+int nd_unet_grad_backward(int flags, const float *params, float *grads, void *blobs, const float *gy_nchw, float *dx_nchw, int batch,
+                          int h, int w, void *workspace, size_t workspace_bytes, void *stream);
 
 /* FLOP per tile by the reference's own accounting, for roofline reports. */
 double nd_utnet_flops(int funit, int cs);

@@ -76,6 +76,14 @@ _SIGNATURES = {
     "nd_unet_step_name": (c_char_p, [c_int]),
     "nd_unet_useful_region": (c_int, [c_int, c_int, c_int, POINTER(c_int)]),
     "nd_unet_denoise_frame": (c_int, [c_int, c_int] + [c_void_p] * 3 + [c_int] * 8 + [c_void_p, c_size_t, c_void_p, PROGRESS_FN, c_void_p]),
+    "nd_unet_param_count": (c_size_t, []),
+    "nd_unet_param_range": (c_int, [c_int, POINTER(c_size_t), POINTER(c_size_t)]),
+    "nd_unet_grad_blob_bytes": (c_size_t, []),
+    "nd_unet_grad_workspace_bytes": (c_size_t, [c_int] * 3),
+    "nd_unet_grad_workspace_init": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
+    "nd_unet_grad_forward": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "nd_unet_grad_backward": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t,
+                                      c_void_p]),
     "nd_utnet_flops": (c_double, [c_int, c_int]),
     "nd_utnet_profile_stack": (c_int, [c_int] * 4 + [c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_int]),
     "nd_utnet_step_name": (c_char_p, [c_int]),

@@ -330,3 +330,19 @@ struct SpliceMap {
 int nd_launch_splice(const QpBuf &src, int src_p0, const QpBuf &dst, int dst_p0, int planes, int tile_begin, int tile_count, int cols,
                      int row0, const SpliceMap &m, int r0, int r1, int c0, int c1, hipStream_t s, int band_rows = 0,
                      long slot_elems = 0, int dst_img0 = 0);
+
+// ------------------------------------------------------------------ gradient kernels shared by the two networks' backward passes
+// (wgrad.hip, train.hip, utnet_train.hip): no atomics, fixed summation order
+// dst (its own grid) = zeros except dst[c][img][y + oy][x + ox] = src[c][img][y * ss + sy][x * ss + sx] for y < h, x < w (interior coordinates)
+int nd_launch_repitch(const QpBuf &src, int src_plane0, int planes, int ss, int sy, int sx, const QpBuf &dst, int oy, int ox, int h, int w,
+                      hipStream_t s);
+size_t nd_wgrad_partial_floats(int taps, int M, int N, long K, int *ksplit_out, int *cps_out);
+int nd_launch_wgrad(const QpBuf &A, int a_plane0, int M, const QpBuf &Bq, int b_plane0, int N, int taps, int taps_total, int tap0,
+                    float *partial, size_t partial_floats, float *dw, hipStream_t s);
+// out[c] = sum over the interior of planes [plane0, ...) of src; scratch: 4 * ceil(C/4) * B floats
+int nd_launch_channel_sum(const QpBuf &src, int plane0, int C, float *out, float *scratch, hipStream_t s);
+int nd_launch_maxpool_bwd_add(const QpBuf &gpool, const QpBuf &fwd, int fwd_plane0, const QpBuf &gfine, int g_plane0, int planes,
+                              hipStream_t s);
+int nd_launch_final_wgrad(const float *gy, int H, int W, const QpBuf &act, int cin, int crop, float *red, float *dw, float *db,
+                          hipStream_t s);
+int nd_launch_final_bwd_data(const float *gy, int H, int W, const float *w, int cin, int crop, const QpBuf &g, hipStream_t s);

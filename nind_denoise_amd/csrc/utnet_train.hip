@@ -561,6 +561,44 @@ static int train_forward(TrainCtx &c, const float *params, const float *x, float
     return ND_OK;
 }
 
+// max-pool backward: planes [g_plane0, +planes) of gfine += the gradient of the pooled tensor gpool (planes from 0) at the argmax of
+// each 2x2 window of fwd (planes from fwd_plane0)
+int nd_launch_maxpool_bwd_add(const QpBuf &gpool, const QpBuf &fwd, int fwd_plane0, const QpBuf &gfine, int g_plane0, int planes,
+                              hipStream_t s) {
+    const int Ho = gpool.Hb - 2 * gpool.pad, Wo = gpool.Wb - 2 * gpool.pad, B = gpool.B;
+    if (fwd.Hb - 2 * fwd.pad < 2 * Ho || fwd.Wb - 2 * fwd.pad < 2 * Wo || gfine.Hb - 2 * gfine.pad < 2 * Ho || gfine.Wb - 2 * gfine.pad < 2 * Wo ||
+        fwd.B != B || gfine.B != B || gpool.planes < planes || fwd.planes < fwd_plane0 + planes || gfine.planes < g_plane0 + planes)
+        ND_FAIL(ND_EINVAL, "maxpool backward: buffers do not fit %d planes of %d x %d windows", planes, Ho, Wo);
+    dim3 grid((Wo + 127) / 128, Ho, B * planes);
+    hipLaunchKernelGGL(k_maxpool_bwd_add, grid, dim3(128), 0, s, (const f32x4 *)gpool.base, gpool.np(), gpool.Hb, gpool.Wb, gpool.pad,
+                       (const f32x4 *)fwd.base + (long)fwd_plane0 * fwd.np(), fwd.np(), fwd.Hb, fwd.Wb, fwd.pad,
+                       (f32x4 *)gfine.base + (long)g_plane0 * gfine.np(), gfine.np(), gfine.Hb, gfine.Wb, gfine.pad, Ho, Wo, B);
+    ND_HIP(hipGetLastError());
+    return ND_OK;
+}
+// final Conv2d(cin, 3, 1) behind a crop of `crop` pixels: weight [3][cin] and bias [3] gradients from gy [B,3,H,W] and the layer's
+// input `act` (H + 2 crop rows); red: 5 * 3 * ceil(cin/4) * B floats of scratch
+int nd_launch_final_wgrad(const float *gy, int H, int W, const QpBuf &act, int cin, int crop, float *red, float *dw, float *db,
+                          hipStream_t s) {
+    const int planes = (cin + 3) / 4, B = act.B;
+    if (act.Hb != H + 2 * crop || act.Wb != W + 2 * crop || act.planes < planes) ND_FAIL(ND_EINVAL, "final 1x1 weight gradient: bad input geometry");
+    f32x4 *pw = (f32x4 *)red;
+    float *pb = red + (size_t)4 * 3 * planes * B;
+    hipLaunchKernelGGL(k_final_wgrad1, dim3(3, planes, B), dim3(256), 0, s, gy, H, W, (const f32x4 *)act.base, act.np(), act.Hb, act.Wb,
+                       crop, pw, pb);
+    hipLaunchKernelGGL(k_final_wgrad2, dim3(3, planes), dim3(64), 0, s, (const f32x4 *)pw, (const float *)pb, planes, B, cin, dw, db);
+    ND_HIP(hipGetLastError());
+    return ND_OK;
+}
+// ... and its data gradient into every element of g (ceil(cin/4) planes of H + 2 crop rows: zero outside the H x W centre)
+int nd_launch_final_bwd_data(const float *gy, int H, int W, const float *w, int cin, int crop, const QpBuf &g, hipStream_t s) {
+    if (g.Hb != H + 2 * crop || g.Wb != W + 2 * crop || g.planes < (cin + 3) / 4) ND_FAIL(ND_EINVAL, "final 1x1 data gradient: bad destination geometry");
+    dim3 grid((g.Wb + 127) / 128, g.Hb, g.B * ((cin + 3) / 4));
+    hipLaunchKernelGGL(k_final_bwd_data, grid, dim3(128), 0, s, gy, H, W, w, cin, crop, (f32x4 *)g.base, g.np(), g.Hb, g.Wb, g.B);
+    ND_HIP(hipGetLastError());
+    return ND_OK;
+}
+
 int nd_launch_input_grad(const QpBuf &g1, const float *w0, int H, int W, float *dx, hipStream_t s) {
     if (g1.dt != ND_F32 || g1.pad < 2 || g1.Hb != H + 2 + 2 * g1.pad || g1.Wb != W + 2 + 2 * g1.pad)
         ND_FAIL(ND_EINVAL, "input gradient: bad source geometry");
@@ -585,33 +623,15 @@ static int train_backward(TrainCtx &c, const float *params, float *grads, const 
     const float *fw = fblob + bl.off[kNumLayers - 1];
     // ---- 4. backward
     // final 1x1
-    {
-        const QpBuf &a = t.fwd.buf[T4B], &g = t.g[T4B];
-        f32x4 *pw = (f32x4 *)t.red;
-        float *pb = t.red + (size_t)4 * 3 * (f / 4) * B;
-        if (grads) {
-            hipLaunchKernelGGL(k_final_wgrad1, dim3(3, f / 4, B), dim3(256), 0, s, gy, H, W, (const f32x4 *)a.base,
-                               a.np(), a.Hb, a.Wb, 2, pw, pb);
-            hipLaunchKernelGGL(k_final_wgrad2, dim3(3, f / 4), dim3(64), 0, s, (const f32x4 *)pw, (const float *)pb, f / 4, B, f,
-                               G("tconvs4.4.weight"), G("tconvs4.4.bias"));
-        }
-        dim3 grid((g.Wb + 127) / 128, g.Hb, B * (f / 4));
-        hipLaunchKernelGGL(k_final_bwd_data, grid, dim3(128), 0, s, gy, H, W, fw, f, 2, (f32x4 *)g.base, g.np(), g.Hb,
-                           g.Wb, B);
-        ND_HIP(hipGetLastError());
-    }
+    if (grads)
+        ND_TRY(nd_launch_final_wgrad(gy, H, W, t.fwd.buf[T4B], f, 2, t.red, G("tconvs4.4.weight"), G("tconvs4.4.bias"), s));
+    ND_TRY(nd_launch_final_bwd_data(gy, H, W, fw, f, 2, t.g[T4B], s));
     for (int si = kNumSteps - 1; si >= 0; --si) {
         const Step &st = kSteps[si];
         if (st.layer < 0) {
             // pool: the skip half of the concat buffer was pooled into P; route g(P) back and ADD it to g(skip)
             const int planes = st.dst_plane0_mul * f / 4, plane0 = planes;
-            const QpBuf &gp = t.g[st.dst], &fw_ = t.fwd.buf[st.src], &gc = t.g[st.src];
-            const int Ho = gp.Hb - 2 * gp.pad, Wo = gp.Wb - 2 * gp.pad;
-            dim3 grid((Wo + 127) / 128, Ho, B * planes);
-            hipLaunchKernelGGL(k_maxpool_bwd_add, grid, dim3(128), 0, s, (const f32x4 *)gp.base, gp.np(), gp.Hb, gp.Wb, gp.pad,
-                               (const f32x4 *)fw_.base + (long)plane0 * fw_.np(), fw_.np(), fw_.Hb, fw_.Wb, fw_.pad,
-                               (f32x4 *)gc.base + (long)plane0 * gc.np(), gc.np(), gc.Hb, gc.Wb, gc.pad, Ho, Wo, B);
-            ND_HIP(hipGetLastError());
+            ND_TRY(nd_launch_maxpool_bwd_add(t.g[st.dst], t.fwd.buf[st.src], plane0, t.g[st.src], plane0, planes, s));
             continue;
         }
         const LayerSpec &l = kLayers[st.layer];

@@ -22,6 +22,9 @@ The recompute uses the module's one training state.  Like every forward under au
 counter: a crop graph built by ``model(x)`` before a frame backward of the same module is stale afterwards, and its
 backward raises.  A frame graph never goes stale (it holds no activations), so several may be in flight.
 
+``UNet`` in eval mode gets the same treatment (``nd_unet_grad_forward`` / ``nd_unet_grad_backward``: BatchNorm on its running
+statistics, every activation kept, ``find_noise`` honoured); a train-mode ``UNet`` raises ``RuntimeError`` as its forward does.
+
 There is no CPU path: a CPU tensor raises.
 """
 import torch
@@ -180,6 +183,67 @@ class _UtNetFrame(torch.autograd.Function):
         return (None, None, None, gimg) + tuple(grads)
 
 
+# ---------------------------------------------------------------------------- UNet (eval mode): the same recompute
+
+class _UNetFrame(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, names, geom, img, *params):
+        cs, ucs, ol, batch, begin, end = geom
+        ctx.model, ctx.names, ctx.geom = model, names, geom
+        ctx.save_for_backward(img, *params)
+        return pipeline.denoise_frame(model, img, cs, ucs, ol, batch=batch, tile_range=(begin, end))
+
+    @staticmethod
+    def backward(ctx, gcanvas):
+        model, names = ctx.model, ctx.names
+        cs, ucs, ol, batch, begin, end = ctx.geom
+        img, *params = ctx.saved_tensors
+        want_img, want_p = ctx.needs_input_grad[3], ctx.needs_input_grad[4:]
+        dev = img.device
+        height, width = img.size(1), img.size(2)
+        lib = _lib.load()
+        st = model._grad_state(dev)
+        st.load(dict(zip(names, params)))
+        st.load(dict(model.named_buffers()))
+        gcanvas = gcanvas.to(torch.float32).contiguous()
+        gimg = torch.zeros_like(img) if want_img else None
+        acc = torch.zeros_like(st.grads) if any(want_p) else None
+        batch = max(1, min(batch, end - begin))
+        x = torch.empty((batch, 3, cs, cs), dtype=torch.float32, device=dev)
+        y, gt = torch.empty_like(x), torch.empty_like(x)
+        dx = torch.empty_like(x) if want_img else None
+        flags = model.grad_flags
+        with torch.cuda.device(dev):
+            s = _lib.stream_ptr(dev)
+            ws = st.workspace(cs, cs, batch)
+            laid_out = batch                      # the launch size the workspace's zero borders are laid out for
+            for t0 in range(begin, end, batch):
+                cnt = min(batch, end - t0)
+                if cnt != laid_out:               # the partial last launch: the same buffer, laid out for fewer tiles
+                    _lib.check(lib.nd_unet_grad_workspace_init(ws.data_ptr(), ws.numel(), cs, cs, cnt, s), "nd_unet_grad_workspace_init")
+                    laid_out = cnt
+                _lib.check(lib.nd_tile_gather(img.data_ptr(), width, height, cs, ucs, ol, t0, cnt, x.data_ptr(), s), "nd_tile_gather")
+                _lib.check(lib.nd_unet_grad_forward(flags, st.flat.data_ptr(), st.blobs.data_ptr(), x.data_ptr(), y.data_ptr(), cnt, cs, cs,
+                                                    ws.data_ptr(), ws.numel(), s), "nd_unet_grad_forward")
+                st.generation += 1                # the workspace now holds this launch: an older crop graph is stale
+                _lib.check(lib.nd_stitch_grad(gcanvas.data_ptr(), width, height, cs, ucs, ol, t0, cnt, gt.data_ptr(), s), "nd_stitch_grad")
+                _lib.check(lib.nd_unet_grad_backward(flags, st.flat.data_ptr(), st.grads.data_ptr() if acc is not None else None,
+                                                     st.blobs.data_ptr(), gt.data_ptr(), dx.data_ptr() if want_img else None, cnt, cs, cs,
+                                                     ws.data_ptr(), ws.numel(), s), "nd_unet_grad_backward")
+                if acc is not None:
+                    acc += st.grads
+                if want_img:
+                    _lib.check(lib.nd_tile_gather_grad(dx.data_ptr(), width, height, cs, ucs, ol, t0, cnt, gimg.data_ptr(), s),
+                               "nd_tile_gather_grad")
+            if laid_out != batch:                 # leave the state's workspace as its key says
+                _lib.check(lib.nd_unet_grad_workspace_init(ws.data_ptr(), ws.numel(), cs, cs, batch, s), "nd_unet_grad_workspace_init")
+        grads = []
+        for n, p, want in zip(names, params, want_p):
+            off, cnt = st.ranges[n]
+            grads.append(acc[off:off + cnt].view(p.shape).clone() if want else None)
+        return (None, None, None, gimg) + tuple(grads)
+
+
 def denoise_frame(model, img, cs, ucs, ol, batch=16, tile_range=None):
     """pipeline.denoise_frame with a graph behind its canvas.  img: [3,H,W] float32 on the GPU; returns the stitched [3,H,W]
     canvas.  When grad mode is on and img or a parameter of the model requires a gradient the canvas has a grad_fn (in
@@ -188,14 +252,14 @@ def denoise_frame(model, img, cs, ucs, ol, batch=16, tile_range=None):
     UtNet (fp32; another compute_dtype raises NotImplementedError, as UtNet.forward under autograd does): the fused inference
     loop forward, a launch-by-launch recompute backward -- memory is one training workspace of (cs, cs, batch), see the module
     docstring (also for the generation counter).  Any other torch-callable model: gather_tiles -> model -> stitch_tiles per
-    launch, whose graphs torch keeps.  UNet has no backward and raises NotImplementedError.
+    launch, whose graphs torch keeps.  UNet (eval mode; train mode raises RuntimeError): as UtNet, on one gradient workspace.
     tile_range=(begin, end): only those tiles, as in pipeline.denoise_frame."""
     _check_frame(img, "the frame")
     params = [(n, p) for n, p in model.named_parameters()] if isinstance(model, torch.nn.Module) else []
     if not (torch.is_grad_enabled() and (img.requires_grad or any(p.requires_grad for _, p in params))):
         return pipeline.denoise_frame(model, img, cs, ucs, ol, batch=batch, tile_range=tile_range)
-    if isinstance(model, UNet):
-        raise NotImplementedError("frame_grad.denoise_frame: UNet has no backward on the HIP path")
+    if isinstance(model, UNet) and model.training:
+        raise RuntimeError("nind_denoise_amd.UNet implements eval mode (BatchNorm running statistics) only; call .eval()")
     img = img.to(torch.float32).contiguous()
     total = pipeline.tile_count(img.size(2), img.size(1), cs, ucs, ol)
     begin, end = (0, total) if tile_range is None else tile_range
@@ -206,6 +270,8 @@ def denoise_frame(model, img, cs, ucs, ol, batch=16, tile_range=None):
         if model.compute_dtype != "f32":
             raise NotImplementedError("UtNet under autograd runs in fp32 (the training step's arithmetic)")
         return _UtNetFrame.apply(model, tuple(n for n, _ in params), (cs, ucs, ol, batch, begin, end), img, *[p for _, p in params])
+    if isinstance(model, UNet):
+        return _UNetFrame.apply(model, tuple(n for n, _ in params), (cs, ucs, ol, batch, begin, end), img, *[p for _, p in params])
     canvas = torch.zeros_like(img)
     for t0 in range(begin, end, batch):
         cnt = min(batch, end - t0)
