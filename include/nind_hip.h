@@ -88,7 +88,7 @@ typedef enum nd_flags {
                                  nd_unet_denoise_frame: the same switch for the UNet decoder (nd_unet_useful_region)             */
 } nd_flags;
 
-int nd_version(void);   /* 117 = this header */
+int nd_version(void);   /* 118 = this header */
 const char *nd_last_error(void);
 
 /* ---------------------------------------------------------------- tile geometry (host, pure integer)
@@ -330,6 +330,38 @@ int nd_unet_grad_forward(int flags, const float *params, void *blobs, const floa
                          void *workspace, size_t workspace_bytes, void *stream);
 int nd_unet_grad_backward(int flags, const float *params, float *grads, void *blobs, const float *gy_nchw, float *dx_nchw, int batch,
                           int h, int w, void *workspace, size_t workspace_bytes, void *stream);
+
+/* UNet TRAINING step halves: BatchNorm on the statistics of the batch (nn.BatchNorm2d in train() mode), fp32, any h, w >= 16,
+ * batch <= 256 and at least 2 values per channel in every BatchNorm layer: batch * (h / 16) * (w / 16) >= 2 (torch: "Expected more
+ * than 1 value per channel when training"); else ND_EINVAL, and nd_unet_train_workspace_bytes returns 0.  params / grads: the flat
+ * layout of nd_unet_param_range.  flags: those of nd_unet_grad_forward.
+ *
+ * nd_unet_train_forward: packs the RAW weights and biases (no fold) into `blobs` (nd_unet_train_blob_bytes) in both roles.  Each of
+ * the 18 Conv3 + BatchNorm + ReLU layers: the convolution without activation into a pre-norm buffer z that is KEPT for the backward
+ * (this about doubles the activation part of the workspace against nd_unet_grad_workspace_bytes); per channel over the N = batch *
+ * H * W interior pixels of the level: mu = mean z, var = E[(z - mu)^2] (biased), inv = 1 / sqrt(var + 1e-5), both kept;
+ * a = ReLU(gamma (z - mu) inv + beta) into the layer's activation buffer; and the running statistics IN `params` move as torch's:
+ * rm <- (1 - momentum) rm + momentum mu, rv <- (1 - momentum) rv + momentum var N / (N - 1).  momentum in [0, 1].  Transposes,
+ * pools, concat and F.pad fix-up lines, the 1x1 head and find_noise: as nd_unet_grad_forward.
+ *
+ * nd_unet_train_backward: from gy = d loss / d y.  For a BatchNorm layer with g_a = the gradient of its post-ReLU output, m = [a > 0]
+ * and xhat = (z - mu) inv:  dbeta = sum g_a m,  dgamma = sum g_a m xhat,  g_z = gamma inv (g_a m - dbeta / N - xhat dgamma / N),
+ * then the weight gradient and the data gradient of the convolution from g_z with the raw weights.  grads (nullable) receives every
+ * parameter gradient; dx_nchw (nullable) d loss / d x; at least one of the two.  The bias gradient of the 18 convolutions that feed a
+ * BatchNorm is written as EXACT ZEROS: BatchNorm removes the channel mean, so that is the exact value (torch writes the rounding
+ * noise of sum g_z, about 1e-9, which Adam's g / (|g| + eps) would turn into full steps).  The slots of running statistics in
+ * `grads` are never written.
+ *
+ * The statistics and the two backward sums are accumulated in double, in a fixed two-stage order (one partial per workgroup, then
+ * one workgroup per 4 channels); no atomics anywhere: two calls give the same bits.  `workspace` (zero-filled once per geometry by
+ * nd_unet_train_workspace_init) and `blobs` carry the forward's state to the backward call. */
+size_t nd_unet_train_blob_bytes(void);
+size_t nd_unet_train_workspace_bytes(int h, int w, int batch);
+int nd_unet_train_workspace_init(void *workspace, size_t workspace_bytes, int h, int w, int batch, void *stream);
+int nd_unet_train_forward(int flags, float *params, void *blobs, const float *x_nchw, float *y_nchw, int batch, int h, int w,
+                          float momentum, void *workspace, size_t workspace_bytes, void *stream);
+int nd_unet_train_backward(int flags, const float *params, float *grads, void *blobs, const float *gy_nchw, float *dx_nchw, int batch,
+                           int h, int w, void *workspace, size_t workspace_bytes, void *stream);
 
 /* FLOP per tile by the reference's own accounting, for roofline reports. */
 double nd_utnet_flops(int funit, int cs);

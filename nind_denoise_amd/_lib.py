@@ -82,6 +82,13 @@ _SIGNATURES = {
     "nd_unet_grad_workspace_bytes": (c_size_t, [c_int] * 3),
     "nd_unet_grad_workspace_init": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
     "nd_unet_grad_forward": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "nd_unet_train_blob_bytes": (c_size_t, []),
+    "nd_unet_train_workspace_bytes": (c_size_t, [c_int] * 3),
+    "nd_unet_train_workspace_init": (c_int, [c_void_p, c_size_t, c_int, c_int, c_int, c_void_p]),
+    "nd_unet_train_forward": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_size_t,
+                                      c_void_p]),
+    "nd_unet_train_backward": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t,
+                                       c_void_p]),
     "nd_unet_grad_backward": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t,
                                       c_void_p]),
     "nd_utnet_flops": (c_double, [c_int, c_int]),

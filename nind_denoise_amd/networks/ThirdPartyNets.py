@@ -5,7 +5,8 @@
 The torch layers below are parameter containers only; ``forward`` never calls them.  No CPU path.
 
 Eval mode is differentiable: an input that requires a gradient gets one, and so do the parameters that require one (fine-tuning
-with frozen BatchNorm statistics) -- ``nd_unet_grad_forward`` / ``nd_unet_grad_backward``.  Train mode (batch statistics) raises.
+with frozen BatchNorm statistics) -- ``nd_unet_grad_forward`` / ``nd_unet_grad_backward``.  Train mode (batch statistics) raises
+here; the training step on batch statistics is ``nind_denoise_amd.train.UNetTrainer``, which drives this module's tensors.
 """
 import ctypes
 

@@ -12,6 +12,8 @@ for batches larger than one (nn_common.py:170-177, 216), so there is no other re
 The module's parameters are views into ONE flat fp32 buffer in state-dict order; gradients come back in a second flat
 buffer with the same layout, so the optimizer is one kernel and the data-parallel reduction runs on nine contiguous level
 buckets of that buffer, each all-reduced as soon as the backward pass has finished it (dist.BucketedGradientAverager).
+
+UNetTrainer, below, is the same surface for UNet: BatchNorm on the statistics of the batch (csrc/unet_train.hip), one GPU.
 """
 import ctypes
 
@@ -135,6 +137,197 @@ class UtNetTrainer:
     def grad_of(self, name):
         off, cnt = self.ranges[name]
         return self.grads[off:off + cnt].view_as(dict(self.model.named_parameters())[name])
+
+    def update_learning_rate(self, lr_decay):
+        self.lr *= lr_decay
+        return self.lr
+
+
+def unet_ranges():
+    """{tensor name: (offset, count)} of the flat UNet layout (nd_unet_param_range): parameters and running statistics."""
+    lib = _lib.load()
+    ranges = {}
+    for i in range(lib.nd_unet_num_tensors()):
+        off, cnt = ctypes.c_size_t(), ctypes.c_size_t()
+        _lib.check(lib.nd_unet_param_range(i, off, cnt))
+        ranges[lib.nd_unet_tensor_name(i).decode()] = (off.value, cnt.value)
+    return ranges
+
+
+def unet_flatten(model, flat, ranges):
+    """Make every parameter AND every BatchNorm running statistic of `model` a view of `flat` (fp32, on the model's device) at its
+    range, keeping the values.  The state-dict keeps its keys and shapes; num_batches_tracked has no slot and stays its own tensor."""
+    seen = set()
+    with torch.no_grad():
+        for prefix, mod in model.named_modules():
+            for kind, table in (("p", mod._parameters), ("b", mod._buffers)):
+                for key, t in table.items():
+                    name = f"{prefix}.{key}" if prefix else key
+                    if t is None or name not in ranges:
+                        continue
+                    off, cnt = ranges[name]
+                    assert t.numel() == cnt, (name, t.numel(), cnt)
+                    view = flat[off:off + cnt].view(t.shape)
+                    view.copy_(t)
+                    if kind == "p":
+                        t.data = view
+                    else:
+                        table[key] = view
+                    seen.add(name)
+    missing = set(ranges) - seen
+    assert not missing, sorted(missing)
+
+
+class UNetTrainer:
+    """UNet training step on the GPU, with the surface of UtNetTrainer: BatchNorm on the statistics of the batch
+    (nd_unet_train_forward / nd_unet_train_backward), the loss of nd_criteria_grad, Adam(amsgrad) in nd_adam_step.
+
+    The module's parameters and its BatchNorm running statistics become views of ONE flat fp32 buffer (nd_unet_param_range).  The
+    forward moves the running statistics in that buffer as torch's train-mode BatchNorm does (momentum of the module's BatchNorm
+    layers); `num_batches_tracked` advances on the host side of the same call.
+
+    One divergence from torch, on purpose: the bias of a convolution that feeds a BatchNorm gets a gradient of exactly 0 (its exact
+    value: BatchNorm removes the channel mean), where torch leaves the rounding noise of a sum that cancels -- which Adam's
+    g / (|g| + eps) would turn into full steps.  Those 18 biases therefore never move.
+
+    The module itself is unchanged: `model.train()(x)` still raises, `model.eval()(x)` runs on the trained parameters and running
+    statistics (the trainer drops the module's packed inference blob whenever it has written the flat buffer)."""
+
+    def __init__(self, model, lr=1e-4, beta1=0.75, beta2=0.999, eps=1e-8, amsgrad=True,
+                 weights=None, device=None, process_group=None, loss_cs=None):
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self.device.type != "cuda":
+            raise RuntimeError("UNetTrainer needs a GPU (no CPU fallback)")
+        if process_group is not None:
+            raise NotImplementedError("UNetTrainer: data-parallel UNet training is not available (the bucketed gradient averager "
+                                      "is laid out for UtNet)")
+        self.weights = {"L1": 0.0, "MSE": 1.0} if weights is None else dict(weights)
+        unknown = set(k for k, v in self.weights.items() if v) - {"L1", "MSE", "SSIM", "MSSSIM"}
+        if unknown:
+            raise NotImplementedError(f"loss terms {sorted(unknown)} are not available (generator losses: L1, MSE, SSIM, MSSSIM)")
+        self.model = model.to(self.device)
+        self.lib = _lib.load()
+        self.lr, self.betas, self.eps, self.amsgrad = lr, (beta1, beta2), eps, amsgrad
+        self.group = None
+        self.loss_cs = loss_cs
+        bns = [m for m in self.model.modules() if isinstance(m, torch.nn.BatchNorm2d)]
+        momenta = {m.momentum for m in bns}
+        if len(momenta) != 1 or None in momenta:
+            raise NotImplementedError(f"UNetTrainer: one numeric BatchNorm momentum for the whole network, got {sorted(map(str, momenta))}")
+        self.momentum = float(momenta.pop())
+        self._tracked = [m.num_batches_tracked for m in bns]
+        self.ranges = unet_ranges()
+        self.flat = torch.zeros(self.lib.nd_unet_param_count(), dtype=torch.float32, device=self.device)
+        unet_flatten(self.model, self.flat, self.ranges)
+        self.grads = torch.zeros_like(self.flat)      # the slots of running statistics are never written: they stay 0
+        self.m = torch.zeros_like(self.flat)
+        self.v = torch.zeros_like(self.flat)
+        self.vmax = torch.zeros_like(self.flat)
+        self.steps = 0
+        self.blobs = torch.empty(self.lib.nd_unet_train_blob_bytes(), dtype=torch.uint8, device=self.device)
+        self._ws = {}
+        self._loss_ws = None
+        self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+
+    @property
+    def flags(self):
+        return self.model.grad_flags
+
+    def workspace(self, h, w, batch):
+        """Training workspace for [batch,3,h,w] crops (zeroed once, then cached; another shape replaces it)."""
+        key = (h, w, batch)
+        ws = self._ws.get(key)
+        if ws is None:
+            nbytes = self.lib.nd_unet_train_workspace_bytes(h, w, batch)
+            if nbytes == 0:
+                _lib.check(self.lib.nd_unet_train_workspace_init(None, 0, h, w, batch, None), "UNet training")
+            self._ws.clear()
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            _lib.check(self.lib.nd_unet_train_workspace_init(ws.data_ptr(), nbytes, h, w, batch, _lib.stream_ptr(self.device)),
+                       "nd_unet_train_workspace_init")
+            self._ws[key] = ws
+        return ws
+
+    def _loss_workspace(self, batch, h, w):
+        nbytes = self.lib.nd_criteria_grad_workspace_bytes(batch, h, w, int(self.loss_cs or 0))
+        if nbytes == 0:      # let the library name what is wrong with the shape
+            _lib.check(self.lib.nd_criteria_grad(None, None, batch, h, w, int(self.loss_cs or 0), 0.0, 0.0, 0.0, 0.0, None, None, None, 0,
+                                                 None), "nd_criteria_grad")
+        if self._loss_ws is None or self._loss_ws.numel() < nbytes:
+            self._loss_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._loss_ws
+
+    def forward(self, noisy):
+        """The train-mode forward alone: output [B,3,H,W]; running statistics and num_batches_tracked advance."""
+        noisy = noisy.to(self.device, torch.float32).contiguous()
+        if noisy.dim() != 4 or noisy.size(1) != 3:
+            raise ValueError(f"expected a [B,3,H,W] batch, got {tuple(noisy.shape)}")
+        batch, h, w = noisy.size(0), noisy.size(2), noisy.size(3)
+        y = torch.empty_like(noisy)
+        with torch.cuda.device(self.device):
+            ws = self.workspace(h, w, batch)
+            _lib.check(self.lib.nd_unet_train_forward(self.flags, self.flat.data_ptr(), self.blobs.data_ptr(), noisy.data_ptr(),
+                                                      y.data_ptr(), batch, h, w, self.momentum, ws.data_ptr(), ws.numel(),
+                                                      _lib.stream_ptr(self.device)), "nd_unet_train_forward")
+            torch._foreach_add_(self._tracked, 1)
+        # the running statistics were rewritten through raw pointers (neither data_ptr nor torch's version counters moved): the
+        # inference blob the module cached is stale
+        self.model._packed = None
+        return y
+
+    def backward(self, gy, want_dx=False):
+        """The backward of the last forward from gy = d loss / d output; fills self.grads.  Returns d loss / d input if asked."""
+        gy = gy.to(self.device, torch.float32).contiguous()
+        batch, h, w = gy.size(0), gy.size(2), gy.size(3)
+        ws = self._ws.get((h, w, batch))
+        if ws is None:
+            raise RuntimeError("UNetTrainer.backward: no forward of this shape came before")
+        dx = torch.empty_like(gy) if want_dx else None
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.nd_unet_train_backward(self.flags, self.flat.data_ptr(), self.grads.data_ptr(), self.blobs.data_ptr(),
+                                                       gy.data_ptr(), dx.data_ptr() if want_dx else None, batch, h, w, ws.data_ptr(),
+                                                       ws.numel(), _lib.stream_ptr(self.device)), "nd_unet_train_backward")
+        return dx
+
+    def forward_backward(self, noisy, clean):
+        """Forward + loss + backward, enqueued on one stream with no read from the GPU in between; fills self.grads.  Returns
+        (output, loss tensor)."""
+        noisy = noisy.to(self.device, torch.float32).contiguous()
+        clean = clean.to(self.device, torch.float32).contiguous()
+        if noisy.shape != clean.shape or noisy.dim() != 4 or noisy.size(1) != 3:
+            raise ValueError(f"expected two [B,3,H,W] batches, got {tuple(noisy.shape)} and {tuple(clean.shape)}")
+        batch, h, w = noisy.size(0), noisy.size(2), noisy.size(3)
+        with torch.cuda.device(self.device):
+            lws = self._loss_workspace(batch, h, w)       # refuses a bad loss window before anything runs
+            y = self.forward(noisy)
+            gy = torch.empty_like(y)
+            # (without find_noise the output is a sigmoid: the criteria's clip to [0, 1] is inert)
+            _lib.check(self.lib.nd_criteria_grad(y.data_ptr(), clean.data_ptr(), batch, h, w, int(self.loss_cs or 0),
+                                                 *[float(self.weights.get(k) or 0.0) for k in ("L1", "MSE", "SSIM", "MSSSIM")],
+                                                 self.loss.data_ptr(), gy.data_ptr(), lws.data_ptr(), lws.numel(),
+                                                 _lib.stream_ptr(self.device)), "nd_criteria_grad")
+            self.backward(gy)
+        return y, self.loss
+
+    def optimizer_step(self):
+        self.steps += 1
+        with torch.cuda.device(self.device):
+            # running statistics: gradient and moments 0 -> an update of exactly 0, the slots keep their bits
+            _lib.check(self.lib.nd_adam_step(self.flat.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                                             self.vmax.data_ptr(), self.flat.numel(), self.lr, self.betas[0], self.betas[1],
+                                             self.eps, self.steps, int(self.amsgrad), _lib.stream_ptr(self.device)),
+                       "nd_adam_step")
+        self.model._packed = None      # written through raw pointers: see forward
+
+    def learn(self, noisy, clean):
+        """One generator update; returns the loss as a float tensor."""
+        _, loss = self.forward_backward(noisy, clean)
+        self.optimizer_step()
+        return loss
+
+    def grad_of(self, name):
+        off, cnt = self.ranges[name]
+        return self.grads[off:off + cnt].view_as(self.model.state_dict()[name])
 
     def update_learning_rate(self, lr_decay):
         self.lr *= lr_decay
