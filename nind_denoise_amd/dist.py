@@ -371,7 +371,8 @@ class BucketedGradientAverager:
     compute stream as soon as the bucket is final (nd_utnet_train_step_act_hw / nd_utnet_train_backward_hw); `reduce()` all-reduces
     bucket k on a side stream behind event k, i.e. under the backward of the shallower levels, and the compute stream only waits
     for the last (smallest) buckets.  On a gloo group (tests, the one-GPU rehearsal) the buckets are reduced one by one through
-    host memory after the step; with CPU tensors there are no events at all.  No-op without an initialised process group."""
+    host memory after the step; with CPU tensors there are no events at all.  No-op without an initialised process group, which reduce() looks for at every call:
+    the averager may be built before the group."""
 
     def __init__(self, funit, flat, group=None):
         import ctypes
@@ -383,8 +384,7 @@ class BucketedGradientAverager:
         _lib.check(min(0, lib.nd_utnet_grad_buckets(funit, off, cnt, n)), "nd_utnet_grad_buckets")
         self.buckets = [(int(off[k]), int(cnt[k])) for k in range(n)]
         assert sum(c for _, c in self.buckets) == flat.numel(), "gradient buckets do not tile the flat buffer"
-        self.flat, self.group = flat, group
-        self.active = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+        self.flat, self.group, self._forced = flat, group, None
         self.events, self.event_ptrs, self.stream = None, None, None
         if flat.is_cuda:
             with torch.cuda.device(flat.device):
@@ -393,6 +393,19 @@ class BucketedGradientAverager:
                 for e in self.events:
                     e.record()                    # (a torch event owns its hipEvent_t from the first record on)
                 self.event_ptrs = (ctypes.c_void_p * n)(*[e.cuda_event for e in self.events])
+
+    @property
+    def active(self):
+        """Whether reduce() averages.  Looked up at every call, not once at construction: a trainer built before
+        init_process_group averages from the first step after it, instead of training on its own without a word.  Assigning
+        True or False overrides the lookup (tests force the reduction at world size 1)."""
+        if self._forced is not None:
+            return self._forced
+        return dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1
+
+    @active.setter
+    def active(self, value):
+        self._forced = None if value is None else bool(value)
 
     def reduce(self):
         """Call right after the step was enqueued: averages self.flat over the group, bucket by bucket."""

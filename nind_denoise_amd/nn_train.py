@@ -10,6 +10,8 @@ egrun:
     python -m nind_denoise_amd.nn_train --config configs/train_conf_utnet_std.yaml --debug_options short_run --epochs 6
 then
     python -m nind_denoise_amd.nn_train --config configs/train_conf_utnet_std.yaml
+data parallel, one process per GPU (this process starts the ranks and stays off the GPU; or start them with torchrun):
+    python -m nind_denoise_amd.nn_train --config configs/train_conf_utnet_std.yaml --gpus 8
 
 Not built, and refused by name: discriminators (--weight_D1 / --weight_D2 and the options that need them), generators other than
 UtNet, the CPU whole-image test pass (--test_interval) and clean-clean mixing (--clean_data_ratio).
@@ -17,8 +19,12 @@ UtNet, the CPU whole-image test pass (--test_interval) and clean-clean mixing (-
 import argparse
 import collections
 import datetime
+import hashlib
 import os
 import shutil
+import signal
+import socket
+import subprocess
 import sys
 import time
 
@@ -30,16 +36,19 @@ from .common.libs import json_saver
 
 DEFAULT_CONFIG_FPATH = os.path.join('configs', 'train_conf_defaults.yaml')
 DEBUG_OPTIONS = ('short_run', 'check_dataset', 'output_val_images', 'output_test_images', 'keep_all_output_images')
+MAX_GPUS = 16         # --gpus: one process per rank, and no more than 16 processes may hold a GPU open at a time
+KILL_GRACE_S = 10     # launch(): seconds between SIGTERM and SIGKILL for the ranks that outlive a failed one
 
 
 class Printer:
-    '''print, and append to a file (nn_common.py:364-378)'''
-    def __init__(self, tostdout=True, tofile=True, file_path='log'):
-        self.tostdout, self.tofile, self.file_path = tostdout, tofile, file_path
+    '''print, and append to a file (nn_common.py:364-378).  prefix: put before every line on stdout (a rank's name); flush: every
+    line leaves at once and whole (ranks share one stdout)'''
+    def __init__(self, tostdout=True, tofile=True, file_path='log', prefix='', flush=False):
+        self.tostdout, self.tofile, self.file_path, self.prefix, self.flush = tostdout, tofile, file_path, prefix, flush
 
     def print(self, msg):
         if self.tostdout:
-            print(msg)
+            print(self.prefix + str(msg) if self.prefix else msg, flush=self.flush)
         if self.tofile:
             try:
                 with open(self.file_path, 'a') as f:
@@ -123,6 +132,8 @@ def build_parser():
     parser.add_argument('--expname', help='Name of the run directory under models_dpath (default: date and command line)')
     parser.add_argument('--log_interval', type=int, default=50, help='Print an iteration line every N steps (0: never)')
     parser.add_argument('--val_batch_size', type=int, default=32, help='Validation pairs per launch of the network')
+    parser.add_argument('--gpus', type=int, help=f'Data-parallel ranks, one process per GPU (1..{MAX_GPUS}; default 1: this process trains). Each rank takes --batch_size crops per step')
+    parser.add_argument('--dist_backend', choices=('nccl', 'gloo'), help='Backend of the process group (default: nccl when every rank has a GPU of its own, else gloo: ranks share GPUs and gradients are staged through the host)')
     return parser
 
 
@@ -278,9 +289,67 @@ def make_expname(argv):
     return (datetime.datetime.now().isoformat()[:-10] + '_' + '_'.join(argv).replace('/', '-'))[0:255]
 
 
+# ------------------------------------------------------------------ data parallel: what the ranks agree on
+def from_rank0(value, group):
+    '''rank 0's `value` on every rank of `group` (any picklable object; one broadcast)'''
+    import torch.distributed as tdist
+    box = [value]
+    tdist.broadcast_object_list(box, src=tdist.get_global_rank(group, 0), group=group)
+    return box[0]
+
+
+def combine_epoch_sums(sums, count, group):
+    '''The means of an epoch over the steps of every rank.  sums: this rank's sums over its own steps, Python floats (doubles);
+    count: the number of those steps.  Every rank gathers every rank's (sums, count) and adds them in rank order, so all ranks
+    hold the same bits.  Returns (the list of means, the total count).'''
+    import torch.distributed as tdist
+    parts = [None] * tdist.get_world_size(group)
+    tdist.all_gather_object(parts, ([float(v) for v in sums], int(count)), group=group)
+    totals, total_count = [0.0] * len(sums), 0
+    for part_sums, part_count in parts:         # rank order
+        totals = [a + b for a, b in zip(totals, part_sums)]
+        total_count += part_count
+    return [t / total_count for t in totals], total_count
+
+
+def check_agreement(flat, group, epoch):
+    '''RuntimeError, on every rank, unless all ranks hold the same parameters: every rank's (sum, sum of magnitudes) of its flat
+    parameter buffer, both in double, are gathered and compared with rank 0's as bits.  One small collective.'''
+    import struct
+    import torch.distributed as tdist
+    d = flat.detach().double()
+    mine = struct.pack('<2d', *torch.stack((d.sum(), d.abs().sum())).tolist())
+    sums = [None] * tdist.get_world_size(group)
+    tdist.all_gather_object(sums, mine, group=group)
+    bad = [r for r, s in enumerate(sums) if s != sums[0]]
+    if bad:
+        shown = ', '.join(f'rank {r}: sum {struct.unpack("<2d", sums[r])[0]!r}, sum of magnitudes {struct.unpack("<2d", sums[r])[1]!r}'
+                          for r in [0] + bad)
+        raise RuntimeError(f'nn_train: after epoch {epoch} the parameters of rank(s) {bad} differ from rank 0\'s ({shown}): '
+                           'the ranks have diverged, and no checkpoint was saved for this epoch')
+
+
+def parameters_digest(state_dict):
+    '''SHA-256 over the tensors of a state dict, in its order, as their raw bytes'''
+    h = hashlib.sha256()
+    for value in state_dict.values():
+        h.update(value.detach().to('cpu').contiguous().numpy().tobytes())
+    return h.hexdigest()
+
+
+class _NoResults:
+    '''what a rank other than 0 holds in place of the JSONSaver: rank 0 owns trainres.json'''
+    def add_res(self, *args, **kwargs):
+        pass
+
+
 # ------------------------------------------------------------------ the run
 def run(args, process_group=None, argv=None):
-    '''The training run, in the reference's order of events.  Returns the run directory.'''
+    '''The training run, in the reference's order of events.  Returns the run directory.
+    process_group: every rank of the group calls this with the same args.  Rank 0 names the run, its parameters are broadcast,
+    it alone writes the run directory's files, its clock decides time_limit; every rank takes batch_size crops per step from its
+    own copy of the whole pool, validation is sharded, the epoch's mean loss is over all ranks' steps, and every epoch ends with
+    check_agreement.  None: this process alone.'''
     from .crop_pool import CropPool
     from .train import UtNetTrainer
     from .validation import ValidationSet, validate
@@ -299,11 +368,18 @@ def run(args, process_group=None, argv=None):
         import torch.distributed as tdist
         rank, world = tdist.get_rank(process_group), tdist.get_world_size(process_group)
 
+    # one run directory, and rank 0 owns every file in it: the other ranks print to stdout under their rank and record nothing
     expname = args.expname if args.expname else make_expname(argv)
+    if world > 1:
+        expname = from_rank0(expname, process_group)
     model_dir = os.path.join(args.models_dpath, expname)
-    os.makedirs(model_dir, exist_ok=True)
-    jsonsaver = json_saver.JSONSaver(os.path.join(model_dir, 'trainres.json'), step_type='epoch')
-    p = Printer(file_path=os.path.join(model_dir, 'train.log'))
+    if rank == 0:
+        os.makedirs(model_dir, exist_ok=True)
+        jsonsaver = json_saver.JSONSaver(os.path.join(model_dir, 'trainres.json'), step_type='epoch')
+        p = Printer(file_path=os.path.join(model_dir, 'train.log'), flush=world > 1)
+    else:
+        jsonsaver = _NoResults()
+        p = Printer(tofile=False, prefix=f'[rank {rank}] ', flush=True)
     p.print(args)
     p.print('cmd: python3 ' + ' '.join(argv))
     args.test_reserve = get_test_reserve_list(args.test_reserve)
@@ -326,11 +402,18 @@ def run(args, process_group=None, argv=None):
         pool.keep_groups(3 * args.batch_size)
     steps = pool.n_groups // args.batch_size // world
     p.print(f'Crop pool: {pool.n_groups} groups, {pool.n_images} images, {pool.nbytes / 1e6:.1f} MB in HBM; {steps} steps per epoch')
+    if world > 1:
+        # CropPool.epoch deals batch k to rank k % world from pools with the same groups and generator state: every rank holds all
+        p.print(f'Data parallel: {world} ranks, {args.batch_size} crops per rank and step; every rank read every file and holds '
+                f'the whole pool: {pool.nbytes / 1e6:.1f} MB of HBM per rank, {world} readers of the same files')
 
     # init models
     model = nn_common.Model.instantiate_model(models_dpath=args.models_dpath, model_path=args.g_model_path, network='UtNet',
                                               device=device, pfun=p.print, keyword='generator', funit=args.g_funit,
                                               activation=args.g_activation)
+    if world > 1:       # rank 0's parameters on every rank, before the trainer takes them into its flat buffer
+        from .dist import broadcast_parameters
+        broadcast_parameters(model, 0, process_group)
     trainer = UtNetTrainer(model, lr=args.g_lr, beta1=args.beta1, weights={k: v for k, v in weights.items() if k[0] != 'D'},
                            device=device, process_group=process_group, loss_cs=args.loss_cs)
     model.train()
@@ -348,12 +431,13 @@ def run(args, process_group=None, argv=None):
         def get_validation_dpath(epoch):
             return os.path.join(model_dir, 'val', str(epoch)) if 'output_val_images' in args.debug_options else None
         validation_loss, _ = validate(model, validation_set, trainer.weights, args.loss_cs, batch_size=args.val_batch_size,
-                                      output_to_dir=get_validation_dpath(0))
+                                      output_to_dir=get_validation_dpath(0), group=process_group)
         jsonsaver.add_res(0, {'validation_loss': validation_loss}, write=True)
         p.print(f'Validation loss: {validation_loss}')
 
-    with open(os.path.join(model_dir, 'config.yaml'), 'w') as fp:
-        yaml.dump(vars(args), fp)
+    if rank == 0:
+        with open(os.path.join(model_dir, 'config.yaml'), 'w') as fp:
+            yaml.dump(vars(args), fp)
 
     start_time = time.time()
     generator_loss_hist = collections.deque(maxlen=args.patience)
@@ -368,15 +452,16 @@ def run(args, process_group=None, argv=None):
                                 exp_mult_max, rank, world, args.log_interval,
                                 lambda it, loss: p.print('Epoch %u batch %u/%u: loss G: weighted: %.3f' % (epoch, it, steps, loss)))
 
-        # cleanup previous epochs
-        removed = delete_outperformed_models(dpath=model_dir, keepers=jsonsaver.get_best_steps(), model_t='generator',
-                                             keep_all_output_images='keep_all_output_images' in args.debug_options)
-        p.print(f'delete_outperformed_models removed {removed}')
+        # cleanup previous epochs (rank 0 alone: it saved them, and every rank has finished writing the images of earlier epochs)
+        if rank == 0:
+            removed = delete_outperformed_models(dpath=model_dir, keepers=jsonsaver.get_best_steps(), model_t='generator',
+                                                 keep_all_output_images='keep_all_output_images' in args.debug_options)
+            p.print(f'delete_outperformed_models removed {removed}')
 
         # Do validation
         if args.validation_interval > 0 and epoch % args.validation_interval == 0:
             validation_loss, _ = validate(model, validation_set, trainer.weights, args.loss_cs, batch_size=args.val_batch_size,
-                                          output_to_dir=get_validation_dpath(epoch))
+                                          output_to_dir=get_validation_dpath(epoch), group=process_group)
             jsonsaver.add_res(epoch, {'validation_loss': validation_loss}, write=False)
             p.print(f'Validation loss: {validation_loss}')
 
@@ -384,7 +469,11 @@ def run(args, process_group=None, argv=None):
         p.print('Time elapsed (s): %u (epoch), %u (total)' % (time.time() - epoch_start_time, time.time() - start_time))
         p.print('Generator:')
         if iteration > 0:
-            means = torch.stack((losses[:iteration].double().mean(), ssim_losses[:iteration].double().mean())).tolist()
+            if world > 1:       # the mean over every rank's steps, the same bits on all ranks: the learning-rate rule reads it
+                sums = torch.stack((losses[:iteration].double().sum(), ssim_losses[:iteration].double().sum())).tolist()
+                means, _ = combine_epoch_sums(sums, iteration, process_group)
+            else:
+                means = torch.stack((losses[:iteration].double().mean(), ssim_losses[:iteration].double().mean())).tolist()
             if want_ssim:
                 p.print('Average SSIM loss: %f' % means[1])
                 jsonsaver.add_res(epoch, {'train_SSIM_loss': means[1]}, write=False)
@@ -400,21 +489,140 @@ def run(args, process_group=None, argv=None):
             jsonsaver.add_res(epoch, {'gen_lr': generator_learning_rate}, write=True)
         else:
             p.print('Generator learned nothing')
+        if world > 1:
+            check_agreement(trainer.flat, process_group, epoch)
         if rank == 0:
             save_model(model, model_dir, epoch, 'generator')
-        if args.time_limit and args.time_limit < time.time() - start_time:
+        time_is_up = bool(args.time_limit and args.time_limit < time.time() - start_time)
+        if world > 1 and args.time_limit:       # rank 0's clock decides: no rank may leave while the others wait in an all-reduce
+            time_is_up = from_rank0(time_is_up, process_group)
+        if time_is_up:
             p.print('Time is up')
             break
         if args.min_lr is not None and generator_learning_rate < args.min_lr:
             p.print('Minimum learning rate reached')
             break
+    if world > 1:
+        p.print(f'rank {rank} of {world}: parameters sha256 {parameters_digest(model.state_dict())}')
     return model_dir
+
+
+# ------------------------------------------------------------------ data parallel: starting the ranks
+def check_gpus(gpus):
+    if not 1 <= gpus <= MAX_GPUS:
+        raise ValueError(f'--gpus {gpus}: the number of ranks is between 1 and {MAX_GPUS}')
+    return gpus
+
+
+def strip_option(argv, name):
+    '''argv without `name VALUE` and `name=VALUE`'''
+    out, skip = [], False
+    for arg in argv:
+        if skip:
+            skip = False
+        elif arg == name:
+            skip = True
+        elif not arg.startswith(name + '='):
+            out.append(arg)
+    return out
+
+
+def _free_port():
+    with socket.socket() as s:
+        s.bind(('127.0.0.1', 0))
+        return s.getsockname()[1]
+
+
+def launch(argv, gpus, command=None):
+    '''Starts `gpus` ranks of this command, each a fresh process running `command` (default: python -m nind_denoise_amd.nn_train)
+    with argv less its --gpus option, and RANK, LOCAL_RANK, WORLD_SIZE, MASTER_ADDR and a free MASTER_PORT in its environment, and
+    waits for all of them.  When a rank exits with a status other than 0 the others get SIGTERM, SIGKILL after KILL_GRACE_S
+    seconds, and that status is returned (128 + the signal for a rank that a signal ended); else 0.  This process never touches
+    a GPU: each rank picks its own device (init_rank).'''
+    check_gpus(gpus)
+    argv = strip_option(list(argv), '--gpus')
+    command = [sys.executable, '-m', 'nind_denoise_amd.nn_train'] if command is None else list(command)
+    port = _free_port()
+    procs = []
+    try:            # a SIGTERM to this process ends the ranks too (SystemExit goes through the finally below)
+        previous = signal.signal(signal.SIGTERM, lambda signum, frame: sys.exit(128 + signum))
+    except ValueError:      # not the main thread: signals cannot be caught here
+        previous = None
+    try:
+        for rank in range(gpus):
+            env = dict(os.environ, RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(gpus), MASTER_ADDR='127.0.0.1',
+                       MASTER_PORT=str(port))
+            procs.append(subprocess.Popen(command + argv, env=env))
+        status = 0
+        while status == 0 and any(proc.returncode is None for proc in procs):
+            time.sleep(0.05)
+            for proc in procs:
+                if proc.poll():
+                    status = proc.returncode
+                    break
+        return status if status >= 0 else 128 - status
+    finally:        # a failed rank, or an exception here (Ctrl-C): nothing is left running
+        alive = [proc for proc in procs if proc.poll() is None]
+        for proc in alive:
+            proc.send_signal(signal.SIGTERM)
+        deadline = time.monotonic() + KILL_GRACE_S
+        for proc in alive:
+            try:
+                proc.wait(timeout=max(0.0, deadline - time.monotonic()))
+            except subprocess.TimeoutExpired:
+                proc.kill()
+                proc.wait()
+        if previous is not None:
+            signal.signal(signal.SIGTERM, previous)
+
+
+def world_from_environment():
+    '''(rank, local rank, world size) a launcher left in the environment (launch, or torchrun), or None'''
+    world = int(os.environ.get('WORLD_SIZE', '1'))
+    if world <= 1:
+        return None
+    rank = int(os.environ['RANK'])
+    return rank, int(os.environ.get('LOCAL_RANK', rank)), world
+
+
+def init_rank(rank, local_rank, world, backend=None):
+    '''This process becomes rank `rank` of `world`: its device is LOCAL_RANK % the number of GPUs, set before anything allocates;
+    the backend is nccl (RCCL) when every rank has a GPU of its own, else gloo: ranks then share GPUs and every message is staged
+    through the host (dist._host_staged), the rehearsal the project runs on one GPU.  Returns the process group.'''
+    import torch.distributed as tdist
+    if not torch.cuda.is_available():
+        raise RuntimeError('nn_train: no GPU visible; nind_denoise_amd has no CPU fallback')
+    n_devices = torch.cuda.device_count()
+    torch.cuda.set_device(local_rank % n_devices)
+    backend = backend or ('nccl' if world <= n_devices else 'gloo')
+    if backend == 'nccl' and world > n_devices:
+        raise ValueError(f'--dist_backend nccl: {world} ranks on {n_devices} GPU(s), and RCCL refuses two ranks on one device; use gloo')
+    tdist.init_process_group(backend, rank=rank, world_size=world)      # MASTER_ADDR, MASTER_PORT from the environment
+    return tdist.group.WORLD
 
 
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = parse_args(argv)
-    run(args, argv=['nn_train.py'] + argv)
+    if args.gpus is not None:
+        check_gpus(args.gpus)
+    ranked = world_from_environment()
+    if ranked is None:
+        if (args.gpus or 1) > 1:
+            check_supported(args)       # refuse here what every rank would refuse
+            return launch(argv, args.gpus)
+        run(args, argv=['nn_train.py'] + argv)
+        return 0
+    # a rank: started by launch() above, or by an external launcher such as torchrun
+    rank, local_rank, world = ranked
+    if args.gpus not in (None, world):
+        raise ValueError(f'--gpus {args.gpus} inside a rank of a world of {world} (WORLD_SIZE): a rank does not start ranks')
+    import torch.distributed as tdist
+    group = init_rank(rank, local_rank, world, args.dist_backend)
+    try:
+        run(args, process_group=group, argv=['nn_train.py'] + argv)     # the trainer is built after the group exists
+    finally:
+        tdist.destroy_process_group()
     return 0
 
 

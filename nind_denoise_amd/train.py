@@ -112,10 +112,10 @@ class UtNetTrainer:
 
     def evaluate(self, validation_set, batch_size=32, output_to_dir=None, also=()):
         """The validation pass on this trainer's network, weights and loss crop (validation.validate): (mean weighted loss as a
-        float, the per-sample weighted losses on the device)."""
+        float, the per-sample weighted losses on the device).  A trainer with a process group shards the set over its ranks."""
         from .validation import validate
         return validate(self.model, validation_set, self.weights, self.loss_cs, batch_size=batch_size, output_to_dir=output_to_dir,
-                        also=also)
+                        also=also, group=self.group)
 
     def optimizer_step(self):
         self.steps += 1

@@ -138,34 +138,74 @@ class ValidationSet:
         return self.clean[i], self.noisy[i]
 
 
-def validate(model, validation_set, weights, loss_cs, batch_size=32, output_to_dir=None, also=()):
+def shard_indices(n, rank, world):
+    """The samples of a set of n that rank `rank` of `world` validates: a contiguous slice, the slices in rank order cover
+    range(n) once, and their lengths differ by one at most (empty for some ranks when n < world)."""
+    if n < 0 or world < 1 or not 0 <= rank < world:
+        raise ValueError(f"shard_indices: n {n}, rank {rank}, world {world}")
+    return range(n * rank // world, n * (rank + 1) // world)
+
+
+def gather_in_order(local, n, group):
+    """local: this rank's values for shard_indices(n, rank, world), a 1-D tensor.  Returns the [n] vector in index order, on
+    local's device, the same bits on every rank: one all-gather of slices padded to the longest one (through host memory on a
+    gloo group), then copies only."""
+    import torch.distributed as tdist
+    from .dist import _host_staged
+    rank, world = tdist.get_rank(group), tdist.get_world_size(group)
+    lengths = [len(shard_indices(n, r, world)) for r in range(world)]
+    if local.dim() != 1 or local.numel() != lengths[rank]:
+        raise ValueError(f"gather_in_order: rank {rank} of {world} holds {tuple(local.shape)} values, its slice of {n} has {lengths[rank]}")
+    if world == 1:
+        return local
+    staged = local.is_cuda and _host_staged(group)
+    wire = torch.zeros(max(lengths), dtype=local.dtype, device="cpu" if staged else local.device)
+    wire[:lengths[rank]] = local
+    parts = [torch.empty_like(wire) for _ in range(world)]
+    tdist.all_gather(parts, wire, group=group)
+    return torch.cat([part[:length] for part, length in zip(parts, lengths)]).to(local.device)
+
+
+def validate(model, validation_set, weights, loss_cs, batch_size=32, output_to_dir=None, also=(), group=None):
     """validate_generator (nn_train.py:51-71) with its batch-1 loop batched: the module in eval() mode under no_grad -- the
     inference executor, the arithmetic denoise_image runs on the checkpoint -- over the set in batches (the last one partial), the
     per-sample criteria of each batch, and the mean over all samples of the weighted loss.  Returns (that mean as a Python float,
     the per-sample weighted losses as an [N] device tensor); one host synchronisation per call.  The module is left in train()
     mode, as the reference leaves it.
-    output_to_dir (debug option output_val_images): <dir>/<i>.tif, 8-bit, the clipped output with its borders."""
+    output_to_dir (debug option output_val_images): <dir>/<i>.tif, 8-bit, the clipped output with its borders.
+    group (a torch.distributed process group; None: this process validates the whole set): every rank of the group calls this
+    with the same set and a model with the same parameters; rank r runs the samples shard_indices(N, r, world) (none, when its
+    slice is empty) and writes their images, the per-sample values are gathered in index order, and every rank returns the same
+    mean and the same [N] vector.  With UtNet.split_k = False a sample's value does not depend on its batch, and both are then
+    the single-process ones bit for bit."""
     if batch_size < 1:
         raise ValueError(f"validate: batch_size {batch_size}")
     n = len(validation_set)
-    per_sample = torch.empty(n, dtype=torch.float32, device=validation_set.clean.device)
+    mine = range(n)
+    if group is not None:
+        import torch.distributed as tdist
+        mine = shard_indices(n, tdist.get_rank(group), tdist.get_world_size(group))
+    per_sample = torch.empty(len(mine), dtype=torch.float32, device=validation_set.clean.device)
     outputs = []
     model.eval()
     try:
         with torch.no_grad():
-            for b0 in range(0, n, batch_size):
-                noisy, clean = validation_set.noisy[b0:b0 + batch_size], validation_set.clean[b0:b0 + batch_size]
+            for b0 in range(mine.start, mine.stop, batch_size):
+                b1 = min(b0 + batch_size, mine.stop)
+                noisy, clean = validation_set.noisy[b0:b1], validation_set.clean[b0:b1]
                 y = model(noisy)
-                per_sample[b0:b0 + noisy.shape[0]] = criteria(y, clean, weights, loss_cs, also)["weighted"]
+                per_sample[b0 - mine.start:b1 - mine.start] = criteria(y, clean, weights, loss_cs, also)["weighted"]
                 if output_to_dir is not None:
                     outputs.append(y)
     finally:
         model.train()
+    if group is not None:
+        per_sample = gather_in_order(per_sample, n, group)
     # the mean in float64 over the fp32 per-sample values, as statistics.mean of the reference's Python floats; one synchronisation
     avgloss = per_sample.double().mean().item()
     if output_to_dir is not None:
         from .denoise_image import _save_dbg_jpg      # torchvision.utils.save_image's conversion: clamp, * 255 + 0.5, uint8
         os.makedirs(output_to_dir, exist_ok=True)
-        for i, img in enumerate(torch.cat(outputs)):
+        for i, img in zip(mine, torch.cat(outputs) if outputs else ()):
             _save_dbg_jpg(img, os.path.join(output_to_dir, str(i) + '.tif'))
     return avgloss, per_sample

@@ -9,7 +9,13 @@ One process measures:
   (b) validation.validate over `pairs` pairs at cs^2 in batches, against the pass the parent revision could run: one image at a
       time through the module, torch / pt_losses criteria on the clipped output, one .item() per image;
   (c) ms per nd_criteria call at batch x 3 x cs^2, with and without MS-SSIM (device events around `iters` calls).
-Images are seeded noise: none of the kernels' traffic depends on the picture."""
+Images are seeded noise: none of the kernels' traffic depends on the picture.
+
+    python tools/bench_nn_train.py --gpus N [--dist_backend nccl|gloo] --out profiles/<name>.json
+
+runs the data-parallel leg instead: this process stays off the GPU and starts N ranks of this file (nn_train.launch); every rank
+times (a)'s epoch loop at `batch` crops per rank with the bucketed gradient mean, and validation.validate sharded over the ranks.
+With more ranks than GPUs the ranks share cards over gloo: a rehearsal, not a scaling figure (profiles/nn_train_dp.json)."""
 import argparse
 import json
 import os
@@ -28,8 +34,77 @@ from nind_denoise_amd.train import UtNetTrainer  # noqa: E402
 from nind_denoise_amd.validation import ValidationSet, criteria, validate  # noqa: E402
 
 
+def data_parallel_leg(args, ranked):
+    """One rank of --gpus N (started by nn_train.launch, below): the epoch loop with the bucketed gradient mean and the sharded
+    validation pass, on the pool, network and shapes of the one-process legs.  Every rank times its own windows; rank 0 gathers
+    them and writes the result.  With more ranks than GPUs (gloo) the ranks share cards and gradients are staged through the
+    host: a rehearsal of the code path, which prices that staging and the sharing, not a scaling figure."""
+    import torch.distributed as tdist
+    rank, local_rank, world = ranked
+    group = nn_train.init_rank(rank, local_rank, world, args.dist_backend)
+    try:
+        dev = torch.device("cuda", torch.cuda.current_device())
+        rng = np.random.default_rng(0)
+        pool = CropPool(dev, seed=1, cs=args.cs)                 # every rank: the same groups and generator state
+        for _ in range(args.groups):
+            clean = rng.integers(0, 256, (3, args.side, args.side), dtype=np.uint8)
+            pool.add_group([clean], [clean ^ rng.integers(0, 16, clean.shape, dtype=np.uint8)])
+        pool.device_buffers()
+        steps = args.groups // args.batch // world
+        net = UtNet(funit=args.funit)
+        net.load_state_dict(synth.make_utnet_state_dict(args.funit, seed=123))
+        weights = {"MSSSIM": 1.0}
+        tr = UtNetTrainer(net, lr=1e-4, beta1=0.75, device=dev, weights=weights, loss_cs=args.cs, process_group=group)
+        losses = torch.zeros(steps, device=dev)
+        for _ in range(args.warmup):
+            tr.learn(*reversed(pool.batch(pool.draw(args.batch), exp_mult_min=0.85, exp_mult_max=1.15)))
+        rates = []
+        for _ in range(args.rounds):
+            torch.cuda.synchronize()
+            tdist.barrier(group)
+            t0 = time.perf_counter()
+            n = nn_train.train_epoch(pool, tr, args.batch, losses, None, 0.85, 1.15, rank, world, log_interval=50, log=lambda it, loss: None)
+            means, count = nn_train.combine_epoch_sums([losses[:n].double().sum().item()], n, group)
+            rates.append(round(args.batch * n / (time.perf_counter() - t0), 2))
+        nn_train.check_agreement(tr.flat, group, 0)
+        vclean = torch.rand(args.pairs, 3, args.cs, args.cs, generator=torch.Generator().manual_seed(2))
+        vs = ValidationSet.from_tensors(vclean, (vclean + 0.05 * torch.randn(vclean.shape, generator=torch.Generator().manual_seed(3))).clip(0, 1), dev)
+        val_s = []
+        for r in range(args.rounds + 1):
+            torch.cuda.synchronize()
+            tdist.barrier(group)
+            t0 = time.perf_counter()
+            val_loss = validate(net, vs, weights, args.cs, batch_size=args.val_batch, group=group)[0]
+            torch.cuda.synchronize()
+            if r:                                                # round 0 warms up
+                val_s.append(round(time.perf_counter() - t0, 4))
+        gathered = [None] * world
+        tdist.all_gather_object(gathered, {"crops_per_s_windows": rates, "validation_s": val_s}, group=group)
+        if rank == 0:
+            per_rank = [sum(g["crops_per_s_windows"]) / len(g["crops_per_s_windows"]) for g in gathered]
+            result = {
+                "device": torch.cuda.get_device_name(dev), "world": world, "backend": tdist.get_backend(group),
+                "gpus_visible": torch.cuda.device_count(), "rehearsal_on_shared_gpus": world > torch.cuda.device_count(),
+                "config": {"groups": args.groups, "source": f"{args.side}x{args.side} u8 pairs", "cs": args.cs, "batch_per_rank": args.batch,
+                           "steps_per_rank_and_epoch": steps, "rounds": args.rounds, "funit": args.funit, "weights": weights,
+                           "exp_mult": [0.85, 1.15], "pairs": args.pairs, "val_batch": args.val_batch},
+                "epoch_loop": {"per_rank": gathered, "crops_per_s_per_rank_mean": [round(v, 2) for v in per_rank],
+                               "crops_per_s_total": round(sum(per_rank), 2), "last_epoch_mean_loss": means[0], "steps_counted": count},
+                "validation": {"sharded_s_rank0": val_s, "mean_s": round(sum(val_s) / len(val_s), 4), "loss": val_loss},
+            }
+            print(json.dumps(result))
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+    finally:
+        tdist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1, help="> 1: the data-parallel leg alone, one fresh process per rank")
+    ap.add_argument("--dist_backend", choices=("nccl", "gloo"))
     ap.add_argument("--groups", type=int, default=1024)
     ap.add_argument("--side", type=int, default=256)
     ap.add_argument("--cs", type=int, default=184)
@@ -42,6 +117,11 @@ def main():
     ap.add_argument("--funit", type=int, default=64)
     ap.add_argument("--out", default=os.path.join("profiles", "nn_train.json"))
     args = ap.parse_args()
+    ranked = nn_train.world_from_environment()
+    if ranked is not None:
+        return data_parallel_leg(args, ranked)
+    if args.gpus > 1:        # this process stays off the GPU: the ranks are fresh children running this file
+        return sys.exit(nn_train.launch(sys.argv[1:], args.gpus, command=[sys.executable, os.path.abspath(__file__)]))
     if not torch.cuda.is_available():
         sys.exit("bench_nn_train needs a GPU")
     dev = torch.device("cuda", 0)
