@@ -12,6 +12,28 @@
  *     the library borrows them for the duration of the call, allocates nothing and frees nothing.
  *   - `stream` is a hipStream_t passed as void*; all work is enqueued on it, no hidden synchronisation.
  *   - images are float32 CHW (RGB), tiles are float32 NCHW, exactly as in the reference.
+ *
+ * Workspaces (held to this by tests/test_workspace_contract.py, between guard bytes and after calls whose data was NaN)
+ *   - alignment: pass every buffer as torch's allocator gives it, 512-byte aligned.  That is the only alignment the tests run, so it
+ *     is the only one promised.  The entry points refuse less than 16 bytes for the UtNet workspace and packed weights and less than
+ *     256 bytes for frame_ws; anything between what a check refuses and 512 bytes is untested.
+ *   - a call writes nothing outside [ptr, ptr + the size its *_bytes query returns) of a workspace, or outside the elements of a
+ *     tensor, and no byte outside them reaches a result.
+ *   - workspaces with an init call -- nd_utnet_workspace_init_hw, nd_unet_workspace_init, nd_utnet_train_workspace_init_hw,
+ *     nd_unet_grad_workspace_init, nd_unet_train_workspace_init -- may hold anything before it (callers pass torch.empty); the init
+ *     call writes every byte the entry points later read without having written it (the zero borders, the padded channel planes, the
+ *     slack).  It runs once per geometry, not once per call: whatever earlier calls with that geometry left behind -- whole-tile or
+ *     useful-region runs, NaN and Inf included -- does not reach a later result.
+ *   - plain scratch, no init call, contents on entry do not matter: the workspaces of nd_layer_forward, nd_layer_forward_winograd (the
+ *     Winograd scratch behind the layer plan too), nd_maxpool2_forward, nd_layer_wgrad, nd_mse, nd_ssim, nd_ms_ssim, nd_ssim_loss_grad,
+ *     nd_ssim_padded(_grad), nd_criteria, nd_criteria_grad; the training `blobs` (packed by every forward / step); the packed blob
+ *     handed to a device packer.  One buffer may serve calls of any shapes one after the other.
+ *   - outputs are written in full (y, canvas += on every pixel of the tile range, dx, dw, db, loss, gy, out); of `grads` every
+ *     parameter's range is written, the ranges of UNet's running statistics and of PReLU slopes the activation does not have never.
+ *   - frame_ws is zero-filled once by the caller, never byte-poisoned.  It may then serve any number of frames without another
+ *     zero-fill, frames of another geometry that needs the same nd_utnet_frame_workspace_bytes included (the Python module caches
+ *     the buffer by that size): every call writes what it reads, the tile-origin tables too, and a short last band does not read
+ *     what a full band of an earlier frame left behind it.
  */
 #ifndef NIND_HIP_H
 #define NIND_HIP_H
