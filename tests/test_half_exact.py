@@ -11,15 +11,14 @@ order, split-K slices and every tile shape included.
   cout one step below and above mblk, cin of one K block and of a K loop with a remainder, split-K on and off.
 """
 import itertools
-import re
 
 import pytest
 import torch
-import torch.nn.functional as F
 
 from nind_denoise_amd import _lib, pipeline
 
 import exact_net as E
+from exact_layer import _expected_layer, _integer_layer, _layer_forward, _mismatch, _pixel_grids, variants
 
 pytestmark = pytest.mark.gpu
 
@@ -55,10 +54,6 @@ def _forward_abi(net, x):
     return y.cpu()
 
 
-def _mismatch(got, want):
-    return f"{int((got != want).sum())} of {want.numel()} values differ (NaN: {int(torch.isnan(got).sum())})"
-
-
 # ---------------------------------------------------------------------------- the whole network
 
 @pytest.mark.parametrize("shape", E.FORWARD_SHAPES, ids=lambda s: "x".join(map(str, s)))
@@ -82,7 +77,7 @@ def test_forward_is_the_restatement(dev, dtype, shape):
 
 def test_fp32_direct_forward_is_the_unrounded_restatement(dev):
     """Same weights, fp32 storage, direct convolution on every 3x3 layer (the Winograd forms transform with non-dyadic
-    fractions and are not part of this)."""
+    fractions and are not part of this: tests/test_f32_exact.py holds them exactly on weights that are multiples of the denominators)."""
     shape = E.FORWARD_SHAPES[0]
     want = E.expected_forward(None, shape)
     net = _net(dev, "f32")
@@ -114,41 +109,10 @@ def test_frame_loop_is_the_restatement(dev, dtype):
 # ---------------------------------------------------------------------------- every 16-bit variant at its tile edges
 
 KBLOCK = 16      # input channels per K block in 16-bit storage
-_NAME = re.compile(r"^(bf16|f16)_m(\d+)x(\d+)_n(\d+)x(\d+)_t(\d+)_k(\d+)_up(true|false)_s(\d+)$")
 
 
 def _variants(dtype):
-    lib = _lib.load()
-    out = []
-    for v in range(lib.nd_num_conv_variants()):
-        m = _NAME.match(lib.nd_conv_variant_name(v).decode())
-        if m and m.group(1) == dtype:
-            mr, wm, nr, wn, taps, kbc = (int(m.group(i)) for i in range(2, 8))
-            out.append(dict(v=v, name=m.group(0), mblk=32 * mr * wm, nblk=32 * nr * wn, taps=taps, kbc=kbc, up=m.group(8) == "true"))
-    return out
-
-
-def _grid_of(count, min_rows):
-    """(rows, cols) with rows * cols == count, both >= min_rows, cols no multiple of 8, as square as possible; None if there is none."""
-    best = None
-    for rows in range(min_rows, count // min_rows + 1):
-        cols = count // rows
-        if count % rows == 0 and cols % 8 and (best is None or abs(rows - cols) < abs(best[0] - best[1])):
-            best = (rows, cols)
-    return best
-
-
-def _pixel_grids(nblk, kind):
-    """Valid grids of nblk - 1 and nblk + 1 pixels per image.  A 3x3 transposed layer has at least three output rows; where
-    nblk + 1 has no such factorisation (257 is prime) it takes the next count above that has one."""
-    min_rows = 3 if kind == "convT3" else 1
-    grids = []
-    for count in (nblk - 1, nblk + 1):
-        while _grid_of(count, min_rows) is None:
-            assert kind == "convT3" and count > nblk
-            count += 1
-        grids.append(_grid_of(count, min_rows))
-    return grids
+    return variants(dtype)
 
 
 def _variant_shapes(V):
@@ -166,56 +130,6 @@ def _variant_shapes(V):
                     "convT2s2": (hv, wv)}[kind]
             cases += [(kind, kb * KBLOCK, cout, h, w) for kb in kblocks for cout in couts]
     return cases
-
-
-def _integer_layer(kind, cin, cout, h, w, seed, batch=3):
-    """Dense small integers (|x| <= 3, |w| <= 2, integer bias): the largest sum, 3 * 2 * 9 * cin + 8 < 2^14 for cin <= 320, is exact."""
-    g = torch.Generator().manual_seed(seed)
-    k = {"conv3": 3, "convT3": 3, "conv1": 1, "conv2s2": 2, "convT2s2": 2}[kind]
-    x = torch.randint(-3, 4, (batch, cin, h, w), generator=g).float()
-    wt = torch.randint(-2, 3, (cout, cin, k, k) if kind in ("conv3", "conv1", "conv2s2") else (cin, cout, k, k), generator=g).float()
-    b = torch.randint(-8, 9, (cout,), generator=g).float()
-    return x, wt, b
-
-
-def _expected_layer(kind, x, w, b, act, slope, tdt):
-    x, w, b = x.double(), w.double(), b.double()
-    if kind in ("conv3", "conv1"):
-        y = F.conv2d(x, w, b)
-    elif kind == "conv2s2":
-        y = F.conv2d(x, w, b, stride=2)
-    else:
-        y = F.conv_transpose2d(x, w, b, stride=2 if kind == "convT2s2" else 1)
-    if act == "PReLU":
-        y = torch.where(y > 0, y, y * slope)
-    return y.to(tdt).float()
-
-
-def _layer_forward(dev, kind, x, w, b, act, slope, variant, dtype, flags):
-    """nd_layer_forward into a NaN-prefilled output (layer_forward of test_hip_parity.py), or None where the launcher refuses the
-    pair of variant and shape with ND_EINVAL."""
-    lib = _lib.load()
-    k, dt = _lib.KIND[kind], _lib.DTYPE[dtype]
-    B, cin, H, W = x.shape
-    cout = w.shape[0] if kind in ("conv3", "conv1", "conv2s2") else w.shape[1]
-    nbytes = lib.nd_layer_packed_bytes(k, cin, cout, dt)
-    packed = torch.empty(nbytes // 4, dtype=torch.float32)
-    wc, bc = w.contiguous(), b.contiguous()
-    _lib.check(lib.nd_layer_pack(k, cin, cout, dt, wc.data_ptr(), bc.data_ptr(), packed.data_ptr(), nbytes))
-    packed = packed.to(dev)
-    oh, ow = {"conv3": (H - 2, W - 2), "convT3": (H + 2, W + 2), "convT2s2": (2 * H, 2 * W), "conv1": (H, W),
-              "conv2s2": (H // 2, W // 2)}[kind]
-    y = torch.full((B, cout, oh, ow), float("nan"), dtype=torch.float32, device=dev)
-    wsb = lib.nd_layer_workspace_bytes(k, B, cin, cout, H, W, dt)
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    xd = x.to(dev).contiguous()
-    rc = lib.nd_layer_forward(k, _lib.ACT[act], slope, dt, packed.data_ptr(), xd.data_ptr(), B, cin, H, W, cout, y.data_ptr(),
-                              ws.data_ptr(), wsb, variant, flags, _lib.stream_ptr(dev))
-    if rc == -1:        # ND_EINVAL
-        return None
-    _lib.check(rc, "nd_layer_forward")
-    torch.cuda.synchronize()
-    return y.cpu()
 
 
 _RAN = {}       # (dtype, variant index in its group) -> [shapes run, shapes refused]
