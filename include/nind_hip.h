@@ -541,6 +541,14 @@ int nd_crop_source(int cs, int nrot, int flips, int y, int x, int *a, int *b);
 int nd_crop_batch(const void *pool, size_t pool_bytes, const int64_t *images, int n_images, const int32_t *draws, int batch, int cs,
                   float exp_mult_min, float exp_mult_max, const float *mult, float *xmax, float *mult_out, float *clean_nchw,
                   float *noisy_nchw, void *stream);
+/* Whole pool images as fp32, for work on the files as stored (the MS-SSIM of every clean-noisy pair, crop_pool.CropPool.score_pairs):
+ * out_nchw[i] = image index[i] ([n] int32 in HBM) of the same pool and table, [n,3,h,w] fp32, samples converted as above and
+ * nothing else: no crop, no padding, no orientation, no multiplier.  Guards as above, and a table row whose H x W is not h x w is
+ * not the image asked for: out_nchw[i] is all zeros for it, for an index outside the table and for a row outside the pool; nothing
+ * is read out of range.  Stream-ordered; allocates nothing.  ND_EINVAL: a null pointer, n_images < 1, n outside [1, 65535], h or w
+ * outside [1, 16384]. */
+int nd_pool_fetch(const void *pool, size_t pool_bytes, const int64_t *images, int n_images, const int32_t *index, int n, int h, int w,
+                  float *out_nchw, void *stream);
 
 /* ---- Winograd forms of a 3x3 layer, fp32 inference (same math as nd_layer_forward on a CONV3 / CONVT3 layer, re-associated).
  * tile = 2 | 4 | 6: three-pass F(tile x tile, 3 x 3) (input transform, one launch of (tile+2)^2 GEMMs, output transform;

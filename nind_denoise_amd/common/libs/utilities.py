@@ -49,3 +49,13 @@ def avg_listofdicts(listofdicts):
         for akey, aval in adict.items():
             res[akey].append(aval)
     return {akey: statistics.mean(vals) for akey, vals in res.items()}
+
+
+def list_of_tuples_to_csv(listoftuples, heading, fpath):
+    """One csv row per tuple under a heading row (utilities.py:71-76)."""
+    import csv
+    with open(fpath, 'w') as fp:
+        csvwriter = csv.writer(fp)
+        csvwriter.writerow(heading)
+        for arow in listoftuples:
+            csvwriter.writerow(arow)

@@ -10,20 +10,27 @@ the device under one seeded generator.  No file decode, no worker processes and 
         clean, noisy = pool.batch(draws)          # the reference's batch[0] is the clean one
         trainer.learn(noisy, clean)
 
+Quality bar (DenoisingDataset.list_content_quality and the docstring of PickyDenoisingDatasetFromList, dataset_torch_3.py:215-298):
+score_pairs() gives the MS-SSIM of every (clean, noisy) pair of the resident files, list_content_quality() writes the reference's
+csv, and after set_min_quality(q) draws take only pairs whose score is above q.
+
 Not built: the sigmamin / sigmamax artificial noise and the JPEG re-compression branch of the reference's __getitem__ (the first is
 "rarely used / experimental" by its docstring, the second calls .save on a numpy array).
 """
+import csv
+import math
 import os
 
 import numpy as np
 import torch
 
 from . import _lib
-from .common.libs import np_imgops
+from .common.libs import np_imgops, utilities
 from .dataset_torch_3 import sortISOs
 
 _TYPES = {np.dtype(np.uint8): _lib.SAMPLE_U8, np.dtype(np.uint16): _lib.SAMPLE_U16, np.dtype(np.float32): _lib.SAMPLE_F32}
 _ALIGN = 16
+MS_SSIM_MIN_SIDE = 161      # nd_ms_ssim (include/nind_hip.h): five scales of an 11-tap window; below it piqa raises
 
 
 def pack_draws(clean, noisy, x0, y0, nrot, flip1, flip2, u, device=None):
@@ -64,6 +71,11 @@ class CropPool:
         self._staged = []        # host arrays not yet uploaded
         self._images = []        # (byte offset, H, W, sample type) per image
         self.sets = []           # from_directories: (datadir, set, crop file, base ISOs, other ISOs) per group
+        self.datadirs = None     # from_directories: the directories as given
+        self.scores = None       # score_pairs: [pairs] fp32 on the device, in pair order
+        self.pairs = None        # score_pairs / set_min_quality: [pairs, 3] int64 on the device (group, clean image, noisy image)
+        self.min_quality = None
+        self._bar = None         # set_min_quality: (passing pairs [P, 2], first [G], count [G], active groups [A]) on the device
         self._groups = []        # (first clean image, clean images, first noisy image, noisy images, H, W) per group
         self._bytes = 0
         self._pool = self._table = self._gt = None
@@ -96,7 +108,7 @@ class CropPool:
             first.append(first[0])
         _, h, w = lists[0][0].shape
         self._groups.append((first[0], len(clean_images), first[1], len(noisy_images), h, w))
-        self._gt = None
+        self._gt = self.scores = self.pairs = self.min_quality = self._bar = None
         return len(self._groups) - 1
 
     def keep_groups(self, count):
@@ -112,6 +124,7 @@ class CropPool:
         arrays = [staged[off] for off, _, _, _ in self._images]
         self.sets = self.sets[:count]
         self._staged, self._images, self._groups, self._bytes, self._gt = [], [], [], 0, None
+        self.scores = self.pairs = self.min_quality = self._bar = None
         moved = {}
         for c0, nc, n0, nn, h, w in groups:        # images of a group are consecutive: re-add each run once, in the old order
             first = []
@@ -134,6 +147,7 @@ class CropPool:
             if len(parts) >= 3 and parts[-2].isdigit() and parts[-1].isdigit():
                 cs = int(parts[-2])
         pool = cls(device, seed=seed, cs=cs)
+        pool.datadirs = [os.fspath(d) for d in datadirs]
 
         def reserved(aset):
             if exact_reserve:
@@ -174,6 +188,11 @@ class CropPool:
     @property
     def n_groups(self):
         return len(self._groups)
+
+    @property
+    def n_active_groups(self):
+        """Groups that draw() and epoch() take from: all of them, or with a quality bar those with a pair above it."""
+        return self.n_groups if self._bar is None else int(self._bar[3].shape[0])
 
     @property
     def n_images(self):
@@ -221,8 +240,13 @@ class CropPool:
         def pick(col, count):       # uniform over [0, count): floor(r * count), clamped against a product that rounds up
             return torch.minimum((r[:, col] * count).to(torch.int64), count - 1)
 
-        clean = gt[:, 0] + pick(0, gt[:, 1])                               # get_x_y_paths: two independent choices
-        noisy = gt[:, 2] + pick(1, gt[:, 3])
+        if self._bar is None:
+            clean = gt[:, 0] + pick(0, gt[:, 1])                           # get_x_y_paths: two independent choices
+            noisy = gt[:, 2] + pick(1, gt[:, 3])
+        else:                                                              # one choice among the group's pairs above the bar
+            passing, first, count, _ = self._bar
+            pair = passing[first[groups] + pick(0, count[groups])]
+            clean, noisy = pair[:, 0], pair[:, 1]
         x0 = pick(2, (gt[:, 5] - cs).clamp_(min=0) + 1)                    # randint(0, W - cs); a padded side gets 0
         y0 = pick(3, (gt[:, 4] - cs).clamp_(min=0) + 1)
         table = pack_draws(clean, noisy, x0, y0, bits & 3, (bits >> 2) & 1, (bits >> 3) & 1, u)
@@ -234,6 +258,10 @@ class CropPool:
         self._group_table()
         if batch_size < 1:
             raise ValueError(f"CropPool.draw: batch_size {batch_size}")
+        if self._bar is not None:
+            active = self._bar[3]
+            return self._draw_groups(active[torch.randint(0, active.shape[0], (batch_size,), device=self.device,
+                                                          generator=self.generator)], cs)
         groups = torch.randint(0, self.n_groups, (batch_size,), device=self.device, generator=self.generator)
         return self._draw_groups(groups, cs)
 
@@ -241,17 +269,155 @@ class CropPool:
         """One pass over the groups in a random order, in full batches (DataLoader(shuffle=True, drop_last=True)).  With world > 1
         every rank must hold a pool with the same groups and generator state: batch k of the single-rank epoch goes to rank
         k % world, each rank gets the same number of batches (the last len(epoch) % world batches are dropped), and the generator
-        advances alike on all ranks."""
+        advances alike on all ranks.  With a quality bar the pass is over the active groups, and so are the counts above."""
         cs = self._cs(cs)
         self._group_table()
         if batch_size < 1 or world < 1 or not 0 <= rank < world:
             raise ValueError(f"CropPool.epoch: batch_size {batch_size}, rank {rank}, world {world}")
-        perm = torch.randperm(self.n_groups, device=self.device, generator=self.generator)
-        steps = self.n_groups // batch_size // world
+        if self._bar is None:
+            perm = torch.randperm(self.n_groups, device=self.device, generator=self.generator)
+        else:
+            perm = self._bar[3][torch.randperm(self.n_active_groups, device=self.device, generator=self.generator)]
+        steps = perm.shape[0] // batch_size // world
         for k in range(steps * world):
             draws = self._draw_groups(perm[k * batch_size:(k + 1) * batch_size], cs)
             if k % world == rank:
                 yield draws
+
+    # ------------------------------------------------------------------ quality
+    def pair_table(self):
+        """[pairs, 3] int64 numpy rows (group, clean image, noisy image) in the order of get_all_crop_pairs_of_paths
+        (dataset_torch_3.py:203-213): groups in pool order, base ISOs outer, other ISOs inner."""
+        rows = [(g, c0 + i, n0 + j) for g, (c0, nc, n0, nn, _, _) in enumerate(self._groups) for i in range(nc) for j in range(nn)]
+        return np.asarray(rows, dtype=np.int64).reshape(-1, 3)
+
+    def _pairs_on_device(self):
+        if self.pairs is None:
+            if not self._groups:
+                raise ValueError("CropPool: the pool has no group")
+            self.pairs = torch.from_numpy(self.pair_table()).to(self.device)
+        return self.pairs
+
+    def score_pairs(self, batch_size=64):
+        """MS-SSIM (piqa's MS_SSIM(): the similarity, not 1 - it) of every (clean image, noisy image) pair of every group, on the
+        files as stored: a [pairs] float32 tensor on the device in the order of pair_table(), kept as self.scores beside
+        self.pairs.  Pairs are taken by size (H, W), batch_size at a time: nd_pool_fetch makes the two fp32 batches, nd_ms_ssim
+        scores each sample on its own, so no score depends on batch_size.  A pair with a side below 161 gets NaN.  Nothing here waits
+        for the GPU."""
+        if batch_size < 1 or batch_size > 10922:      # nd_ms_ssim takes 32767 image planes at most
+            raise ValueError(f"CropPool.score_pairs: batch_size {batch_size} outside [1, 10922]")
+        table = self.pair_table()
+        if not len(table):
+            raise ValueError("CropPool: the pool has no group")
+        pool, images = self._upload()
+        sizes = np.asarray([(g[4], g[5]) for g in self._groups], dtype=np.int64)[table[:, 0]]
+        order = np.lexsort((np.arange(len(table)), sizes[:, 1], sizes[:, 0]))        # by size, pair order inside a size
+        # one upload: the pairs in scoring order, as the kernel's index type, and where each goes in pair order
+        up = torch.from_numpy(np.ascontiguousarray(np.stack((table[order, 1], table[order, 2], order)))).to(self.device)
+        by_size, place = up[:2].to(torch.int32).contiguous(), up[2]
+        assert by_size.stride() == (len(table), 1)                         # rows of the kernel's index type, sliced below
+        scored = torch.full((len(table),), float("nan"), dtype=torch.float32, device=self.device)
+        lib = _lib.load()
+        sorted_sizes = sizes[order]
+        bounds = np.flatnonzero((np.diff(sorted_sizes, axis=0) != 0).any(axis=1)) + 1
+        with torch.cuda.device(self.device):
+            stream = _lib.stream_ptr(self.device)
+            for a, b in zip(np.concatenate(([0], bounds)), np.concatenate((bounds, [len(table)]))):
+                h, w = (int(v) for v in sorted_sizes[a])
+                if min(h, w) < MS_SSIM_MIN_SIDE:
+                    continue
+                n = int(min(batch_size, b - a))
+                x = torch.empty(2, n, 3, h, w, dtype=torch.float32, device=self.device)
+                wsb = lib.nd_ssim_workspace_bytes(n, 3, h, w)
+                ws = torch.empty(max(wsb, 4096), dtype=torch.uint8, device=self.device)
+                for k in range(int(a), int(b), n):
+                    m = int(min(n, b - k))
+                    for side in (0, 1):
+                        _lib.check(lib.nd_pool_fetch(pool.data_ptr(), pool.numel(), images.data_ptr(), images.shape[0],
+                                                     by_size[side, k:k + m].data_ptr(), m, h, w, x[side].data_ptr(), stream),
+                                   "nd_pool_fetch")
+                    _lib.check(lib.nd_ms_ssim(x[0].data_ptr(), x[1].data_ptr(), m, 3, h, w, scored[k:k + m].data_ptr(), ws.data_ptr(),
+                                              ws.numel(), stream), "nd_ms_ssim")
+        scores = torch.empty_like(scored)
+        scores[place] = scored
+        self.scores = scores
+        self._pairs_on_device()
+        return scores
+
+    def pair_paths(self):
+        """(xpath, ypath) of every pair in pair order, formed as get_all_crop_pairs_of_paths forms them (dataset_torch_3.py:191,
+        211-212).  Only for a pool made by from_directories."""
+        if self.datadirs is None or len(self.sets) != len(self._groups):
+            raise ValueError("CropPool: file paths are known only for a pool made by from_directories")
+        paths = []
+        for datadir, aset, animg, bisos, isos in self.sets:
+            base = os.path.join(datadir, aset, 'ISOBASE', animg).replace(isos[0] + '_', 'ISOBASE_')
+            for biso in bisos:
+                for iso in isos:
+                    paths.append(tuple(base.replace('ISOBASE_', v + '_').replace('/ISOBASE/', '/' + v + '/') for v in (biso, iso)))
+        return paths
+
+    @property
+    def dsname(self):
+        if self.datadirs is None:
+            raise ValueError("CropPool: a dataset name is known only for a pool made by from_directories")
+        return '+'.join(utilities.get_leaf(path) for path in self.datadirs)
+
+    def list_content_quality(self, export=False, out_dir='datasets'):
+        """(xpath, ypath, score) of every pair, in pair order (DenoisingDataset.list_content_quality, dataset_torch_3.py:215-229);
+        the score is a float, NaN where score_pairs gives NaN.  Scores the pool first unless it holds scores.  export: writes
+        <out_dir>/<dsname>-msssim.csv with the header xpath,ypath,score; a score is written as repr(float), NaN as an empty field.
+        The one read of the scores is the only wait for the GPU."""
+        paths = self.pair_paths()
+        scores = (self.scores if self.scores is not None else self.score_pairs()).cpu().tolist()
+        rows = [(x, y, s) for (x, y), s in zip(paths, scores)]
+        if export:
+            os.makedirs(out_dir, exist_ok=True)
+            outpath = os.path.join(out_dir, self.dsname + '-msssim.csv')
+            utilities.list_of_tuples_to_csv([(x, y, '' if math.isnan(s) else repr(s)) for x, y, s in rows],
+                                            ('xpath', 'ypath', 'score'), outpath)
+            print(f'Quality check exported to {outpath}')
+        return rows
+
+    def _scores_from_csv(self, fpath):
+        paths = self.pair_paths()
+        with open(fpath, 'r', newline='') as fp:
+            rows = [(r['xpath'], r['ypath'], r['score']) for r in csv.DictReader(fp)]
+        listed, mine = {(x, y): s for x, y, s in rows}, set(paths)
+        missing = next((p for p in paths if p not in listed), None)
+        extra = next(((x, y) for x, y, _ in rows if (x, y) not in mine), None)
+        if missing is not None or extra is not None:
+            said = []
+            if missing is not None:
+                said.append(f"the pool's pair {missing[0]}, {missing[1]} is missing from it")
+            if extra is not None:
+                said.append(f"it lists the pair {extra[0]}, {extra[1]}, which the pool does not hold")
+            raise ValueError(f"CropPool.set_min_quality: {fpath} does not list this pool's pairs: " + "; ".join(said))
+        return torch.tensor([float(listed[p]) if listed[p] != '' else float('nan') for p in paths], dtype=torch.float32)
+
+    def set_min_quality(self, q, scores=None):
+        """From now on draw() and epoch() take a group's (clean, noisy) pair uniformly among its pairs with score > q (strictly, as
+        PickyDenoisingDatasetFromList writes it; NaN never passes), and leave out the groups that have none: n_active_groups says
+        how many remain.  scores: a tensor in pair order, the path of a csv that list_content_quality wrote (ValueError unless it
+        lists exactly this pool's pairs), or None for the pool's own scores (score_pairs() first if need be).  q None removes the
+        bar, and draws are again what a pool without one makes.  Returns the number of pairs above the bar."""
+        if q is None:
+            self.min_quality = self._bar = None
+            return None
+        if scores is None:
+            scores = self.scores if self.scores is not None else self.score_pairs()
+        elif isinstance(scores, (str, os.PathLike)):
+            scores = self._scores_from_csv(os.fspath(scores))
+        pairs = self._pairs_on_device()
+        scores = torch.as_tensor(scores, dtype=torch.float32).to(self.device).reshape(-1)
+        if scores.shape[0] != pairs.shape[0]:
+            raise ValueError(f"CropPool.set_min_quality: {scores.shape[0]} scores for {pairs.shape[0]} pairs")
+        above = pairs[scores > float(q)]                                   # pair order: a group's pairs stay consecutive
+        count = torch.bincount(above[:, 0], minlength=self.n_groups)
+        first = torch.cumsum(count, 0) - count
+        self._bar = (above[:, 1:].contiguous(), first, count, torch.nonzero(count).reshape(-1))
+        self.min_quality = float(q)
+        return int(above.shape[0])
 
     # ------------------------------------------------------------------ batches
     def device_buffers(self):

@@ -153,6 +153,21 @@ __global__ __launch_bounds__(256) void k_crop_batch(const unsigned char *__restr
         noisy[out + c * plane] = vn;
     }
 }
+// grid (ceil(h * w / 256), n): image index[n] as fp32, whole: no crop, no padding, no orientation.  A row of another size than
+// h x w is not this image: it reads as zeros, like an index outside the table or a row outside the pool
+__global__ __launch_bounds__(256) void k_pool_fetch(const unsigned char *__restrict__ pool, size_t pool_bytes,
+                                                    const long long *__restrict__ images, int n_images, const int *__restrict__ index,
+                                                    int h, int w, float *__restrict__ out) {
+    const int n = blockIdx.y;
+    const int pix = blockIdx.x * 256 + threadIdx.x;
+    if (pix >= h * w) return;
+    const int y = pix / w, x = pix - y * w;
+    CropImage im = crop_image(pool, pool_bytes, images, n_images, index[n]);
+    if (im.h != h || im.w != w) im.base = nullptr;
+    const size_t plane = (size_t)h * w, o = (size_t)n * 3 * plane + pix;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[o + c * plane] = crop_sample(im, c, y, x);
+}
 }  // namespace
 
 extern "C" int nd_crop_source(int cs, int nrot, int flips, int y, int x, int *a, int *b) {
@@ -185,6 +200,18 @@ extern "C" int nd_crop_batch(const void *pool, size_t pool_bytes, const int64_t 
     }
     hipLaunchKernelGGL(k_crop_batch, dim3((cs * cs + 255) / 256, batch), dim3(256), 0, s, p, pool_bytes, im, n_images, draws, cs, mult,
                        clean_nchw, noisy_nchw);
+    ND_HIP(hipGetLastError());
+    return ND_OK;
+}
+
+extern "C" int nd_pool_fetch(const void *pool, size_t pool_bytes, const int64_t *images, int n_images, const int32_t *index, int n, int h,
+                             int w, float *out_nchw, void *stream) {
+    if (!pool || !pool_bytes || !images || !index || !out_nchw) ND_FAIL(ND_EINVAL, "nd_pool_fetch: null pointer");
+    if (n_images < 1) ND_FAIL(ND_EINVAL, "nd_pool_fetch: n_images %d < 1", n_images);
+    if (h < 1 || h > 16384 || w < 1 || w > 16384) ND_FAIL(ND_EINVAL, "nd_pool_fetch: %d x %d, a side outside [1, 16384]", h, w);
+    if (n < 1 || n > 65535) ND_FAIL(ND_EINVAL, "nd_pool_fetch: n %d outside [1, 65535]", n);
+    hipLaunchKernelGGL(k_pool_fetch, dim3((h * w + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, (const unsigned char *)pool,
+                       pool_bytes, (const long long *)images, n_images, index, h, w, out_nchw);
     ND_HIP(hipGetLastError());
     return ND_OK;
 }

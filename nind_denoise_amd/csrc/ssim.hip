@@ -12,6 +12,11 @@
 // of x and y staged in LDS (row filter of the five moment maps into LDS, then the column filter per output pixel) and
 // reduces it to one partial (sum ss, sum cs); partials are added in a fixed order (deterministic, no atomics).
 // Algorithmic bytes: 2 * 4 B per input pixel per scale (x 1.72 for the 10-pixel halo of a 32 x 32 patch, mostly served by L2).
+//
+// The x, y and xy moments of k_ssim_tile are written with explicit fmaf and explicit roundings, the same operations for all three,
+// so that the map of two equal images is exactly 1 at every pixel.  Left to the compiler's contraction they were not the same: the
+// packed-math pairing took (m0, m1) and (m2, m3) into v_pk_fma and fused s_xx and s_yy, and left the fifth moment with an unfused
+// last tap and s_xy = m4 - round(m0 m1), which put cs of (image, image) up to 2e-6 from 1 where the variance is small against c2.
 #include <math.h>
 
 #include "nd_common.h"
@@ -47,11 +52,11 @@ __global__ __launch_bounds__(256) void k_ssim_tile(const float *__restrict__ x, 
 #pragma unroll
         for (int k = 0; k < kWin; ++k) {
             const float g = c_gauss[k], u = sx[r][c + k], v = sy[r][c + k];
-            a += g * u;
-            b += g * v;
-            aa += g * (u * u);
-            bb += g * (v * v);
-            ab += g * (u * v);
+            a = fmaf(g, u, a);
+            b = fmaf(g, v, b);
+            aa = fmaf(g, u * u, aa);
+            bb = fmaf(g, v * v, bb);
+            ab = fmaf(g, u * v, ab);
         }
         hm[0][r][c] = a;
         hm[1][r][c] = b;
@@ -71,12 +76,18 @@ __global__ __launch_bounds__(256) void k_ssim_tile(const float *__restrict__ x, 
         for (int k = 0; k < kWin; ++k) {
             const float g = c_gauss[k];
 #pragma unroll
-            for (int q = 0; q < 5; ++q) m[q] += g * hm[q][r + k][c];
+            for (int q = 0; q < 5; ++q) m[q] = fmaf(g, hm[q][r + k][c], m[q]);
         }
-        const float mxx = m[0] * m[0], myy = m[1] * m[1], mxy = m[0] * m[1];
-        const float sxx = m[2] - mxx, syy = m[3] - myy, sxy = m[4] - mxy;
-        const float cs = (2.f * sxy + c2) / (sxx + syy + c2);
-        const float ss = (2.f * mxy + c1) / (mxx + myy + c1) * cs;
+        float cs, ss;
+        {
+#pragma clang fp contract(off)
+            // every product and sum below rounds once, as written: with x == y numerator and denominator are the same number
+            const float mxx = m[0] * m[0], myy = m[1] * m[1], mxy = m[0] * m[1];
+            const float sxx = fmaf(-m[0], m[0], m[2]), syy = fmaf(-m[1], m[1], m[3]), sxy = fmaf(-m[0], m[1], m[4]);
+            const float two_sxy = sxy + sxy, two_mxy = mxy + mxy;
+            cs = (two_sxy + c2) / ((sxx + syy) + c2);
+            ss = (two_mxy + c1) / ((mxx + myy) + c1) * cs;
+        }
         sum_ss += ss;
         sum_cs += cs;
     }

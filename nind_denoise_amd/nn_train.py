@@ -15,6 +15,10 @@ data parallel, one process per GPU (this process starts the ranks and stays off 
 
 Not built, and refused by name: discriminators (--weight_D1 / --weight_D2 and the options that need them), generators other than
 UtNet, the CPU whole-image test pass (--test_interval) and clean-clean mixing (--clean_data_ratio).
+
+Quality bar (the cure README.md:140 of the reference names for an unstable start, PickyDenoisingDatasetFromList): --min_quality Q
+trains on the pairs whose MS-SSIM is above Q, for the first --min_quality_epochs epochs or for the whole run; the scores are
+computed from the resident pool at start, or read from the csv of tools.make_dataset_crops_list with --quality_csv.
 '''
 import argparse
 import collections
@@ -132,6 +136,9 @@ def build_parser():
     parser.add_argument('--expname', help='Name of the run directory under models_dpath (default: date and command line)')
     parser.add_argument('--log_interval', type=int, default=50, help='Print an iteration line every N steps (0: never)')
     parser.add_argument('--val_batch_size', type=int, default=32, help='Validation pairs per launch of the network')
+    parser.add_argument('--min_quality', type=float, help='Train only on clean-noisy pairs whose MS-SSIM is above this (strictly); groups without such a pair are left out')
+    parser.add_argument('--min_quality_epochs', type=int, default=0, help='--min_quality holds for the first N epochs of the run, counted from --start_epoch (0: every epoch)')
+    parser.add_argument('--quality_csv', help='Take the pair scores from this csv (python -m nind_denoise_amd.tools.make_dataset_crops_list) instead of scoring the pool at start')
     parser.add_argument('--gpus', type=int, help=f'Data-parallel ranks, one process per GPU (1..{MAX_GPUS}; default 1: this process trains). Each rank takes --batch_size crops per step')
     parser.add_argument('--dist_backend', choices=('nccl', 'gloo'), help='Backend of the process group (default: nccl when every rank has a GPU of its own, else gloo: ranks share GPUs and gradients are staged through the host)')
     return parser
@@ -200,6 +207,12 @@ def check_supported(args):
         raise NotImplementedError('--test_interval > 0: the CPU whole-image test pass is not built; run denoise_dir on a checkpoint')
     if (args.clean_data_ratio or 0) > 0:
         raise NotImplementedError('--clean_data_ratio > 0: clean-clean mixing is not built')
+    if getattr(args, 'min_quality', None) is None:
+        for name in ('min_quality_epochs', 'quality_csv'):
+            if getattr(args, name, None):
+                raise ValueError(f'--{name} needs --min_quality')
+    elif (args.min_quality_epochs or 0) < 0:
+        raise ValueError(f'--min_quality_epochs {args.min_quality_epochs} < 0')
     unknown = set(args.debug_options) - set(DEBUG_OPTIONS)
     if unknown:
         raise ValueError(f'unknown debug options {sorted(unknown)} (available: {DEBUG_OPTIONS})')
@@ -223,6 +236,21 @@ def get_weights(args):
 
 
 # ------------------------------------------------------------------ the pieces of an epoch
+def set_quality_bar(pool, min_quality, quality_csv, batch_size, world, pfun):
+    '''The pool's bar from --min_quality (scores: --quality_csv, or one scoring pass over the pool), with the log lines of it.
+    ValueError when the pairs above the bar leave fewer groups than one step of every rank takes.  Returns the steps per epoch.'''
+    start = time.time()
+    passing = pool.set_min_quality(min_quality, scores=quality_csv)
+    source = quality_csv if quality_csv else 'scored on the pool in %.3f s' % (time.time() - start)
+    steps = pool.n_active_groups // batch_size // world
+    pfun(f'Quality bar: MS-SSIM > {min_quality} ({source}): {passing} of {pool.pairs.shape[0]} pairs pass, '
+         f'{pool.n_active_groups} of {pool.n_groups} groups active; {steps} steps per epoch')
+    if steps < 1:
+        raise ValueError(f'nn_train: --min_quality {min_quality} leaves {pool.n_active_groups} active groups, fewer than the '
+                         f'{batch_size * world} one step takes (batch_size {batch_size} x {world} rank(s))')
+    return steps
+
+
 def delete_outperformed_models(dpath, keepers, model_t='generator', keep_all_output_images=False):
     '''Removes the <model_t>_<epoch>.pt files, and the val/<epoch> and testimages/<epoch> directories unless
     keep_all_output_images, whose epoch is not in keepers (nn_train.py:95-116).  Returns what it removed.'''
@@ -400,8 +428,10 @@ def run(args, process_group=None, argv=None):
         args.cs = pool.cs
     if 'short_run' in args.debug_options:
         pool.keep_groups(3 * args.batch_size)
-    steps = pool.n_groups // args.batch_size // world
+    steps = all_steps = pool.n_groups // args.batch_size // world
     p.print(f'Crop pool: {pool.n_groups} groups, {pool.n_images} images, {pool.nbytes / 1e6:.1f} MB in HBM; {steps} steps per epoch')
+    if args.min_quality is not None:        # every rank scores its own identical pool: the kernels are deterministic
+        steps = set_quality_bar(pool, args.min_quality, args.quality_csv, args.batch_size, world, p.print)
     if world > 1:
         # CropPool.epoch deals batch k to rank k % world from pools with the same groups and generator state: every rank holds all
         p.print(f'Data parallel: {world} ranks, {args.batch_size} crops per rank and step; every rank read every file and holds '
@@ -442,12 +472,17 @@ def run(args, process_group=None, argv=None):
     start_time = time.time()
     generator_loss_hist = collections.deque(maxlen=args.patience)
     generator_learning_rate = trainer.lr
-    losses = torch.zeros(max(steps, 1), dtype=torch.float32, device=device)
+    losses = torch.zeros(max(all_steps, 1), dtype=torch.float32, device=device)
     ssim_losses = torch.zeros_like(losses)
 
     # Train
     for epoch in range(args.start_epoch, args.epochs):
         epoch_start_time = time.time()
+        if pool.min_quality is not None and 0 < args.min_quality_epochs <= epoch - args.start_epoch:
+            pool.set_min_quality(None)
+            steps = all_steps
+            p.print(f'Quality bar lifted after {args.min_quality_epochs} epoch(s): {pool.n_active_groups} groups active; '
+                    f'{steps} steps per epoch')
         iteration = train_epoch(pool, trainer, args.batch_size, losses, ssim_losses if want_ssim else None, exp_mult_min,
                                 exp_mult_max, rank, world, args.log_interval,
                                 lambda it, loss: p.print('Epoch %u batch %u/%u: loss G: weighted: %.3f' % (epoch, it, steps, loss)))
