@@ -110,7 +110,7 @@ typedef enum nd_flags {
                                  nd_unet_denoise_frame: the same switch for the UNet decoder (nd_unet_useful_region)             */
 } nd_flags;
 
-int nd_version(void);   /* 118 = this header */
+int nd_version(void);   /* 119 = this header */
 const char *nd_last_error(void);
 
 /* ---------------------------------------------------------------- tile geometry (host, pure integer)
@@ -459,6 +459,28 @@ int nd_utnet_train_backward_hw(int funit, int act, int flags, const float *param
 int nd_utnet_grad_buckets(int funit, size_t *offsets, size_t *counts, int max);
 int nd_adam_step(float *params, const float *grads, float *m, float *v, float *vmax, size_t n, float lr, float beta1,
                  float beta2, float eps, int step, int amsgrad, void *stream);
+/* Guarded optimizer step (119): gradient clipping by global norm and skipping of non-finite steps, decided on the device.  Both
+ * calls are enqueued on `stream`: no host read, no allocation, no event.
+ *
+ * nd_grad_guard: one streaming pass over the n fp32 gradients (16-byte loads, grads 16-byte aligned, a scalar tail for n % 4;
+ * the grid depends on n alone), per-workgroup partial sums in `workspace` (nd_grad_guard_workspace_bytes), then one workgroup
+ * that adds them in a fixed order: no atomics, the same bits on every run.  It leaves four doubles in HBM at `state`:
+ *   [0] sum of g^2, accumulated in double          [1] the number of non-finite entries (NaN, +inf, -inf)
+ *   [2] scale = max_norm > 0 ? min(max_norm / (sqrt([0]) + 1e-6), 1) : 1  -- the coefficient of torch.nn.utils.clip_grad_norm_,
+ *       in double; a NaN norm gives a NaN scale (torch.clamp keeps NaN), an infinite one gives 0
+ *   [3] ok = skip_nonfinite && [1] > 0 ? 0 : 1
+ *
+ * nd_adam_step_guarded = nd_adam_step reading that state: with ok == 0 it touches nothing; otherwise every element takes
+ * g = grads[i] * (float)scale, one fp32 multiply, into nd_adam_step's own arithmetic -- with scale == 1 the result equals
+ * nd_adam_step bit for bit.  grads is NOT modified: it keeps the unclipped gradient.  `step` comes from the host as for
+ * nd_adam_step (the host never waits to learn whether a step was applied), so a skipped step still advances it.  That differs
+ * from torch.cuda.amp.GradScaler, which does not call optimizer.step() on a skipped step: here the bias-correction index counts
+ * attempts, while m, v, vmax and the parameters do not move on a skipped step. */
+size_t nd_grad_guard_workspace_bytes(size_t n);
+int nd_grad_guard(const float *grads, size_t n, float max_norm, int skip_nonfinite, double *state, void *workspace,
+                  size_t workspace_bytes, void *stream);
+int nd_adam_step_guarded(float *params, const float *grads, float *m, float *v, float *vmax, size_t n, float lr, float beta1,
+                         float beta2, float eps, int step, int amsgrad, const double *state, void *stream);
 
 /* ---- image-quality scores of the eval harness ------------------------------------------
  * Replace pt_helpers.get_losses (common/libs/pt_helpers.py:40-48): F.mse_loss, piqa.SSIM and piqa.MS_SSIM with piqa's

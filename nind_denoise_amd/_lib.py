@@ -128,6 +128,9 @@ _SIGNATURES = {
                                            c_float, c_float, c_float, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p,
                                            POINTER(c_void_p), c_int]),
     "nd_adam_step": (c_int, [c_void_p] * 5 + [c_size_t, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p]),
+    "nd_grad_guard_workspace_bytes": (c_size_t, [c_size_t]),
+    "nd_grad_guard": (c_int, [c_void_p, c_size_t, c_float, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "nd_adam_step_guarded": (c_int, [c_void_p] * 5 + [c_size_t, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_void_p]),
     "nd_ssim_workspace_bytes": (c_size_t, [c_int] * 4),
     "nd_ssim": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_size_t, c_void_p]),
     "nd_ms_ssim": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p, c_size_t, c_void_p]),

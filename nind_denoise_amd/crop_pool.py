@@ -216,6 +216,14 @@ class CropPool:
     def seed(self, seed):
         self.generator.manual_seed(seed)
 
+    def rng_state(self):
+        """The state of the generator behind every draw, as a CPU byte tensor (torch.Generator.get_state): with it, and the same
+        groups and quality bar, another pool makes this pool's next draws."""
+        return self.generator.get_state().clone()
+
+    def set_rng_state(self, state):
+        self.generator.set_state(torch.as_tensor(state, dtype=torch.uint8, device="cpu").contiguous())
+
     def _group_table(self):
         if self._gt is None:
             if not self._groups:

@@ -28,7 +28,7 @@ void nd_set_error(const char *fmt, ...) {
 }
 
 extern "C" const char *nd_last_error(void) { return g_err; }
-extern "C" int nd_version(void) { return 118; }   // 118: UNet training on batch statistics (nd_unet_train_*); 117: UNet under autograd in eval mode (nd_unet_param_*, nd_unet_grad_*); 116: the adjoints of gather and stitch for gradients through a tiled frame (nd_stitch_grad, nd_tile_gather_grad) and the index maps they share with the forward kernels (nd_tile_source, nd_stitch_weight); 115: the training loss and its gradient on their own (nd_criteria_grad), nd_utnet_train_step_hw removed (nd_utnet_train_step_act_hw with ND_ACT_PRELU is that call); 114: per-sample criteria of a batch (nd_criteria), the fused training step for every activation (nd_utnet_train_step_act_hw); 113: augmented training batches from a device-resident crop pool (nd_crop_batch, nd_crop_source); 112: mosaic tile grids of the three-pass Winograd layers (nd_wino_mosaic, ND_FLAG_TILE_WINO); 111: the reference's own zero-padded SSIM, forward and gradient (nd_ssim_padded*); 110: skip halves of the decoder once per band (nd_utnet_frame_folds, ND_FLAG_TILE_SKIPS); 109: UNet on the fused frame loop (nd_unet_denoise_frame, nd_unet_useful_region, nd_unet_pack_weights_device, ND_FLAG_FIND_NOISE); 108: level 2 of the shared encoder (nd_utnet_frame_levels, ND_FLAG_TILE_LEVEL2); 107: nd_utnet_pack_weights_device packs bf16 / fp16 blobs; 106: the square UtNet entry points and nd_utnet_train_step_ev removed (the _hw forms remain); 105: shared-encoder frame loop (nd_utnet_denoise_frame, ND_FLAG_TILE_ENCODER); 104: H x W training entry points, input-image gradient (nd_utnet_train_*_hw); 103: round-3 ABI (train forward / backward halves, gradient bucket events, ND_FLAG_UNFUSED_POOL, GEMM row order of the 2x2 stride-2 transposes)
+extern "C" int nd_version(void) { return 119; }   // 119: guarded optimizer step (nd_grad_guard, nd_adam_step_guarded); 118: UNet training on batch statistics (nd_unet_train_*); 117: UNet under autograd in eval mode (nd_unet_param_*, nd_unet_grad_*); 116: the adjoints of gather and stitch for gradients through a tiled frame (nd_stitch_grad, nd_tile_gather_grad) and the index maps they share with the forward kernels (nd_tile_source, nd_stitch_weight); 115: the training loss and its gradient on their own (nd_criteria_grad), nd_utnet_train_step_hw removed (nd_utnet_train_step_act_hw with ND_ACT_PRELU is that call); 114: per-sample criteria of a batch (nd_criteria), the fused training step for every activation (nd_utnet_train_step_act_hw); 113: augmented training batches from a device-resident crop pool (nd_crop_batch, nd_crop_source); 112: mosaic tile grids of the three-pass Winograd layers (nd_wino_mosaic, ND_FLAG_TILE_WINO); 111: the reference's own zero-padded SSIM, forward and gradient (nd_ssim_padded*); 110: skip halves of the decoder once per band (nd_utnet_frame_folds, ND_FLAG_TILE_SKIPS); 109: UNet on the fused frame loop (nd_unet_denoise_frame, nd_unet_useful_region, nd_unet_pack_weights_device, ND_FLAG_FIND_NOISE); 108: level 2 of the shared encoder (nd_utnet_frame_levels, ND_FLAG_TILE_LEVEL2); 107: nd_utnet_pack_weights_device packs bf16 / fp16 blobs; 106: the square UtNet entry points and nd_utnet_train_step_ev removed (the _hw forms remain); 105: shared-encoder frame loop (nd_utnet_denoise_frame, ND_FLAG_TILE_ENCODER); 104: H x W training entry points, input-image gradient (nd_utnet_train_*_hw); 103: round-3 ABI (train forward / backward halves, gradient bucket events, ND_FLAG_UNFUSED_POOL, GEMM row order of the 2x2 stride-2 transposes)
 
 static inline uint16_t f32_to_bf16_rne(float f) {
     uint32_t u;

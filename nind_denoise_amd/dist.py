@@ -346,6 +346,23 @@ def broadcast_parameters(module, src=0, group=None):
     return flat.numel() * 4
 
 
+def broadcast_buffers(buffers, src=0, group=None):
+    """Rank `src`'s contents of every tensor of `buffers` on every rank, in place (same shapes and types everywhere; a GPU tensor
+    over gloo goes through host memory).  nn_train --resume: rank 0 read the state file, the optimizer's buffers travel from it.
+    Returns the bytes broadcast."""
+    total = 0
+    for t in buffers:
+        if dist.get_world_size(group) > 1:
+            if t.is_cuda and _host_staged(group):
+                h = t.detach().cpu()
+                dist.broadcast(h, src, group)
+                t.copy_(h)
+            else:
+                dist.broadcast(t, src, group)
+        total += t.numel() * t.element_size()
+    return total
+
+
 def average_gradients(flat, group=None):
     """Data-parallel training (BASELINE config 5): ONE all-reduce of the flat state-dict-order gradient buffer
     (124 MB fp32 for UtNet(64)), then the mean.  No-op without an initialised process group."""

@@ -19,6 +19,11 @@ UtNet, the CPU whole-image test pass (--test_interval) and clean-clean mixing (-
 Quality bar (the cure README.md:140 of the reference names for an unstable start, PickyDenoisingDatasetFromList): --min_quality Q
 trains on the pairs whose MS-SSIM is above Q, for the first --min_quality_epochs epochs or for the whole run; the scores are
 computed from the resident pool at start, or read from the csv of tools.make_dataset_crops_list with --quality_csv.
+
+Long runs: --g_clip_norm X clips the gradient by its global norm and --skip_nonfinite_steps leaves a step with a non-finite
+gradient unapplied, both decided on the device (train._GuardedStep); --max_skipped_steps N ends a run that keeps skipping.
+--save_state writes train_state.pt after every epoch and --resume RUN_DIR continues that run to the bits the uninterrupted run
+would have left (--g_model_path + --start_epoch starts a new optimisation from old weights: "cosmetics", as the reference says).
 '''
 import argparse
 import collections
@@ -42,6 +47,9 @@ DEFAULT_CONFIG_FPATH = os.path.join('configs', 'train_conf_defaults.yaml')
 DEBUG_OPTIONS = ('short_run', 'check_dataset', 'output_val_images', 'output_test_images', 'keep_all_output_images')
 MAX_GPUS = 16         # --gpus: one process per rank, and no more than 16 processes may hold a GPU open at a time
 KILL_GRACE_S = 10     # launch(): seconds between SIGTERM and SIGKILL for the ranks that outlive a failed one
+STATE_FNAME = 'train_state.pt'      # --save_state / --resume: the latest epoch's training state, in the run directory
+STATE_FORMAT = 1
+RESUME_OVERRIDES = ('epochs', 'time_limit', 'min_lr', 'log_interval')      # what the command line may set next to --resume
 
 
 class Printer:
@@ -141,6 +149,11 @@ def build_parser():
     parser.add_argument('--quality_csv', help='Take the pair scores from this csv (python -m nind_denoise_amd.tools.make_dataset_crops_list) instead of scoring the pool at start')
     parser.add_argument('--gpus', type=int, help=f'Data-parallel ranks, one process per GPU (1..{MAX_GPUS}; default 1: this process trains). Each rank takes --batch_size crops per step')
     parser.add_argument('--dist_backend', choices=('nccl', 'gloo'), help='Backend of the process group (default: nccl when every rank has a GPU of its own, else gloo: ranks share GPUs and gradients are staged through the host)')
+    parser.add_argument('--g_clip_norm', type=float, help='Clip the generator\'s gradient to this global L2 norm (torch.nn.utils.clip_grad_norm_) before every update')
+    parser.add_argument('--skip_nonfinite_steps', action='store_true', help='Do not apply an update whose gradient holds a NaN or an infinity; its loss is left out of the epoch\'s means')
+    parser.add_argument('--max_skipped_steps', type=int, help='End the run with an error after an epoch with more skipped steps than this (needs --skip_nonfinite_steps)')
+    parser.add_argument('--save_state', action='store_true', help=f'Write {STATE_FNAME} (parameters, optimizer, learning-rate rule, pool generator) into the run directory after every epoch, for --resume')
+    parser.add_argument('--resume', metavar='RUN_DIR', help=f'Continue the run of this directory from its {STATE_FNAME}: options come from its config.yaml; only {", ".join("--" + n for n in RESUME_OVERRIDES)} may be given with it')
     return parser
 
 
@@ -167,6 +180,8 @@ def parse_args(argv=None):
     for action in explicit._actions:
         action.default = argparse.SUPPRESS
     given = vars(explicit.parse_args(argv))
+    if given.get('resume') is not None:
+        return resume_args(parser, args, given)
     by_key = {}
     for action in parser._actions:
         for opt in action.option_strings:
@@ -192,6 +207,30 @@ def parse_args(argv=None):
     return args
 
 
+def resume_args(parser, defaults, given):
+    '''The options of --resume RUN_DIR: those RUN_DIR/config.yaml recorded (options the file does not know keep their defaults),
+    with RESUME_OVERRIDES from the command line.  ValueError naming any other option given beside --resume.  test_reserve comes
+    back as the list the first run expanded it to, and start_epoch as that run's: --min_quality_epochs counts from it.'''
+    for dest in given:
+        if dest != 'resume' and dest not in RESUME_OVERRIDES:
+            raise ValueError(f'--{dest} cannot be given with --resume: the options come from the run\'s config.yaml (only '
+                             f'{", ".join("--" + n for n in RESUME_OVERRIDES)} may be set)')
+    run_dir = os.path.normpath(given['resume'])
+    conf_path = os.path.join(run_dir, 'config.yaml')
+    if not os.path.isfile(conf_path):
+        raise ValueError(f'--resume {given["resume"]}: {conf_path} not found (not a run directory?)')
+    with open(conf_path, 'r') as f:
+        conf = yaml.safe_load(f) or {}
+    args = argparse.Namespace(**vars(defaults))
+    for dest, value in conf.items():
+        setattr(args, dest, value)
+    for dest, value in given.items():
+        setattr(args, dest, value)
+    args.resume = run_dir
+    args.save_state = True
+    return args
+
+
 def check_supported(args):
     '''NotImplementedError naming the first option that asks for something that is not built'''
     if args.g_network is not None and args.g_network != 'UtNet':
@@ -213,6 +252,14 @@ def check_supported(args):
                 raise ValueError(f'--{name} needs --min_quality')
     elif (args.min_quality_epochs or 0) < 0:
         raise ValueError(f'--min_quality_epochs {args.min_quality_epochs} < 0')
+    clip = getattr(args, 'g_clip_norm', None)
+    if clip is not None and not 0 < clip < float('inf'):
+        raise ValueError(f'--g_clip_norm {clip}: a positive finite norm')
+    if getattr(args, 'max_skipped_steps', None) is not None:
+        if not getattr(args, 'skip_nonfinite_steps', False):
+            raise ValueError('--max_skipped_steps needs --skip_nonfinite_steps')
+        if args.max_skipped_steps < 0:
+            raise ValueError(f'--max_skipped_steps {args.max_skipped_steps} < 0')
     unknown = set(args.debug_options) - set(DEBUG_OPTIONS)
     if unknown:
         raise ValueError(f'unknown debug options {sorted(unknown)} (available: {DEBUG_OPTIONS})')
@@ -285,9 +332,11 @@ def update_lr_on_plateau(history, lr_loss, trainer, reduce_lr_factor):
 
 
 def train_epoch(pool, trainer, batch_size, losses, ssim_losses=None, exp_mult_min=1, exp_mult_max=1, rank=0, world=1,
-                log_interval=0, log=None):
+                log_interval=0, log=None, guard_log=None):
     '''One pass over the pool (nn_train.py:308-380 without the discriminators): a batch from the pool, one generator update, the
     step's loss kept on the device in losses[k] (and, with ssim_losses, the mean SSIM loss of the step's output in ssim_losses[k]).
+    guard_log ([steps, 4] float64 on the device, for a trainer with a guarded step): row k takes the step's guard_state, and the
+    losses of a step that was not applied are stored as 0.
     Nothing here waits for the GPU except an iteration line, every log_interval steps.  Returns the number of steps.'''
     from .validation import criteria
     iteration = 0
@@ -300,6 +349,11 @@ def train_epoch(pool, trainer, batch_size, losses, ssim_losses=None, exp_mult_mi
         else:
             loss = trainer.learn(noisy, clean)
         losses[iteration - 1] = loss[0]        # stays on the device: the epoch's mean is read once
+        if guard_log is not None:
+            guard_log[iteration - 1] = trainer.guard_state
+            applied = trainer.guard_state[3] > 0
+            for kept in (losses,) if ssim_losses is None else (losses, ssim_losses):
+                kept[iteration - 1] = torch.where(applied, kept[iteration - 1], torch.zeros_like(kept[iteration - 1]))
         if log is not None and log_interval > 0 and iteration % log_interval == 0:
             log(iteration, loss.item())
     return iteration
@@ -311,6 +365,96 @@ def save_model(model, model_dir, epoch, name='generator'):
     path = os.path.join(model_dir, '%s_%u.pt' % (name, epoch))
     torch.save({k: v.detach().to('cpu', copy=True).contiguous() for k, v in model.state_dict().items()}, path)
     return path
+
+
+def file_sha256(path):
+    h = hashlib.sha256()
+    with open(path, 'rb') as f:
+        for block in iter(lambda: f.read(1 << 20), b''):
+            h.update(block)
+    return h.hexdigest()
+
+
+def guard_summary(guard_rows):
+    '''The figures of an epoch from its steps' guard states ([steps, 4] on the host: sum g^2, non-finite count, scale, ok):
+    (applied steps, skipped steps, clipped steps, mean and maximum gradient norm over the applied steps).'''
+    ok = guard_rows[:, 3] > 0
+    applied = int(ok.sum())
+    norms = guard_rows[ok, 0].sqrt()
+    clipped = int((guard_rows[ok, 2] < 1).sum())
+    mean = norms.mean().item() if applied else float('nan')
+    return applied, guard_rows.shape[0] - applied, clipped, mean, (norms.max().item() if applied else float('nan'))
+
+
+def save_train_state(model_dir, state):
+    '''train_state.pt, replaced atomically: written under a temporary name, flushed to the disk, then renamed over the old file.  A
+    failure on the way leaves the old file in place.'''
+    path = os.path.join(model_dir, STATE_FNAME)
+    tmp = path + '.tmp'
+    try:
+        with open(tmp, 'wb') as f:
+            torch.save(state, f)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+    return path
+
+
+def load_train_state(run_dir):
+    '''The state --save_state left in run_dir.  ValueError when there is none, or when a later version of the program wrote it.'''
+    path = os.path.join(run_dir, STATE_FNAME)
+    if not os.path.isfile(path):
+        raise ValueError(f'--resume {run_dir}: no {STATE_FNAME} there (the run was started without --save_state, or ended before its '
+                         'first epoch did)')
+    state = torch.load(path, map_location='cpu', weights_only=True)
+    if not isinstance(state, dict) or 'format' not in state:
+        raise ValueError(f'--resume {run_dir}: {path} is not a training state')
+    if state['format'] > STATE_FORMAT:
+        raise ValueError(f'--resume {run_dir}: {path} has format {state["format"]}, this program reads up to {STATE_FORMAT}')
+    return state
+
+
+def state_world(run_dir):
+    '''The number of ranks of the run whose state file lies in run_dir, read without reading the file's tensors (they are mapped,
+    not loaded: the launcher of a data-parallel run asks, and stays a small process).  ValueError as load_train_state.'''
+    path = os.path.join(run_dir, STATE_FNAME)
+    if not os.path.isfile(path):
+        return load_train_state(run_dir)['world']        # raises, with the words of the one refusal
+    state = torch.load(path, map_location='cpu', weights_only=True, mmap=True)
+    if not isinstance(state, dict) or 'world' not in state:
+        raise ValueError(f'--resume {run_dir}: {path} is not a training state')
+    return int(state['world'])
+
+
+def check_resumable(state, run_dir, world, pool_groups):
+    '''ValueError unless the run can go on from `state` exactly: the same number of ranks, a pool of the same groups, and, where the
+    checkpoint of the state's epoch is still there, the checkpoint the state was written beside.'''
+    if state['world'] != world:
+        raise ValueError(f'--resume {run_dir}: the state was written by a run of {state["world"]} rank(s), this one has {world}')
+    if state['pool_groups'] != pool_groups:
+        raise ValueError(f'--resume {run_dir}: the crop pool holds {pool_groups} groups, the state was written with '
+                         f'{state["pool_groups"]} (the training data changed)')
+    ckpt = os.path.join(run_dir, 'generator_%u.pt' % state['epoch'])
+    if os.path.isfile(ckpt) and file_sha256(ckpt) != state['generator_sha256']:
+        raise ValueError(f'--resume {run_dir}: {ckpt} is not the checkpoint {STATE_FNAME} was written beside (sha256 differs)')
+
+
+def restore_trainer(trainer, state, rank=0, group=None):
+    '''The trainer as the state file's run left it.  group: rank 0 holds the whole state; its scalars reach the other ranks as one
+    object and its four buffers (parameters, m, v, vmax) by broadcast, straight into each trainer's own buffers.'''
+    if group is None:
+        trainer.load_state_dict(state['trainer'])
+        return
+    from .dist import broadcast_buffers
+    buffers = ('flat', 'm', 'v', 'vmax')
+    small = from_rank0({k: v for k, v in state['trainer'].items() if k not in buffers} if rank == 0 else None, group)
+    # (a rank other than 0 checks and takes the scalars against its own buffers, which the broadcast then fills)
+    trainer.load_state_dict(state['trainer'] if rank == 0 else dict(small, **{k: getattr(trainer, k) for k in buffers}))
+    broadcast_buffers([getattr(trainer, k) for k in buffers], 0, group)
 
 
 def make_expname(argv):
@@ -370,6 +514,17 @@ class _NoResults:
     def add_res(self, *args, **kwargs):
         pass
 
+    def write(self):
+        pass
+
+
+def record_figures(jsonsaver, epoch, figures):
+    '''Figures of an epoch that are no score: they go into the epoch's entry of trainres.json (written with the entry's next write)
+    and stay out of best_epoch / best_val, so checkpoint pruning, which keeps the best epochs, does not keep the epoch with the
+    smallest gradient norm or the fewest clipped steps.'''
+    if isinstance(jsonsaver, json_saver.JSONSaver):
+        jsonsaver.results.setdefault(epoch, dict()).update(figures)
+
 
 # ------------------------------------------------------------------ the run
 def run(args, process_group=None, argv=None):
@@ -397,10 +552,25 @@ def run(args, process_group=None, argv=None):
         rank, world = tdist.get_rank(process_group), tdist.get_world_size(process_group)
 
     # one run directory, and rank 0 owns every file in it: the other ranks print to stdout under their rank and record nothing
+    resume_dir = getattr(args, 'resume', None)
+    guard_on = getattr(args, 'g_clip_norm', None) is not None or bool(getattr(args, 'skip_nonfinite_steps', False))
+    save_state = bool(getattr(args, 'save_state', False)) or resume_dir is not None
     expname = args.expname if args.expname else make_expname(argv)
     if world > 1:
         expname = from_rank0(expname, process_group)
-    model_dir = os.path.join(args.models_dpath, expname)
+    model_dir = resume_dir if resume_dir is not None else os.path.join(args.models_dpath, expname)
+    state = None
+    if resume_dir is not None:      # rank 0 reads the state file; what the other ranks need of it is broadcast below
+        refusal = None
+        if rank == 0:
+            try:
+                state = load_train_state(resume_dir)
+            except ValueError as e:
+                refusal = str(e)
+        if world > 1:               # every rank raises rank 0's refusal, none is left waiting for a broadcast
+            refusal = from_rank0(refusal, process_group)
+        if refusal is not None:
+            raise ValueError(refusal)
     if rank == 0:
         os.makedirs(model_dir, exist_ok=True)
         jsonsaver = json_saver.JSONSaver(os.path.join(model_dir, 'trainres.json'), step_type='epoch')
@@ -410,7 +580,8 @@ def run(args, process_group=None, argv=None):
         p = Printer(tofile=False, prefix=f'[rank {rank}] ', flush=True)
     p.print(args)
     p.print('cmd: python3 ' + ' '.join(argv))
-    args.test_reserve = get_test_reserve_list(args.test_reserve)
+    if resume_dir is None:          # (a resumed run's list comes from config.yaml, already expanded)
+        args.test_reserve = get_test_reserve_list(args.test_reserve)
     p.print(f'test_reserve: {args.test_reserve}')
     torch.manual_seed(args.seed)
 
@@ -430,7 +601,13 @@ def run(args, process_group=None, argv=None):
         pool.keep_groups(3 * args.batch_size)
     steps = all_steps = pool.n_groups // args.batch_size // world
     p.print(f'Crop pool: {pool.n_groups} groups, {pool.n_images} images, {pool.nbytes / 1e6:.1f} MB in HBM; {steps} steps per epoch')
-    if args.min_quality is not None:        # every rank scores its own identical pool: the kernels are deterministic
+    if resume_dir is not None:
+        if world > 1:       # the small fields; the trainer's buffers follow once the trainer exists
+            small = from_rank0({k: v for k, v in state.items() if k != 'trainer'} if rank == 0 else None, process_group)
+            state = state if rank == 0 else small
+        check_resumable(state, resume_dir, world, pool.n_groups)
+    if args.min_quality is not None and (state is None or state['quality_bar_active']):
+        # every rank scores its own identical pool: the kernels are deterministic
         steps = set_quality_bar(pool, args.min_quality, args.quality_csv, args.batch_size, world, p.print)
     if world > 1:
         # CropPool.epoch deals batch k to rank k % world from pools with the same groups and generator state: every rank holds all
@@ -445,14 +622,21 @@ def run(args, process_group=None, argv=None):
         from .dist import broadcast_parameters
         broadcast_parameters(model, 0, process_group)
     trainer = UtNetTrainer(model, lr=args.g_lr, beta1=args.beta1, weights={k: v for k, v in weights.items() if k[0] != 'D'},
-                           device=device, process_group=process_group, loss_cs=args.loss_cs)
+                           device=device, process_group=process_group, loss_cs=args.loss_cs,
+                           max_grad_norm=getattr(args, 'g_clip_norm', None),
+                           skip_nonfinite=bool(getattr(args, 'skip_nonfinite_steps', False)))
+    if resume_dir is not None:
+        restore_trainer(trainer, state, rank, process_group if world > 1 else None)
+        pool.set_rng_state(state['pool_rng_state'])       # every rank restores its own generator: they all held this state
+        p.print(f'Resumed from {os.path.join(resume_dir, STATE_FNAME)}: epoch {state["epoch"]} done, {trainer.steps} steps, '
+                f'learning rate {trainer.lr}')
     model.train()
     want_ssim = weights['SSIM'] > 0 or args.compute_SSIM_anyway
     exp_mult_min = 1 if args.exp_mult_min is None else args.exp_mult_min
     exp_mult_max = 1 if args.exp_mult_max is None else args.exp_mult_max
 
     # Validation data
-    validation_loss = None
+    validation_loss = None if state is None else state['validation_loss']
     if args.validation_interval > 0:
         if args.validation_set_yaml is None:
             raise ValueError('nn_train: --validation_set_yaml is not set (or give --validation_interval 0)')
@@ -460,23 +644,25 @@ def run(args, process_group=None, argv=None):
 
         def get_validation_dpath(epoch):
             return os.path.join(model_dir, 'val', str(epoch)) if 'output_val_images' in args.debug_options else None
-        validation_loss, _ = validate(model, validation_set, trainer.weights, args.loss_cs, batch_size=args.val_batch_size,
-                                      output_to_dir=get_validation_dpath(0), group=process_group)
-        jsonsaver.add_res(0, {'validation_loss': validation_loss}, write=True)
-        p.print(f'Validation loss: {validation_loss}')
+        if state is None:       # (a resumed run validated before its first epoch already, and carries the last loss)
+            validation_loss, _ = validate(model, validation_set, trainer.weights, args.loss_cs, batch_size=args.val_batch_size,
+                                          output_to_dir=get_validation_dpath(0), group=process_group)
+            jsonsaver.add_res(0, {'validation_loss': validation_loss}, write=True)
+            p.print(f'Validation loss: {validation_loss}')
 
-    if rank == 0:
+    if rank == 0 and resume_dir is None:        # (a resumed run keeps the first run's file: its options are that run's)
         with open(os.path.join(model_dir, 'config.yaml'), 'w') as fp:
-            yaml.dump(vars(args), fp)
+            yaml.dump({k: v for k, v in vars(args).items() if k != 'resume'}, fp)
 
     start_time = time.time()
-    generator_loss_hist = collections.deque(maxlen=args.patience)
-    generator_learning_rate = trainer.lr
+    generator_loss_hist = collections.deque([] if state is None else state['loss_hist'], maxlen=args.patience)
+    generator_learning_rate = trainer.lr if state is None else state['gen_lr']
     losses = torch.zeros(max(all_steps, 1), dtype=torch.float32, device=device)
     ssim_losses = torch.zeros_like(losses)
+    guard_log = torch.zeros(max(all_steps, 1), 4, dtype=torch.float64, device=device) if guard_on else None
 
     # Train
-    for epoch in range(args.start_epoch, args.epochs):
+    for epoch in range(args.start_epoch if state is None else state['epoch'] + 1, args.epochs):
         epoch_start_time = time.time()
         if pool.min_quality is not None and 0 < args.min_quality_epochs <= epoch - args.start_epoch:
             pool.set_min_quality(None)
@@ -485,7 +671,15 @@ def run(args, process_group=None, argv=None):
                     f'{steps} steps per epoch')
         iteration = train_epoch(pool, trainer, args.batch_size, losses, ssim_losses if want_ssim else None, exp_mult_min,
                                 exp_mult_max, rank, world, args.log_interval,
-                                lambda it, loss: p.print('Epoch %u batch %u/%u: loss G: weighted: %.3f' % (epoch, it, steps, loss)))
+                                lambda it, loss: p.print('Epoch %u batch %u/%u: loss G: weighted: %.3f' % (epoch, it, steps, loss)),
+                                **({'guard_log': guard_log} if guard_on else {}))
+        applied = iteration
+        if guard_on and iteration > 0:
+            # the epoch's one read of the guard: under a process group every rank saw the same averaged gradients, so the same rows
+            applied, skipped, clipped, norm_mean, norm_max = guard_summary(guard_log[:iteration].cpu())
+            if args.max_skipped_steps is not None and skipped > args.max_skipped_steps:
+                raise RuntimeError(f'nn_train: epoch {epoch} skipped {skipped} of {iteration} steps for non-finite gradients, more than '
+                                   f'--max_skipped_steps {args.max_skipped_steps}; no checkpoint was saved for this epoch')
 
         # cleanup previous epochs (rank 0 alone: it saved them, and every rank has finished writing the images of earlier epochs)
         if rank == 0:
@@ -503,12 +697,22 @@ def run(args, process_group=None, argv=None):
         p.print('Epoch %u summary:' % epoch)
         p.print('Time elapsed (s): %u (epoch), %u (total)' % (time.time() - epoch_start_time, time.time() - start_time))
         p.print('Generator:')
-        if iteration > 0:
+        if iteration > 0 and applied == 0:
+            p.print(f'Generator learned nothing: all {iteration} steps were skipped for non-finite gradients')
+            record_figures(jsonsaver, epoch, {'skipped_steps': skipped, 'clipped_steps': 0})
+            jsonsaver.write()
+        elif iteration > 0:
             if world > 1:       # the mean over every rank's steps, the same bits on all ranks: the learning-rate rule reads it
                 sums = torch.stack((losses[:iteration].double().sum(), ssim_losses[:iteration].double().sum())).tolist()
-                means, _ = combine_epoch_sums(sums, iteration, process_group)
+                means, _ = combine_epoch_sums(sums, applied, process_group)
+            elif guard_on:      # the losses of skipped steps are stored as 0: the means run over the applied steps
+                means = (torch.stack((losses[:iteration].double().sum(), ssim_losses[:iteration].double().sum())) / applied).tolist()
             else:
                 means = torch.stack((losses[:iteration].double().mean(), ssim_losses[:iteration].double().mean())).tolist()
+            if guard_on:
+                p.print('Gradient norm: mean %f, max %f; clipped steps: %u, skipped steps: %u (of %u)'
+                        % (norm_mean, norm_max, clipped, skipped, iteration))
+                record_figures(jsonsaver, epoch, {'grad_norm_mean': norm_mean, 'clipped_steps': clipped, 'skipped_steps': skipped})
             if want_ssim:
                 p.print('Average SSIM loss: %f' % means[1])
                 jsonsaver.add_res(epoch, {'train_SSIM_loss': means[1]}, write=False)
@@ -527,7 +731,13 @@ def run(args, process_group=None, argv=None):
         if world > 1:
             check_agreement(trainer.flat, process_group, epoch)
         if rank == 0:
-            save_model(model, model_dir, epoch, 'generator')
+            ckpt = save_model(model, model_dir, epoch, 'generator')
+            if save_state:
+                save_train_state(model_dir, {
+                    'format': STATE_FORMAT, 'epoch': epoch, 'trainer': trainer.state_dict(), 'loss_hist': list(generator_loss_hist),
+                    'gen_lr': generator_learning_rate, 'validation_loss': validation_loss, 'pool_rng_state': pool.rng_state(),
+                    'quality_bar_active': pool.min_quality is not None, 'world': world, 'pool_groups': pool.n_groups,
+                    'generator_sha256': file_sha256(ckpt)})
         time_is_up = bool(args.time_limit and args.time_limit < time.time() - start_time)
         if world > 1 and args.time_limit:       # rank 0's clock decides: no rank may leave while the others wait in an all-reduce
             time_is_up = from_rank0(time_is_up, process_group)
@@ -642,6 +852,10 @@ def main(argv=None):
     if args.gpus is not None:
         check_gpus(args.gpus)
     ranked = world_from_environment()
+    if ranked is None and getattr(args, 'resume', None) is not None:
+        # a run that `--gpus N` started recorded `gpus: null` (launch() takes the option off every rank's command line, and rank 0
+        # writes config.yaml): the state file knows how many ranks wrote it, and that many are started again
+        args.gpus = state_world(args.resume)
     if ranked is None:
         if (args.gpus or 1) > 1:
             check_supported(args)       # refuse here what every rank would refuse

@@ -24,9 +24,86 @@ from .dist import BucketedGradientAverager
 from .networks.UtNet import UtNet, valid_cs
 
 
-class UtNetTrainer:
+class _GuardedStep:
+    """What UtNetTrainer and UNetTrainer share behind the optimizer: the guarded step and the trainer's state dict.
+
+    max_grad_norm (None: off): the gradient is clipped to this global L2 norm, torch.nn.utils.clip_grad_norm_'s coefficient.
+    skip_nonfinite: a step whose gradient holds a NaN or an infinity is not applied -- parameters, m, v and vmax keep their bits.
+    Both off: optimizer_step is one nd_adam_step launch.  Either on: nd_grad_guard + nd_adam_step_guarded on the same stream,
+    behind whatever nd_adam_step would wait for (under a process group: the averaged gradient, so every rank decides alike), and
+    `guard_state` holds four doubles on the device: sum g^2, the number of non-finite entries, the scale, ok (include/nind_hip.h).
+    Nothing is read back: `steps` counts attempts, so a skipped step still advances Adam's bias-correction index (unlike
+    torch.cuda.amp.GradScaler, which skips optimizer.step()).  The clipped gradient is never stored: self.grads and grad_of keep
+    the unclipped one."""
+    kind = None
+
+    def _init_guard(self, max_grad_norm, skip_nonfinite):
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not (0.0 < max_grad_norm < float("inf")):
+                raise ValueError(f"max_grad_norm {max_grad_norm}: a positive finite norm, or None")
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
+        self.guard_state = self._guard_ws = None
+        if self.guarded:
+            self.guard_state = torch.zeros(4, dtype=torch.float64, device=self.device)
+            self._guard_ws = torch.empty(self.lib.nd_grad_guard_workspace_bytes(self.flat.numel()), dtype=torch.uint8, device=self.device)
+
+    @property
+    def guarded(self):
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    def _adam(self):
+        """the optimizer launch(es) of one step, self.steps already advanced"""
+        adam = (self.flat.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.vmax.data_ptr(),
+                self.flat.numel(), self.lr, self.betas[0], self.betas[1], self.eps, self.steps, int(self.amsgrad))
+        if not self.guarded:
+            _lib.check(self.lib.nd_adam_step(*adam, _lib.stream_ptr(self.device)), "nd_adam_step")
+            return
+        _lib.check(self.lib.nd_grad_guard(self.grads.data_ptr(), self.grads.numel(), float(self.max_grad_norm or 0.0),
+                                          int(self.skip_nonfinite), self.guard_state.data_ptr(), self._guard_ws.data_ptr(),
+                                          self._guard_ws.numel(), _lib.stream_ptr(self.device)), "nd_grad_guard")
+        _lib.check(self.lib.nd_adam_step_guarded(*adam, self.guard_state.data_ptr(), _lib.stream_ptr(self.device)),
+                   "nd_adam_step_guarded")
+
+    def _weights_written(self):
+        raise NotImplementedError
+
+    def state_dict(self):
+        """Everything the next step reads, as CPU copies: the flat parameter buffer (UNet: with the running statistics), Adam's
+        m, v and vmax, the step count, the rate and Adam's constants, and the guard's two settings."""
+        state = {"kind": self.kind, "funit": getattr(self, "funit", None), "param_count": self.flat.numel(),
+                 "steps": self.steps, "lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "amsgrad": bool(self.amsgrad),
+                 "max_grad_norm": self.max_grad_norm, "skip_nonfinite": self.skip_nonfinite}
+        for key in ("flat", "m", "v", "vmax"):
+            state[key] = getattr(self, key).detach().to("cpu", copy=True)
+        return state
+
+    def load_state_dict(self, state):
+        """Writes `state` (state_dict of a trainer of the same network) into the existing buffers, so the module's views stay
+        valid.  ValueError for another network, funit or parameter count.  The state's max_grad_norm and skip_nonfinite REPLACE
+        this trainer's own, and guard_state is allocated anew: a reference to the old tensor no longer sees the steps."""
+        if state.get("kind") != self.kind or state.get("funit") != getattr(self, "funit", None):
+            raise ValueError(f"{self.kind}.load_state_dict: the state is of {state.get('kind')} funit {state.get('funit')}, this "
+                             f"trainer is {self.kind} funit {getattr(self, 'funit', None)}")
+        for key in ("flat", "m", "v", "vmax"):
+            t = state[key]
+            if state.get("param_count") != self.flat.numel() or tuple(t.shape) != tuple(self.flat.shape) or t.dtype != torch.float32:
+                raise ValueError(f"{self.kind}.load_state_dict: {key} holds {tuple(t.shape)} {t.dtype} (parameter count "
+                                 f"{state.get('param_count')}), this trainer {self.flat.numel()} float32 parameters")
+        with torch.no_grad():
+            for key in ("flat", "m", "v", "vmax"):
+                getattr(self, key).copy_(state[key])
+        self.steps, self.lr, self.eps, self.amsgrad = int(state["steps"]), float(state["lr"]), float(state["eps"]), bool(state["amsgrad"])
+        self.betas = (float(state["betas"][0]), float(state["betas"][1]))
+        self._init_guard(state.get("max_grad_norm"), state.get("skip_nonfinite", False))
+        self._weights_written()
+
+
+class UtNetTrainer(_GuardedStep):
+    kind = "UtNetTrainer"
+
     def __init__(self, model: UtNet, lr=1e-4, beta1=0.75, beta2=0.999, eps=1e-8, amsgrad=True,
-                 weights=None, device=None, process_group=None, loss_cs=None):
+                 weights=None, device=None, process_group=None, loss_cs=None, max_grad_norm=None, skip_nonfinite=False):
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.device.type != "cuda":
             raise RuntimeError("UtNetTrainer needs a GPU (no CPU fallback)")
@@ -67,6 +144,7 @@ class UtNetTrainer:
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         # data parallel: the gradient mean runs bucket by bucket (one per network level) under the rest of the backward pass
         self.averager = BucketedGradientAverager(self.funit, self.grads, self.group)
+        self._init_guard(max_grad_norm, skip_nonfinite)
 
     def workspace(self, h, batch, w=None):
         """Training workspace for [batch,3,h,w or h] crops (zero borders initialised once, then cached)."""
@@ -120,10 +198,10 @@ class UtNetTrainer:
     def optimizer_step(self):
         self.steps += 1
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.nd_adam_step(self.flat.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                             self.vmax.data_ptr(), self.flat.numel(), self.lr, self.betas[0], self.betas[1],
-                                             self.eps, self.steps, int(self.amsgrad), _lib.stream_ptr(self.device)),
-                       "nd_adam_step")
+            self._adam()
+        self._weights_written()
+
+    def _weights_written(self):
         # the parameters were rewritten through raw pointers (torch's version counters did not move): the inference blob the
         # module cached before this step is stale
         self.model.weights_generation += 1
@@ -178,7 +256,7 @@ def unet_flatten(model, flat, ranges):
     assert not missing, sorted(missing)
 
 
-class UNetTrainer:
+class UNetTrainer(_GuardedStep):
     """UNet training step on the GPU, with the surface of UtNetTrainer: BatchNorm on the statistics of the batch
     (nd_unet_train_forward / nd_unet_train_backward), the loss of nd_criteria_grad, Adam(amsgrad) in nd_adam_step.
 
@@ -191,10 +269,14 @@ class UNetTrainer:
     g / (|g| + eps) would turn into full steps.  Those 18 biases therefore never move.
 
     The module itself is unchanged: `model.train()(x)` still raises, `model.eval()(x)` runs on the trained parameters and running
-    statistics (the trainer drops the module's packed inference blob whenever it has written the flat buffer)."""
+    statistics (the trainer drops the module's packed inference blob whenever it has written the flat buffer).
+
+    max_grad_norm / skip_nonfinite (_GuardedStep) protect the parameter update only: a non-finite forward has already moved the
+    BatchNorm running statistics and num_batches_tracked by the time the gradient is looked at."""
+    kind = "UNetTrainer"
 
     def __init__(self, model, lr=1e-4, beta1=0.75, beta2=0.999, eps=1e-8, amsgrad=True,
-                 weights=None, device=None, process_group=None, loss_cs=None):
+                 weights=None, device=None, process_group=None, loss_cs=None, max_grad_norm=None, skip_nonfinite=False):
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.device.type != "cuda":
             raise RuntimeError("UNetTrainer needs a GPU (no CPU fallback)")
@@ -228,6 +310,7 @@ class UNetTrainer:
         self._ws = {}
         self._loss_ws = None
         self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._init_guard(max_grad_norm, skip_nonfinite)
 
     @property
     def flags(self):
@@ -313,11 +396,22 @@ class UNetTrainer:
         self.steps += 1
         with torch.cuda.device(self.device):
             # running statistics: gradient and moments 0 -> an update of exactly 0, the slots keep their bits
-            _lib.check(self.lib.nd_adam_step(self.flat.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                             self.vmax.data_ptr(), self.flat.numel(), self.lr, self.betas[0], self.betas[1],
-                                             self.eps, self.steps, int(self.amsgrad), _lib.stream_ptr(self.device)),
-                       "nd_adam_step")
+            self._adam()
+        self._weights_written()
+
+    def _weights_written(self):
         self.model._packed = None      # written through raw pointers: see forward
+
+    def state_dict(self):
+        state = super().state_dict()
+        state["num_batches_tracked"] = [int(t) for t in self._tracked]      # the one piece of BatchNorm state outside the flat buffer
+        return state
+
+    def load_state_dict(self, state):
+        super().load_state_dict(state)
+        with torch.no_grad():
+            for t, value in zip(self._tracked, state["num_batches_tracked"]):
+                t.fill_(value)
 
     def learn(self, noisy, clean):
         """One generator update; returns the loss as a float tensor."""

@@ -15,7 +15,13 @@ Images are seeded noise: none of the kernels' traffic depends on the picture.
 
 runs the data-parallel leg instead: this process stays off the GPU and starts N ranks of this file (nn_train.launch); every rank
 times (a)'s epoch loop at `batch` crops per rank with the bucketed gradient mean, and validation.validate sharded over the ranks.
-With more ranks than GPUs the ranks share cards over gloo: a rehearsal, not a scaling figure (profiles/nn_train_dp.json)."""
+With more ranks than GPUs the ranks share cards over gloo: a rehearsal, not a scaling figure (profiles/nn_train_dp.json).
+
+    python tools/bench_nn_train.py --g_clip_norm X [--skip_nonfinite_steps] --out profiles/train_guard.json
+
+runs the guard leg instead: (a)'s epoch loop with a plain trainer and with a guarded one in alternating windows, nd_grad_guard and
+the two optimizer launches alone (device events; the guard's share of the HBM rate from the bytes it reads), and the seconds one
+train_state.pt takes to write."""
 import argparse
 import json
 import os
@@ -101,6 +107,118 @@ def data_parallel_leg(args, ranked):
         tdist.destroy_process_group()
 
 
+def guard_leg(args, dev, pool, steps):
+    """--g_clip_norm: what the guarded step costs in the epoch loop and on its own, and what the state file costs per epoch"""
+    import tempfile
+    from nind_denoise_amd import _lib
+    weights = {"MSSSIM": 1.0}
+    trainers = {}
+    for name, kw in (("plain", {}), ("guarded", {"max_grad_norm": args.g_clip_norm, "skip_nonfinite": args.skip_nonfinite_steps})):
+        net = UtNet(funit=args.funit)
+        net.load_state_dict(synth.make_utnet_state_dict(args.funit, seed=123))
+        trainers[name] = UtNetTrainer(net, lr=1e-4, beta1=0.75, device=dev, weights=weights, loss_cs=args.cs, **kw)
+    losses = torch.zeros(steps, device=dev)
+    guard_log = torch.zeros(steps, 4, dtype=torch.float64, device=dev)
+
+    def window(name):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        extra = {"guard_log": guard_log} if name == "guarded" else {}
+        n = nn_train.train_epoch(pool, trainers[name], args.batch, losses, None, 0.85, 1.15, log_interval=50, log=lambda it, loss: None, **extra)
+        mean = losses[:n].double().mean().item()                # the epoch's one synchronisation
+        summary = nn_train.guard_summary(guard_log[:n].cpu()) if extra else None
+        return time.perf_counter() - t0, n, mean, summary
+    for tr in trainers.values():
+        for _ in range(args.warmup):
+            tr.learn(*reversed(pool.batch(pool.draw(args.batch), exp_mult_min=0.85, exp_mult_max=1.15)))
+    rates, summary = {"plain": [], "guarded": []}, None
+    for _ in range(args.rounds):                                 # alternating windows: both see the same machine
+        for name in rates:
+            dt, n, mean, got = window(name)
+            rates[name].append(round(args.batch * n / dt, 2))
+            summary = got or summary
+    median = {k: sorted(v)[len(v) // 2] for k, v in rates.items()}
+
+    # the launches alone
+    tr, lib, sp = trainers["guarded"], _lib.load(), _lib.stream_ptr(dev)
+    adam = (tr.flat.data_ptr(), tr.grads.data_ptr(), tr.m.data_ptr(), tr.v.data_ptr(), tr.vmax.data_ptr(), tr.flat.numel(), 0.0, 0.75,
+            0.999, 1e-8, 10, 1)                                  # lr 0: the parameters stay where they are
+    calls = {
+        "nd_grad_guard": lambda: lib.nd_grad_guard(tr.grads.data_ptr(), tr.grads.numel(), args.g_clip_norm, int(args.skip_nonfinite_steps),
+                                                   tr.guard_state.data_ptr(), tr._guard_ws.data_ptr(), tr._guard_ws.numel(), sp),
+        "nd_adam_step": lambda: lib.nd_adam_step(*adam, sp),
+        "nd_adam_step_guarded": lambda: lib.nd_adam_step_guarded(*adam, tr.guard_state.data_ptr(), sp),
+    }
+    ms = {}
+    for name, call in calls.items():
+        for _ in range(10):
+            _lib.check(call(), name)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        torch.cuda.synchronize()
+        ev[0].record()
+        for _ in range(args.iters):
+            call()
+        ev[1].record()
+        torch.cuda.synchronize()
+        ms[name] = round(ev[0].elapsed_time(ev[1]) / args.iters, 5)
+    grad_bytes = tr.grads.numel() * 4
+    # the guard's pass from HBM: copies of the gradient buffer taken in turn, together over four times the 256 MiB Infinity Cache, so
+    # no call finds its buffer cached (measuring: a rate from a cache-resident buffer is no HBM rate)
+    copies = [tr.grads.clone() for _ in range(max(2, -(-4 * 256 * 2 ** 20 // grad_bytes)))]
+
+    def rotated(k):
+        g = copies[k % len(copies)]
+        return lib.nd_grad_guard(g.data_ptr(), g.numel(), args.g_clip_norm, int(args.skip_nonfinite_steps), tr.guard_state.data_ptr(),
+                                 tr._guard_ws.data_ptr(), tr._guard_ws.numel(), sp)
+    for k in range(len(copies)):
+        _lib.check(rotated(k), "nd_grad_guard")
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    torch.cuda.synchronize()
+    ev[0].record()
+    for k in range(args.iters):
+        rotated(k)
+    ev[1].record()
+    torch.cuda.synchronize()
+    hbm_ms = ev[0].elapsed_time(ev[1]) / args.iters
+    del copies
+
+    # the state file
+    write_s = []
+    with tempfile.TemporaryDirectory() as tmp:
+        for _ in range(args.rounds):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            path = nn_train.save_train_state(tmp, {"format": nn_train.STATE_FORMAT, "epoch": 1, "trainer": tr.state_dict(),
+                                                   "pool_rng_state": pool.rng_state()})
+            write_s.append(round(time.perf_counter() - t0, 4))
+        state_bytes = os.path.getsize(path)
+    result = {
+        "device": torch.cuda.get_device_name(0),
+        "config": {"groups": args.groups, "source": f"{args.side}x{args.side} u8 pairs", "cs": args.cs, "batch": args.batch,
+                   "steps_per_epoch": steps, "rounds": args.rounds, "funit": args.funit, "weights": weights, "exp_mult": [0.85, 1.15],
+                   "g_clip_norm": args.g_clip_norm, "skip_nonfinite_steps": args.skip_nonfinite_steps, "iters": args.iters},
+        "epoch_loop": {"crops_per_s_windows": rates, "crops_per_s_median": median,
+                       "guarded_over_plain": round(median["guarded"] / median["plain"], 4),
+                       "last_guarded_epoch": dict(zip(("applied", "skipped", "clipped", "grad_norm_mean", "grad_norm_max"), summary))},
+        "launches_ms_per_call": dict(ms, gradient_bytes=grad_bytes,
+                                     nd_grad_guard_GB_per_s=round(grad_bytes / ms["nd_grad_guard"] / 1e6, 1),
+                                     note="back-to-back calls on one buffer of %.0f MB: smaller than the 256 MB last-level cache, so the "
+                                          "rate is an upper bound on what a step sees" % (grad_bytes / 1e6),
+                                     nd_grad_guard_from_hbm={
+                                         "ms_per_call": round(hbm_ms, 5), "GB_per_s": round(grad_bytes / hbm_ms / 1e6, 1),
+                                         "share_of_8000_GB_per_s_spec": round(grad_bytes / hbm_ms / 1e6 / 8000, 3),
+                                         "share_of_6290_GB_per_s_float4_copy": round(grad_bytes / hbm_ms / 1e6 / 6290, 3),
+                                         "how": "buffers of %.0f MB taken in turn, over 1 GiB together (4 x the 256 MiB cache); both "
+                                                "launches of the call timed" % (grad_bytes / 1e6)}),
+        "state_file": {"write_s": write_s, "bytes": state_bytes},
+    }
+    print(json.dumps(result))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1, help="> 1: the data-parallel leg alone, one fresh process per rank")
@@ -116,6 +234,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--funit", type=int, default=64)
     ap.add_argument("--out", default=os.path.join("profiles", "nn_train.json"))
+    ap.add_argument("--g_clip_norm", type=float, help="the guard leg alone: the epoch loop with and without nn_train's --g_clip_norm")
+    ap.add_argument("--skip_nonfinite_steps", action="store_true", help="with --g_clip_norm: the guarded trainer also skips non-finite steps")
     args = ap.parse_args()
     ranked = nn_train.world_from_environment()
     if ranked is not None:
@@ -132,6 +252,8 @@ def main():
         pool.add_group([clean], [clean ^ rng.integers(0, 16, clean.shape, dtype=np.uint8)])
     pool.device_buffers()
     steps = args.groups // args.batch
+    if args.g_clip_norm is not None:
+        return guard_leg(args, dev, pool, steps)
 
     # ---- (a) the epoch loop against the resident step
     net = UtNet(funit=args.funit)
