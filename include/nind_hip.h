@@ -571,6 +571,25 @@ int nd_crop_batch(const void *pool, size_t pool_bytes, const int64_t *images, in
  * outside [1, 16384]. */
 int nd_pool_fetch(const void *pool, size_t pool_bytes, const int64_t *images, int n_images, const int32_t *index, int n, int h, int w,
                   float *out_nchw, void *stream);
+/* The same two calls on a pool of whole frames, each stored once, whose images are windows into them (crop_pool.CropPool.from_full_size:
+ * the crops of the reference's tools/crop_img.sh without the crop files).  `windows` is a table in HBM of eight int64 per image:
+ *   {byte offset of the parent into the pool (a multiple of the sample size), H, W, nd_sample_type, y, x, PH, PW}
+ * The parent is planar [3][PH][PW] at the offset; the image is its rows [y, y + H) x columns [x, x + W) in each plane, so sample
+ * (c, i, j) of the image is sample c * PH * PW + (y + i) * PW + (x + j) of the parent: the row pitch is PW and the plane pitch PH * PW,
+ * in samples.  The first four columns are those of the dense table, with the offset naming the parent.
+ * Everything said above holds with "the image" meaning the window: conversion, centred zero padding of a side shorter than cs, the
+ * cut at x0 / y0, orientation, xmax (the maximum over the window's part of the crop, not over the parent's) and the multiplier; and
+ * a pixel outside the window reads as 0 even where the parent holds data there, so padding is zeros as it is for a crop file.
+ * nd_crop_batch_windows on a window table gives, bit for bit, what nd_crop_batch gives on a dense pool of the cut-out windows.
+ * Guards, on the device: an index outside the table, a bad type or alignment, a negative y or x, a window that does not lie inside
+ * its parent (y + H > PH or x + W > PW), or a parent that does not lie inside the pool gives zero samples; for
+ * nd_pool_fetch_windows a row of another size than h x w does too.  Nothing is read out of range, whatever the table or the draws
+ * hold.  Stream-ordered; allocates nothing.  ND_EINVAL as for the dense forms. */
+int nd_crop_batch_windows(const void *pool, size_t pool_bytes, const int64_t *windows, int n_windows, const int32_t *draws, int batch,
+                          int cs, float exp_mult_min, float exp_mult_max, const float *mult, float *xmax, float *mult_out,
+                          float *clean_nchw, float *noisy_nchw, void *stream);
+int nd_pool_fetch_windows(const void *pool, size_t pool_bytes, const int64_t *windows, int n_windows, const int32_t *index, int n,
+                          int h, int w, float *out_nchw, void *stream);
 
 /* ---- Winograd forms of a 3x3 layer, fp32 inference (same math as nd_layer_forward on a CONV3 / CONVT3 layer, re-associated).
  * tile = 2 | 4 | 6: three-pass F(tile x tile, 3 x 3) (input transform, one launch of (tile+2)^2 GEMMs, output transform;

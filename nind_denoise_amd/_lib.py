@@ -152,6 +152,8 @@ _SIGNATURES = {
     "nd_crop_source": (c_int, [c_int] * 5 + [POINTER(c_int)] * 2),
     "nd_crop_batch": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_float] + [c_void_p] * 6),
     "nd_pool_fetch": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "nd_crop_batch_windows": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_float] + [c_void_p] * 6),
+    "nd_pool_fetch_windows": (c_int, [c_void_p, c_size_t, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "nd_num_conv_variants": (c_int, []),
     "nd_conv_variant_name": (c_char_p, [c_int]),
 }

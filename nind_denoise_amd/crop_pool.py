@@ -14,6 +14,10 @@ Quality bar (DenoisingDataset.list_content_quality and the docstring of PickyDen
 score_pairs() gives the MS-SSIM of every (clean, noisy) pair of the resident files, list_content_quality() writes the reference's
 csv, and after set_min_quality(q) draws take only pairs whose score is above q.
 
+Without the pre-cropped dataset: CropPool.from_full_size reads the full-size images, keeps each once in HBM as a frame, and makes
+of every crop the reference's cropper would have written (crop_grid: tools/crop_img.sh) a window into its frame.  Groups, draws,
+batches and scores are those of the pool of crop files, bit for bit (nd_crop_batch_windows, nd_pool_fetch_windows).
+
 Not built: the sigmamin / sigmamax artificial noise and the JPEG re-compression branch of the reference's __getitem__ (the first is
 "rarely used / experimental" by its docstring, the second calls .save on a numpy array).
 """
@@ -52,6 +56,61 @@ def _to_chw(img):
     raise ValueError(f"CropPool: expected an HWC or CHW image, got shape {img.shape}")
 
 
+def _tdiv(a, b):
+    """a / b as bash's $(( )) divides: towards zero"""
+    q = abs(a) // abs(b)
+    return q if (a < 0) == (b < 0) else -q
+
+
+def crop_grid(width, height, cs, stride):
+    """(xcrop, ycrop, xbeg, ybeg) of every crop the reference's cropper writes for a width x height image, in its loop's order
+    (rows outer): the arithmetic of tools/crop_img.sh:28-64 as it stands.  The crop is the cs x cs rectangle at (xbeg, ybeg), and its
+    file is <basename>_<xcrop>_<ycrop>_<stride>.<ext>.  The loop runs over width / stride + 1 columns and height / stride + 1 rows; a
+    crop is written only when it is a full cs x cs, its origin is not negative and its useful size is at least stride, so the first
+    column and row (cs - (cs - stride) / 2 wide, unless cs == stride) and the last ones (cut by the image's edge) never are: the
+    first crop starts at stride - (cs - stride) / 2, and an image with a side below that plus cs yields nothing.  ValueError unless
+    cs and stride are non-negative multiples of 8, where the script exits."""
+    for name, v in (("cs", cs), ("stride", stride)):
+        if isinstance(v, bool) or int(v) != v or v < 0 or v % 8:
+            raise ValueError(f"crop_grid: {name} {v!r} is an invalid crop size, must be a multiple of 8")
+    cs, stride, width, height = int(cs), int(stride), int(width), int(height)
+    if stride == 0:
+        raise ValueError("crop_grid: stride 0 (the script divides by it)")
+    margin = _tdiv(cs - stride, 2)
+    nx, ny = _tdiv(width, stride) + 1, _tdiv(height, stride) + 1
+    crops = []
+    for cury in range(ny):
+        for curx in range(nx):
+            xcs = ycs = cs
+            cucs = stride
+            xbeg, ybeg = curx * stride - margin, cury * stride - margin
+            if curx == 0:
+                xcs, xbeg = cs - margin, 0
+            if cury == 0:
+                ycs, ybeg = cs - margin, 0
+            xcs, ycs = min(xcs, width - xbeg), min(ycs, height - ybeg)
+            if curx == nx - 1:
+                cucs = xcs - margin
+            if cury == ny - 1:
+                cucs = min(cucs, ycs - margin)
+            if xbeg >= 0 and ybeg >= 0 and cucs >= stride and ycs == cs and xcs == cs:
+                # every written crop's name ends in _<stride>: another useful size needs a last column or row that is a full cs,
+                # and there width % stride + (cs - stride) / 2 < cs
+                crops.append((curx, cury, xbeg, ybeg))
+    return crops
+
+
+def findisoval(fn):
+    """The ISO value of a full-size file name as the reference's cropper finds it (tools/crop_ds.py:32-39); None if it has none."""
+    for part in fn.split('_'):          # the first part that says ISO, GT or NOISY decides
+        if 'ISO' in part:
+            return part.split('.')[0]
+        for word in ('GT', 'NOISY'):    # from the word to the first dot, underscores included
+            if word in part:
+                return fn[fn.find(word):].split('.')[0]
+    return None
+
+
 class Draws:
     """One batch of draws a pool made itself: valid by construction, so CropPool.batch takes it without looking at its values."""
 
@@ -69,7 +128,10 @@ class CropPool:
         self.generator = torch.Generator(device=self.device)
         self.generator.manual_seed(seed)
         self._staged = []        # host arrays not yet uploaded
-        self._images = []        # (byte offset, H, W, sample type) per image
+        self._images = []        # (byte offset, H, W, sample type) per image; in a pool of windows (byte offset of the frame, H, W,
+        #                          sample type, y, x, frame H, frame W): the rows of the two table formats of nd_crop_batch
+        self._frames = None      # a pool of windows: (byte offset, H, W, sample type) per frame; None: a pool of dense images
+        self._image_frame = []   # a pool of windows: the frame of each image
         self.sets = []           # from_directories: (datadir, set, crop file, base ISOs, other ISOs) per group
         self.datadirs = None     # from_directories: the directories as given
         self.scores = None       # score_pairs: [pairs] fp32 on the device, in pair order
@@ -94,6 +156,9 @@ class CropPool:
         two lists hold the same arrays (a clean-clean entry) they are uploaded once.  Returns the group's index."""
         if self._pool is not None:
             raise RuntimeError("CropPool: the pool was uploaded by its first batch; add every group before that")
+        if self._frames is not None:
+            raise ValueError("CropPool.add_group: this pool holds frames and windows (add_frame); a pool holds either dense images "
+                             "or windows, not both")
         if not len(clean_images) or not len(noisy_images):
             raise ValueError("CropPool.add_group: a group needs at least one clean and one noisy image")
         clean_images, noisy_images = list(clean_images), list(noisy_images)
@@ -111,15 +176,83 @@ class CropPool:
         self._gt = self.scores = self.pairs = self.min_quality = self._bar = None
         return len(self._groups) - 1
 
+    def add_frame(self, chw):
+        """A whole image, stored once, for add_window_group to take windows from (HWC, CHW or HW samples).  Returns the frame's
+        index.  A pool holds either dense images (add_group) or frames and windows, not both: ValueError."""
+        if self._pool is not None:
+            raise RuntimeError("CropPool: the pool was uploaded by its first batch; add every frame before that")
+        if self._frames is None:
+            if self._images:
+                raise ValueError("CropPool.add_frame: this pool holds dense images (add_group); a pool holds either dense images or "
+                                 "windows, not both")
+            self._frames = []
+        chw = _to_chw(chw)
+        off = self._bytes
+        self._staged.append((off, chw))
+        self._frames.append((off, chw.shape[1], chw.shape[2], _TYPES[chw.dtype]))
+        self._bytes = (off + chw.nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
+        return len(self._frames) - 1
+
+    def add_window_group(self, clean_frames, noisy_frames, y, x, h, w):
+        """A group whose images are rows [y, y + h) x columns [x, x + w) of each named frame (indices add_frame gave): what add_group
+        makes of that rectangle cut out of each, without a second copy of its samples.  When the two lists are equal (a clean-clean
+        entry) the images are shared.  ValueError unless the rectangle lies inside every frame.  Returns the group's index."""
+        if self._pool is not None:
+            raise RuntimeError("CropPool: the pool was uploaded by its first batch; add every group before that")
+        if self._frames is None:
+            raise ValueError("CropPool.add_window_group: the pool has no frame (add_frame first; a pool of dense images takes no windows)")
+        clean_frames, noisy_frames = [int(f) for f in clean_frames], [int(f) for f in noisy_frames]
+        if not clean_frames or not noisy_frames:
+            raise ValueError("CropPool.add_window_group: a group needs at least one clean and one noisy frame")
+        y, x, h, w = int(y), int(x), int(h), int(w)
+        for f in clean_frames + noisy_frames:
+            if not 0 <= f < len(self._frames):
+                raise ValueError(f"CropPool.add_window_group: frame {f} outside [0, {len(self._frames)})")
+            _, fh, fw, _ = self._frames[f]
+            if h < 1 or w < 1 or y < 0 or x < 0 or y + h > fh or x + w > fw:
+                raise ValueError(f"CropPool.add_window_group: the {h} x {w} window at ({y}, {x}) does not lie inside frame {f} "
+                                 f"({fh} x {fw})")
+
+        def add(frames):        # consecutive rows of the table, like the images of a dense group
+            first = len(self._images)
+            for f in frames:
+                off, fh, fw, typ = self._frames[f]
+                self._images.append((off, h, w, typ, y, x, fh, fw))
+                self._image_frame.append(f)
+            return first
+
+        c0 = add(clean_frames)
+        n0 = c0 if clean_frames == noisy_frames else add(noisy_frames)
+        self._groups.append((c0, len(clean_frames), n0, len(noisy_frames), h, w))
+        self._gt = self.scores = self.pairs = self.min_quality = self._bar = None
+        return len(self._groups) - 1
+
+    def _keep_window_groups(self, count):
+        groups, staged = self._groups[:count], dict(self._staged)
+        used = sorted({self._image_frame[i] for c0, nc, n0, nn, _, _ in groups for i0, cnt in ((c0, nc), (n0, nn))
+                       for i in range(i0, i0 + cnt)})
+        arrays = {f: staged[self._frames[f][0]] for f in used}
+        old_images, old_frame = self._images, self._image_frame
+        self._staged, self._images, self._image_frame, self._frames, self._groups, self._bytes = [], [], [], [], [], 0
+        renumbered = {f: self.add_frame(arrays[f]) for f in used}             # the frames still named, in their old order
+        for c0, nc, n0, nn, h, w in groups:
+            _, _, _, _, y, x, _, _ = old_images[c0]
+            self.add_window_group([renumbered[old_frame[i]] for i in range(c0, c0 + nc)],
+                                  [renumbered[old_frame[i]] for i in range(n0, n0 + nn)], y, x, h, w)
+
     def keep_groups(self, count):
         """Drops every group past the first `count` (debug option short_run: DDataset.dataset[:3 * batch_size], nn_train.py:225-226),
-        and with them the images no remaining group names.  Only before the first upload."""
+        and with them the images, or in a pool of windows the frames, no remaining group names.  Only before the first upload."""
         if self._pool is not None:
             raise RuntimeError("CropPool: the pool was uploaded by its first batch; drop groups before that")
         if count < 0:
             raise ValueError(f"CropPool.keep_groups: count {count}")
         if count >= len(self._groups):
             return
+        if self._frames is not None:
+            self.sets = self.sets[:count]
+            self._gt = self.scores = self.pairs = self.min_quality = self._bar = None
+            return self._keep_window_groups(count)
         groups, staged = self._groups[:count], dict(self._staged)
         arrays = [staged[off] for off, _, _, _ in self._images]
         self.sets = self.sets[:count]
@@ -180,10 +313,103 @@ class CropPool:
                     pool.sets.append((datadir, aset, animg, tuple(bisos), tuple(isos)))
         return pool
 
+    @classmethod
+    def from_full_size(cls, dsdirs, ds_cs=256, ds_stride=192, test_reserve=(), exact_reserve=False, device=None, seed=0, cs=None,
+                       crops_dir=None):
+        """The pool from_directories would make of the tree the reference's cropper (tools/crop_ds.py --cs ds_cs --stride ds_stride,
+        which runs tools/crop_img.sh on every image) writes for the full-size dataset <dsdir>/<set>/<image files>, without that
+        tree: every image of a set that is not reserved is read once and uploaded once as a frame, and every crop is a window into
+        its frame.  Groups and their order, sets, pair_paths() and dsname are those of the cropped tree at crops_dir (default: the
+        cropper's own <root of dsdir>/cropped/<leaf of dsdir>_<ds_cs>_<ds_stride>; one path per dsdir): sets in sorted order, the ISO
+        of a file as the cropper finds it (findisoval), base and other ISOs by sortISOs, one group per crop file name of the first
+        noisy ISO in sorted file-name order, <basename>_<xcrop>_<ycrop>_<ds_stride>.<ext> (crop_grid), the crop of another ISO
+        named by the same replacement of the ISO in that name.  When an ISO's own image size does not yield that crop,
+        FileNotFoundError names the crop file that would be missing, as from_directories raises it on the cropped tree.  A set
+        whose images yield no crop contributes nothing.  cs defaults to ds_cs.
+
+        Where this differs from the cropper.  A second file of a set with an ISO value already seen is the ISO <iso>-2, a third
+        <iso>-2-2, in sorted file order, and its crops are named as if the file had been renamed so; the cropper renames the user's
+        files on disk, in directory order.  This pool renames nothing.  JPEG sources are decoded like any other file: equality with a
+        jpegtran-cropped tree is not claimed, since a decoder upsamples chroma differently at the border of a crop file than inside
+        the whole image.  For PNG and TIFF a crop file is a rectangle of its image, and the pools are equal bit for bit."""
+        if isinstance(dsdirs, (str, os.PathLike)):
+            dsdirs = [dsdirs]
+        dsdirs = [os.fspath(d) for d in dsdirs]
+        if crops_dir is None:
+            crops_dirs = [os.path.join(utilities.get_root(d), 'cropped', f'{utilities.get_leaf(d)}_{ds_cs}_{ds_stride}') for d in dsdirs]
+        else:
+            crops_dirs = [os.fspath(crops_dir)] if isinstance(crops_dir, (str, os.PathLike)) else [os.fspath(d) for d in crops_dir]
+            if len(crops_dirs) != len(dsdirs):
+                raise ValueError(f"CropPool.from_full_size: {len(crops_dirs)} crops_dir for {len(dsdirs)} dataset directories")
+        crop_grid(0, 0, ds_cs, ds_stride)         # refuses the sizes the script refuses, before any file is read
+        pool = cls(device, seed=seed, cs=int(ds_cs) if cs is None else cs)
+        pool.datadirs = crops_dirs
+        pool._frames = []
+
+        def reserved(aset):
+            if exact_reserve:
+                return aset in test_reserve
+            return any(s in aset for s in test_reserve)
+
+        for dsdir, datadir in zip(dsdirs, crops_dirs):
+            for aset in sorted(os.listdir(dsdir)):
+                if reserved(aset):
+                    continue
+                files = {}                        # ISO -> (path, the name the cropper would have cropped it under)
+                for image in sorted(os.listdir(os.path.join(dsdir, aset))):
+                    iso = old = findisoval(image)
+                    if iso is None:
+                        raise ValueError(f"CropPool.from_full_size: {os.path.join(dsdir, aset, image)} names no ISO value "
+                                         "(ISO<value>, GT... or NOISY... between underscores)")
+                    while iso in files:
+                        iso += '-2'
+                    files[iso] = (os.path.join(dsdir, aset, image), image.replace(old, iso))
+                if not files:
+                    continue
+                bisos, isos = sortISOs(sorted(files))
+                if not isos:
+                    raise ValueError(f"CropPool.from_full_size: {os.path.join(dsdir, aset)} has no noisy ISO image")
+                samples, crops = {}, {}           # ISO -> its image; ISO -> {crop file name: (xbeg, ybeg)}
+                for iso in bisos + isos:
+                    fpath, name = files[iso]
+                    try:
+                        samples[iso] = np_imgops.img_path_to_np_samples(fpath)
+                    except FileNotFoundError:
+                        raise
+                    except Exception as e:
+                        raise ValueError(f"CropPool.from_full_size: cannot read {fpath}: {e}") from e
+                    _, h, w = samples[iso].shape
+                    stem, ext = name[:-4], name.lower()[-3:]     # crop_img.sh:9-10, 26
+                    crops[iso] = {f'{stem}_{xc}_{yc}_{ds_stride}.{ext}': (xb, yb) for xc, yc, xb, yb in crop_grid(w, h, ds_cs, ds_stride)}
+                if not crops[isos[0]]:
+                    continue
+                frames = {iso: pool.add_frame(samples[iso]) for iso in bisos + isos}
+                del samples
+                for animg in sorted(crops[isos[0]]):
+                    xb, yb = crops[isos[0]][animg]
+                    for iso in isos + bisos:      # the order in which from_directories opens a group's files
+                        theirs = animg.replace(isos[0] + '_', iso + '_')
+                        if theirs not in crops[iso]:
+                            raise FileNotFoundError(os.path.join(datadir, aset, iso, theirs))
+                    pool.add_window_group([frames[iso] for iso in bisos], [frames[iso] for iso in isos], yb, xb, ds_cs, ds_cs)
+                    pool.sets.append((datadir, aset, animg, tuple(bisos), tuple(isos)))
+        return pool
+
     @property
     def nbytes(self):
-        """Bytes of the pool buffer (images in their own sample type, each aligned to 16 bytes)."""
+        """Bytes of the pool buffer (images in their own sample type, each aligned to 16 bytes; in a pool of windows the frames,
+        each counted once)."""
         return self._bytes
+
+    @property
+    def windowed(self):
+        """True for a pool of frames and windows (add_frame / add_window_group, from_full_size)."""
+        return self._frames is not None
+
+    @property
+    def n_frames(self):
+        """Frames of a pool of windows; 0 for a pool of dense images."""
+        return len(self._frames) if self._frames is not None else 0
 
     @property
     def n_groups(self):
@@ -205,8 +431,15 @@ class CropPool:
 
     def image(self, i):
         """Image i as the pool holds it: a [3, H, W] numpy array of its sample type (read back from the device once uploaded)."""
-        off, h, w, typ = self._images[i]
+        off, h, w, typ = self._images[i][:4]
         dtype = [k for k, v in _TYPES.items() if v == typ][0]
+        if self._frames is not None:        # a window: its samples, cut out of the frame
+            _, _, _, _, y, x, fh, fw = self._images[i]
+            if self._pool is None:
+                frame = dict(self._staged)[off]
+            else:
+                frame = self._pool[off:off + 3 * fh * fw * dtype.itemsize].cpu().numpy().view(dtype).reshape(3, fh, fw)
+            return np.ascontiguousarray(frame[:, y:y + h, x:x + w])
         if self._pool is None:
             return dict(self._staged)[off]
         raw = self._pool[off:off + 3 * h * w * dtype.itemsize].cpu().numpy()
@@ -326,6 +559,8 @@ class CropPool:
         assert by_size.stride() == (len(table), 1)                         # rows of the kernel's index type, sliced below
         scored = torch.full((len(table),), float("nan"), dtype=torch.float32, device=self.device)
         lib = _lib.load()
+        fetch_name = "nd_pool_fetch" if self._frames is None else "nd_pool_fetch_windows"
+        fetch = getattr(lib, fetch_name)
         sorted_sizes = sizes[order]
         bounds = np.flatnonzero((np.diff(sorted_sizes, axis=0) != 0).any(axis=1)) + 1
         with torch.cuda.device(self.device):
@@ -341,9 +576,8 @@ class CropPool:
                 for k in range(int(a), int(b), n):
                     m = int(min(n, b - k))
                     for side in (0, 1):
-                        _lib.check(lib.nd_pool_fetch(pool.data_ptr(), pool.numel(), images.data_ptr(), images.shape[0],
-                                                     by_size[side, k:k + m].data_ptr(), m, h, w, x[side].data_ptr(), stream),
-                                   "nd_pool_fetch")
+                        _lib.check(fetch(pool.data_ptr(), pool.numel(), images.data_ptr(), images.shape[0],
+                                         by_size[side, k:k + m].data_ptr(), m, h, w, x[side].data_ptr(), stream), fetch_name)
                     _lib.check(lib.nd_ms_ssim(x[0].data_ptr(), x[1].data_ptr(), m, 3, h, w, scored[k:k + m].data_ptr(), ws.data_ptr(),
                                               ws.numel(), stream), "nd_ms_ssim")
         scores = torch.empty_like(scored)
@@ -354,9 +588,9 @@ class CropPool:
 
     def pair_paths(self):
         """(xpath, ypath) of every pair in pair order, formed as get_all_crop_pairs_of_paths forms them (dataset_torch_3.py:191,
-        211-212).  Only for a pool made by from_directories."""
+        211-212).  Only for a pool made by from_directories or from_full_size (there: the files of the cropped tree)."""
         if self.datadirs is None or len(self.sets) != len(self._groups):
-            raise ValueError("CropPool: file paths are known only for a pool made by from_directories")
+            raise ValueError("CropPool: file paths are known only for a pool made by from_directories or from_full_size")
         paths = []
         for datadir, aset, animg, bisos, isos in self.sets:
             base = os.path.join(datadir, aset, 'ISOBASE', animg).replace(isos[0] + '_', 'ISOBASE_')
@@ -368,7 +602,7 @@ class CropPool:
     @property
     def dsname(self):
         if self.datadirs is None:
-            raise ValueError("CropPool: a dataset name is known only for a pool made by from_directories")
+            raise ValueError("CropPool: a dataset name is known only for a pool made by from_directories or from_full_size")
         return '+'.join(utilities.get_leaf(path) for path in self.datadirs)
 
     def list_content_quality(self, export=False, out_dir='datasets'):
@@ -430,7 +664,7 @@ class CropPool:
     # ------------------------------------------------------------------ batches
     def device_buffers(self):
         """(pool bytes, image table) as nd_crop_batch takes them: a uint8 tensor and an int64 [images, 4] tensor on the device; the
-        first call uploads them."""
+        first call uploads them.  A pool of windows: the frames, and the [images, 8] table of nd_crop_batch_windows."""
         return self._upload()
 
     def _upload(self):
@@ -453,7 +687,7 @@ class CropPool:
         if t.dim() != 2 or t.shape[1] != 8 or t.shape[0] < 1 or t.dtype != torch.int32:
             raise ValueError(f"CropPool: draws must be an int32 [B, 8] table (pack_draws), got {t.dtype} {tuple(t.shape)}")
         d = t.cpu().numpy()
-        images = np.asarray(self._images, dtype=np.int64).reshape(-1, 4)
+        images = np.asarray(self._images, dtype=np.int64).reshape(len(self._images), -1)     # H, W in columns 1, 2 of both formats
         for name, col in (("clean", 0), ("noisy", 1)):
             if ((d[:, col] < 0) | (d[:, col] >= len(images))).any():
                 raise ValueError(f"CropPool: {name} image index outside [0, {len(images)})")
@@ -511,10 +745,11 @@ class CropPool:
                 raise ValueError(f"CropPool.batch: exp_mult_min {exp_mult_min} > exp_mult_max {exp_mult_max}")
             xmax, mout = torch.empty(2, n, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().nd_crop_batch(
+            name = "nd_crop_batch" if self._frames is None else "nd_crop_batch_windows"
+            _lib.check(getattr(_lib.load(), name)(
                 pool.data_ptr(), pool.numel(), images.data_ptr(), images.shape[0], table.data_ptr(), n, cs, float(exp_mult_min),
                 float(exp_mult_max), None if mult is None else mult.data_ptr(), None if xmax is None else xmax.data_ptr(),
                 None if mout is None else mout.data_ptr(), clean.data_ptr(), noisy.data_ptr(), _lib.stream_ptr(self.device)),
-                "nd_crop_batch")
+                name)
         self.last_xmax, self.last_mult = xmax, mout
         return clean, noisy

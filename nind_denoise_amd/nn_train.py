@@ -152,9 +152,36 @@ def build_parser():
     parser.add_argument('--g_clip_norm', type=float, help='Clip the generator\'s gradient to this global L2 norm (torch.nn.utils.clip_grad_norm_) before every update')
     parser.add_argument('--skip_nonfinite_steps', action='store_true', help='Do not apply an update whose gradient holds a NaN or an infinity; its loss is left out of the epoch\'s means')
     parser.add_argument('--max_skipped_steps', type=int, help='End the run with an error after an epoch with more skipped steps than this (needs --skip_nonfinite_steps)')
+    add_full_size_options(parser)
     parser.add_argument('--save_state', action='store_true', help=f'Write {STATE_FNAME} (parameters, optimizer, learning-rate rule, pool generator) into the run directory after every epoch, for --resume')
     parser.add_argument('--resume', metavar='RUN_DIR', help=f'Continue the run of this directory from its {STATE_FNAME}: options come from its config.yaml; only {", ".join("--" + n for n in RESUME_OVERRIDES)} may be given with it')
     return parser
+
+
+DS_CS, DS_STRIDE = 256, 192     # the cropper's defaults (tools/crop_ds.py:15-16)
+
+
+def add_full_size_options(parser):
+    '''--full_size_data, --ds_cs, --ds_stride (also of tools.make_dataset_crops_list).  They leave no attribute when they are not
+    given, so the result of a command line without them is what it was before they existed: read them with full_size_options.'''
+    parser.add_argument('--full_size_data', nargs='+', metavar='DIR', default=argparse.SUPPRESS,
+                        help='(space-separated) Path(s) to the full-size dataset (<DIR>/<set>/<image files>), instead of --train_data: '
+                             'its images are held whole in HBM and the crops of the cropper (tools/crop_ds.py) are windows into them')
+    parser.add_argument('--ds_cs', type=int, default=argparse.SUPPRESS, help=f'Crop size of the cropper with --full_size_data (default: {DS_CS})')
+    parser.add_argument('--ds_stride', type=int, default=argparse.SUPPRESS, help=f'Stride (useful crop size) of the cropper with --full_size_data (default: {DS_STRIDE})')
+
+
+def full_size_options(args, parser=None):
+    '''(full_size_data or None, ds_cs, ds_stride) of parsed options.  Refuses --train_data beside --full_size_data: through the
+    parser if there is one, else with ValueError.  Without --full_size_data the other two are inert.'''
+    full = getattr(args, 'full_size_data', None) or None
+    if full and args.train_data:
+        msg = '--train_data and --full_size_data are both given: the pool holds either the pre-cropped files or the full-size images'
+        if parser is not None:
+            parser.error(msg)
+        raise ValueError(msg)
+    ds_cs, ds_stride = getattr(args, 'ds_cs', None), getattr(args, 'ds_stride', None)
+    return full, DS_CS if ds_cs is None else ds_cs, DS_STRIDE if ds_stride is None else ds_stride
 
 
 def _convert(action, value):
@@ -204,6 +231,9 @@ def parse_args(argv=None):
         setattr(args, dest, value)
     if args.test_reserve is None:
         parser.error('the following arguments are required: --test_reserve (on the command line or in a config file)')
+    full, _, ds_stride = full_size_options(args, parser)
+    if full and args.loss_cs is None:       # the <UCS> of the directory the cropper would have made (nn_train.py:220-222)
+        args.loss_cs = ds_stride
     return args
 
 
@@ -542,8 +572,9 @@ def run(args, process_group=None, argv=None):
         raise RuntimeError('nn_train: no GPU visible; nind_denoise_amd has no CPU fallback')
     device = nn_common.default_device()
     argv = ['nn_train.py'] + sys.argv[1:] if argv is None else list(argv)
+    full_size_data, ds_cs, ds_stride = full_size_options(args)
     for name in ('models_dpath', 'train_data', 'batch_size', 'g_lr', 'beta1', 'patience', 'reduce_lr_factor'):
-        if getattr(args, name) is None:
+        if getattr(args, name) is None and not (name == 'train_data' and full_size_data):
             raise ValueError(f'nn_train: --{name} is not set (on the command line or in a config file)')
     weights = get_weights(args)
     rank, world = 0, 1
@@ -588,8 +619,15 @@ def run(args, process_group=None, argv=None):
     # Train data
     if not args.min_crop_size and 'check_dataset' in args.debug_options:
         args.min_crop_size = args.cs
-    pool = CropPool.from_directories(args.train_data, test_reserve=args.test_reserve, min_crop_size=args.min_crop_size or None,
-                                     cs=args.cs, device=device, seed=args.seed)
+    if full_size_data:          # (min_crop_size is inert: every window is ds_cs x ds_cs)
+        args.ds_cs, args.ds_stride = ds_cs, ds_stride       # into config.yaml, so that a resumed run rebuilds the same pool
+        pool = CropPool.from_full_size(full_size_data, ds_cs=ds_cs, ds_stride=ds_stride, test_reserve=args.test_reserve,
+                                       cs=args.cs, device=device, seed=args.seed)
+        if args.loss_cs is None:
+            args.loss_cs = ds_stride
+    else:
+        pool = CropPool.from_directories(args.train_data, test_reserve=args.test_reserve, min_crop_size=args.min_crop_size or None,
+                                         cs=args.cs, device=device, seed=args.seed)
     if args.loss_cs is None:      # the <UCS> of a directory named <DSNAME>_<CS>_<UCS> (nn_train.py:220-222)
         parts = os.path.basename(os.path.normpath(os.fspath(args.train_data[0]))).split('_')
         if len(parts) < 3 or not parts[-1].isdigit():
@@ -600,7 +638,8 @@ def run(args, process_group=None, argv=None):
     if 'short_run' in args.debug_options:
         pool.keep_groups(3 * args.batch_size)
     steps = all_steps = pool.n_groups // args.batch_size // world
-    p.print(f'Crop pool: {pool.n_groups} groups, {pool.n_images} images, {pool.nbytes / 1e6:.1f} MB in HBM; {steps} steps per epoch')
+    frames = f' (windows into {pool.n_frames} frames)' if pool.windowed else ''
+    p.print(f'Crop pool: {pool.n_groups} groups, {pool.n_images} images{frames}, {pool.nbytes / 1e6:.1f} MB in HBM; {steps} steps per epoch')
     if resume_dir is not None:
         if world > 1:       # the small fields; the trainer's buffers follow once the trainer exists
             small = from_rank0({k: v for k, v in state.items() if k != 'trainer'} if rank == 0 else None, process_group)

@@ -8,6 +8,10 @@ datasets/<dsname>-msssim.csv with the header xpath,ypath,score.
 
 egrun:
     python -m nind_denoise_amd.tools.make_dataset_crops_list --train_data datasets/train/NIND_256_192 --test_reserve configs/test_set_nind.yaml
+    python -m nind_denoise_amd.tools.make_dataset_crops_list --full_size_data datasets/NIND --test_reserve configs/test_set_nind.yaml
+
+--full_size_data DIR [--ds_cs 256 --ds_stride 192] (nn_train's options) scores the crops the cropper would cut from the full-size
+dataset, as windows into its images (CropPool.from_full_size): the csv is the one the cropped tree gives, paths and scores.
 '''
 import argparse
 import os
@@ -31,6 +35,7 @@ def build_parser():
     parser.add_argument('--min_crop_size', type=int, help='Minimum crop size. Dataset will be checked if this value is set.')
     parser.add_argument('--loss_cs', '--loss_crop_size', type=int, help='Center crop size used in loss function. default: use stride size from dataset directory name')
     parser.add_argument('--debug_options', '--debug', nargs='*', default=[], help=f'(space-separated) Debug options (available: {nn_train.DEBUG_OPTIONS})')
+    nn_train.add_full_size_options(parser)
     return parser
 
 
@@ -63,8 +68,9 @@ def parse_args(argv=None):
         setattr(args, dest, value)
     if args.test_reserve is None:
         parser.error('the following arguments are required: --test_reserve (on the command line or in a config file)')
-    if not args.train_data:
-        parser.error('the following arguments are required: --train_data (on the command line or in a config file)')
+    full, _, _ = nn_train.full_size_options(args, parser)
+    if not args.train_data and not full:
+        parser.error('the following arguments are required: --train_data or --full_size_data (on the command line or in a config file)')
     return args
 
 
@@ -78,8 +84,13 @@ def main(argv=None):
         raise RuntimeError('make_dataset_crops_list: no GPU visible; nind_denoise_amd has no CPU fallback')
     if not args.min_crop_size and 'check_dataset' in args.debug_options:
         args.min_crop_size = args.cs
-    pool = CropPool.from_directories(args.train_data, test_reserve=nn_train.get_test_reserve_list(args.test_reserve),
-                                     min_crop_size=args.min_crop_size or None, cs=args.cs, device=nn_common.default_device())
+    full, ds_cs, ds_stride = nn_train.full_size_options(args)
+    if full:
+        pool = CropPool.from_full_size(full, ds_cs=ds_cs, ds_stride=ds_stride, cs=args.cs, device=nn_common.default_device(),
+                                       test_reserve=nn_train.get_test_reserve_list(args.test_reserve))
+    else:
+        pool = CropPool.from_directories(args.train_data, test_reserve=nn_train.get_test_reserve_list(args.test_reserve),
+                                         min_crop_size=args.min_crop_size or None, cs=args.cs, device=nn_common.default_device())
     pool.device_buffers()
     torch.cuda.synchronize(pool.device)
     start = time.perf_counter()

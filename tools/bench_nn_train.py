@@ -234,6 +234,9 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--funit", type=int, default=64)
     ap.add_argument("--out", default=os.path.join("profiles", "nn_train.json"))
+    ap.add_argument("--windows", action="store_true", help="a third leg: the epoch loop fed from a pool of frames and windows holding the same crops (tools/bench_crop_pool.py --windows)")
+    ap.add_argument("--frame", default="3000x2000", help="--windows: WxH of a frame")
+    ap.add_argument("--ds_stride", type=int, default=192, help="--windows: the cropper's stride (its crop size is --side)")
     ap.add_argument("--g_clip_norm", type=float, help="the guard leg alone: the epoch loop with and without nn_train's --g_clip_norm")
     ap.add_argument("--skip_nonfinite_steps", action="store_true", help="with --g_clip_norm: the guarded trainer also skips non-finite steps")
     args = ap.parse_args()
@@ -246,11 +249,17 @@ def main():
         sys.exit("bench_nn_train needs a GPU")
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(0)
-    pool = CropPool(dev, seed=1, cs=args.cs)
-    for _ in range(args.groups):
-        clean = rng.integers(0, 256, (3, args.side, args.side), dtype=np.uint8)
-        pool.add_group([clean], [clean ^ rng.integers(0, 16, clean.shape, dtype=np.uint8)])
-    pool.device_buffers()
+    wpool = None
+    if args.windows:            # the same crops twice: cut out (pool), and as windows into their frames (wpool)
+        from bench_crop_pool import window_pools
+        pools = window_pools(args, dev)
+        pool, wpool = pools["dense"], pools["windows"]
+    else:
+        pool = CropPool(dev, seed=1, cs=args.cs)
+        for _ in range(args.groups):
+            clean = rng.integers(0, 256, (3, args.side, args.side), dtype=np.uint8)
+            pool.add_group([clean], [clean ^ rng.integers(0, 16, clean.shape, dtype=np.uint8)])
+        pool.device_buffers()
     steps = args.groups // args.batch
     if args.g_clip_norm is not None:
         return guard_leg(args, dev, pool, steps)
@@ -267,7 +276,7 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if loop:
-            n = nn_train.train_epoch(pool, tr, args.batch, losses, None, 0.85, 1.15, log_interval=50, log=lambda it, loss: None)
+            n = nn_train.train_epoch(loop, tr, args.batch, losses, None, 0.85, 1.15, log_interval=50, log=lambda it, loss: None)
             mean = losses[:n].double().mean().item()            # the epoch's one synchronisation
         else:
             for k in range(steps):
@@ -278,9 +287,10 @@ def main():
     for _ in range(args.warmup):
         tr.learn(noisy0, clean0)
         tr.learn(*reversed(pool.batch(pool.draw(args.batch), exp_mult_min=0.85, exp_mult_max=1.15)))
-    rates = {"resident": [], "epoch_loop": []}
-    for _ in range(args.rounds):                                 # alternating windows: both see the same machine
-        for name, loop in (("resident", False), ("epoch_loop", True)):
+    legs = [("resident", None), ("epoch_loop", pool)] + ([("epoch_loop_windows", wpool)] if wpool is not None else [])
+    rates = {name: [] for name, _ in legs}
+    for _ in range(args.rounds):                                 # alternating windows: all see the same machine
+        for name, loop in legs:
             dt, n, mean = window(loop)
             rates[name].append(round(args.batch * n / dt, 2))
     mean_rate = {k: sum(v) / len(v) for k, v in rates.items()}
@@ -342,6 +352,10 @@ def main():
                              one_by_one_over_batched=round(vmean["one_by_one_s"] / vmean["batched_s"], 2)),
         "c_criteria_ms_per_call": dict(crit, bytes_read=2 * args.batch * 3 * args.cs * args.cs * 4),
     }
+    if wpool is not None:
+        result["config"]["source"] = f"{args.side}x{args.side} u8 crops of {args.frame} frames at stride {args.ds_stride}, cut out and as windows"
+        result["a_epoch"]["epoch_loop_windows_over_resident"] = round(mean_rate["epoch_loop_windows"] / mean_rate["resident"], 4)
+        result["a_epoch"]["epoch_loop_windows_over_epoch_loop"] = round(mean_rate["epoch_loop_windows"] / mean_rate["epoch_loop"], 4)
     print(json.dumps(result))
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
