@@ -293,6 +293,34 @@ def read_png(path):
     return np.ascontiguousarray(data).view(dt).reshape(H, W, ch).astype(np.uint8 if depth == 8 else np.uint16)
 
 
+# ------------------------------------------------------------------------------------------------ header only
+
+def image_size(path):
+    """(width, height) of an image from its header, without decoding a sample: PNG (IHDR), TIFF (tags 256 / 257 of the first
+    directory, inline SHORT or LONG), anything else through PIL, which opens lazily.  None when the header does not give them."""
+    with open(path, "rb") as f:
+        head = f.read(24)
+        if head[:8] == b"\x89PNG\r\n\x1a\n" and head[12:16] == b"IHDR":
+            return struct.unpack(">II", head[16:24])
+        bo = {b"II": "<", b"MM": ">"}.get(head[:2])
+        if bo is not None and len(head) >= 8 and struct.unpack(bo + "H", head[2:4])[0] == 42:
+            f.seek(struct.unpack(bo + "I", head[4:8])[0])
+            n = struct.unpack(bo + "H", f.read(2).ljust(2, b"\0"))[0]
+            ifd = f.read(12 * n)
+            size = {}
+            for e in range(0, len(ifd) - 11, 12):
+                tag, typ, cnt = struct.unpack(bo + "HHI", ifd[e:e + 8])
+                if tag in (256, 257) and typ in (3, 4) and cnt == 1:
+                    size[tag] = struct.unpack(bo + ("H" if typ == 3 else "I"), ifd[e + 8:e + (10 if typ == 3 else 12)])[0]
+            return (size[256], size[257]) if len(size) == 2 else None
+    try:
+        from PIL import Image
+        with Image.open(path) as im:
+            return im.size
+    except Exception:
+        return None
+
+
 def write_png(path, img):
     img = np.ascontiguousarray(img)
     if img.ndim != 3 or img.shape[2] != 3 or img.dtype not in (np.uint8, np.uint16):

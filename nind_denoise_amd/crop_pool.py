@@ -17,6 +17,8 @@ csv, and after set_min_quality(q) draws take only pairs whose score is above q.
 Without the pre-cropped dataset: CropPool.from_full_size reads the full-size images, keeps each once in HBM as a frame, and makes
 of every crop the reference's cropper would have written (crop_grid: tools/crop_img.sh) a window into its frame.  Groups, draws,
 batches and scores are those of the pool of crop files, bit for bit (nd_crop_batch_windows, nd_pool_fetch_windows).
+crop_source goes the other way, from the path of a crop file to its window of a full-size image (the validation lists name crop
+files: validation.ValidationSet.from_full_size); set_images and crop_names are the naming both share.
 
 Not built: the sigmamin / sigmamax artificial noise and the JPEG re-compression branch of the reference's __getitem__ (the first is
 "rarely used / experimental" by its docstring, the second calls .save on a numpy array).
@@ -24,12 +26,13 @@ Not built: the sigmamin / sigmamax artificial noise and the JPEG re-compression 
 import csv
 import math
 import os
+import re
 
 import numpy as np
 import torch
 
 from . import _lib
-from .common.libs import np_imgops, utilities
+from .common.libs import imgcodec, np_imgops, utilities
 from .dataset_torch_3 import sortISOs
 
 _TYPES = {np.dtype(np.uint8): _lib.SAMPLE_U8, np.dtype(np.uint16): _lib.SAMPLE_U16, np.dtype(np.float32): _lib.SAMPLE_F32}
@@ -109,6 +112,111 @@ def findisoval(fn):
             if word in part:
                 return fn[fn.find(word):].split('.')[0]
     return None
+
+
+def set_images(set_dpath):
+    """{ISO: (path of the full-size file, the name the cropper would have cropped it under)} of one set directory of a full-size
+    dataset, in sorted file order: the ISO of a file as the cropper finds it (findisoval); a second file with an ISO already seen
+    is <iso>-2, a third <iso>-2-2, and named as if it had been renamed so (tools/crop_ds.py:48-55).  No file is opened.
+    ValueError for a file that names no ISO value."""
+    files = {}
+    for image in sorted(os.listdir(set_dpath)):
+        iso = old = findisoval(image)
+        if iso is None:
+            raise ValueError(f"crop_pool.set_images: {os.path.join(set_dpath, image)} names no ISO value "
+                             "(ISO<value>, GT... or NOISY... between underscores)")
+        while iso in files:
+            iso += '-2'
+        files[iso] = (os.path.join(set_dpath, image), image.replace(old, iso))
+    return files
+
+
+def crop_names(name, width, height, ds_cs, ds_stride):
+    """{crop file name: (xbeg, ybeg)} of the crops the cropper writes for a width x height image it crops under `name`, in its
+    loop's order: <name less its last four characters>_<xcrop>_<ycrop>_<ds_stride>.<the last three, in lower case>
+    (tools/crop_img.sh:9-10, 26)."""
+    stem, ext = name[:-4], name.lower()[-3:]
+    return {f'{stem}_{xc}_{yc}_{ds_stride}.{ext}': (xb, yb) for xc, yc, xb, yb in crop_grid(width, height, ds_cs, ds_stride)}
+
+
+def crops_dirs_of(dsdirs, ds_cs, ds_stride, crops_dir=None):
+    """(dsdirs as a list of strings, the directory of each one's cropped tree): crops_dir, one path per dsdir, or the cropper's own
+    <root of dsdir>/cropped/<leaf of dsdir>_<ds_cs>_<ds_stride>.  ValueError when the two lists differ in length."""
+    if isinstance(dsdirs, (str, os.PathLike)):
+        dsdirs = [dsdirs]
+    dsdirs = [os.fspath(d) for d in dsdirs]
+    if crops_dir is None:
+        return dsdirs, [os.path.join(utilities.get_root(d), 'cropped', f'{utilities.get_leaf(d)}_{ds_cs}_{ds_stride}') for d in dsdirs]
+    crops_dirs = [os.fspath(crops_dir)] if isinstance(crops_dir, (str, os.PathLike)) else [os.fspath(d) for d in crops_dir]
+    if len(crops_dirs) != len(dsdirs):
+        raise ValueError(f"crop_pool: {len(crops_dirs)} crops_dir for {len(dsdirs)} dataset directories")
+    return dsdirs, crops_dirs
+
+
+class CropSources:
+    """crop_source for many paths of one dataset: the table of a set and the crop names of an image are made once.  decoded holds
+    the images that had to be decoded for their size (float32 [3,H,W], by path), for the caller to take instead of decoding again;
+    image_size gives the size of every format np_imgops reads from the header, so it stays empty."""
+
+    def __init__(self, dsdirs, ds_cs, ds_stride, crops_dir=None):
+        self.dsdirs, self.crops_dirs = crops_dirs_of(dsdirs, ds_cs, ds_stride, crops_dir)
+        crop_grid(0, 0, ds_cs, ds_stride)
+        self.ds_cs, self.ds_stride = int(ds_cs), int(ds_stride)
+        self.leaves = [utilities.get_leaf(d) for d in self.crops_dirs]
+        self.decoded = {}
+        self._sets, self._names = {}, {}
+
+    def _names_of(self, fpath, name):
+        if fpath not in self._names:
+            size = imgcodec.image_size(fpath)
+            if size is None:
+                self.decoded[fpath] = np_imgops.img_path_to_np_flt(fpath)
+                size = self.decoded[fpath].shape[2], self.decoded[fpath].shape[1]
+            self._names[fpath] = (crop_names(name, size[0], size[1], self.ds_cs, self.ds_stride), size)
+        return self._names[fpath]
+
+    def source(self, crop_path):
+        given = os.fspath(crop_path)
+        parts = [p for p in given.replace(os.sep, '/').split('/') if p and p != '.']
+        if len(parts) < 4 or parts[-4] not in self.leaves:
+            return None
+        leaf, aset, iso, fname = parts[-4:]
+        dsdir = self.dsdirs[self.leaves.index(leaf)]
+        set_dpath = os.path.join(dsdir, aset)
+        if aset in ('.', '..') or not os.path.isdir(set_dpath):
+            raise FileNotFoundError(f"{given}: {dsdir} has no set {aset!r}")
+        if set_dpath not in self._sets:
+            self._sets[set_dpath] = set_images(set_dpath)
+        if iso not in self._sets[set_dpath]:
+            raise FileNotFoundError(f"{given}: {set_dpath} has no image of ISO {iso!r} (it has {', '.join(self._sets[set_dpath])})")
+        fpath, name = self._sets[set_dpath][iso]
+        names, (width, height) = self._names_of(fpath, name)
+        if fname not in names:
+            # the crop of the same indices, where the name shows them and the grid yields them (another extension, stem or stride
+            # suffix), else the first one
+            m = re.fullmatch(r'.*_(\d+)_(\d+)_\d+\.[^.]*', fname)
+            example = m and f'{name[:-4]}_{m[1]}_{m[2]}_{self.ds_stride}.{name.lower()[-3:]}'
+            example = example if example in names else next(iter(names), None)
+            would = f"it writes {len(names)} crops, such as {example}" if names else "it writes no crop of it"
+            raise FileNotFoundError(f"{given}: not a crop the cropper writes for {fpath} ({width} x {height}) at crop size "
+                                    f"{self.ds_cs}, stride {self.ds_stride}: {would}")
+        xbeg, ybeg = names[fname]
+        return fpath, ybeg, xbeg
+
+
+def crop_source(crop_path, dsdirs, ds_cs, ds_stride, crops_dir=None):
+    """Where the crop file crop_path lies in the full-size dataset: (path of the full-size image, ybeg, xbeg) of the ds_cs x ds_cs
+    rectangle the reference's cropper (tools/crop_ds.py --cs ds_cs --stride ds_stride) would have written under that name, or None
+    when the path is not a crop of this data.  Decided by the path's last four components <crops leaf>/<set>/<iso>/<file name>
+    alone; what comes before them is ignored (lists hold paths relative to a working directory the user may not have), and no
+    crop file is looked for.  <crops leaf> is the leaf of the cropped tree CropPool.from_full_size derives for one of dsdirs
+    (<leaf of dsdir>_<ds_cs>_<ds_stride>, or the leaf of its crops_dir entry); the first dsdir that matches takes the path, and
+    None is returned when none does.  From there on a mismatch is FileNotFoundError naming crop_path as given: a set the dsdir
+    does not have, an ISO the set does not have (set_images), or a file name other than <stem>_<xcrop>_<ycrop>_<ds_stride>.<ext>
+    with the stem and extension of that ISO's image and indices that crop_grid yields for its size; the message then names a
+    crop the cropper does write for the image.  Sizes are read from the file header (imgcodec.image_size).
+    For many paths make one CropSources and call its source()."""
+    return CropSources(dsdirs, ds_cs, ds_stride, crops_dir).source(crop_path)
 
 
 class Draws:
@@ -332,15 +440,7 @@ class CropPool:
         files on disk, in directory order.  This pool renames nothing.  JPEG sources are decoded like any other file: equality with a
         jpegtran-cropped tree is not claimed, since a decoder upsamples chroma differently at the border of a crop file than inside
         the whole image.  For PNG and TIFF a crop file is a rectangle of its image, and the pools are equal bit for bit."""
-        if isinstance(dsdirs, (str, os.PathLike)):
-            dsdirs = [dsdirs]
-        dsdirs = [os.fspath(d) for d in dsdirs]
-        if crops_dir is None:
-            crops_dirs = [os.path.join(utilities.get_root(d), 'cropped', f'{utilities.get_leaf(d)}_{ds_cs}_{ds_stride}') for d in dsdirs]
-        else:
-            crops_dirs = [os.fspath(crops_dir)] if isinstance(crops_dir, (str, os.PathLike)) else [os.fspath(d) for d in crops_dir]
-            if len(crops_dirs) != len(dsdirs):
-                raise ValueError(f"CropPool.from_full_size: {len(crops_dirs)} crops_dir for {len(dsdirs)} dataset directories")
+        dsdirs, crops_dirs = crops_dirs_of(dsdirs, ds_cs, ds_stride, crops_dir)
         crop_grid(0, 0, ds_cs, ds_stride)         # refuses the sizes the script refuses, before any file is read
         pool = cls(device, seed=seed, cs=int(ds_cs) if cs is None else cs)
         pool.datadirs = crops_dirs
@@ -355,15 +455,7 @@ class CropPool:
             for aset in sorted(os.listdir(dsdir)):
                 if reserved(aset):
                     continue
-                files = {}                        # ISO -> (path, the name the cropper would have cropped it under)
-                for image in sorted(os.listdir(os.path.join(dsdir, aset))):
-                    iso = old = findisoval(image)
-                    if iso is None:
-                        raise ValueError(f"CropPool.from_full_size: {os.path.join(dsdir, aset, image)} names no ISO value "
-                                         "(ISO<value>, GT... or NOISY... between underscores)")
-                    while iso in files:
-                        iso += '-2'
-                    files[iso] = (os.path.join(dsdir, aset, image), image.replace(old, iso))
+                files = set_images(os.path.join(dsdir, aset))
                 if not files:
                     continue
                 bisos, isos = sortISOs(sorted(files))
@@ -379,8 +471,7 @@ class CropPool:
                     except Exception as e:
                         raise ValueError(f"CropPool.from_full_size: cannot read {fpath}: {e}") from e
                     _, h, w = samples[iso].shape
-                    stem, ext = name[:-4], name.lower()[-3:]     # crop_img.sh:9-10, 26
-                    crops[iso] = {f'{stem}_{xc}_{yc}_{ds_stride}.{ext}': (xb, yb) for xc, yc, xb, yb in crop_grid(w, h, ds_cs, ds_stride)}
+                    crops[iso] = crop_names(name, w, h, ds_cs, ds_stride)
                 if not crops[isos[0]]:
                     continue
                 frames = {iso: pool.add_frame(samples[iso]) for iso in bisos + isos}

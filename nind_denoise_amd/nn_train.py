@@ -20,6 +20,13 @@ Quality bar (the cure README.md:140 of the reference names for an unstable start
 trains on the pairs whose MS-SSIM is above Q, for the first --min_quality_epochs epochs or for the whole run; the scores are
 computed from the resident pool at start, or read from the csv of tools.make_dataset_crops_list with --quality_csv.
 
+Without the pre-cropped dataset: --full_size_data DIR [--ds_cs 256 --ds_stride 192] stands in for --train_data.  The pool holds the
+full-size images and takes the cropper's crops as windows into them (CropPool.from_full_size), and the pairs of
+--validation_set_yaml are cut out of the full-size images of the reserved sets in the same way (ValidationSet.from_full_size): a
+path of the list that names a crop of DIR (crop_pool.crop_source: by its last four components, never by what exists on disk) is a
+window, any other pair is read from disk.  tools.pick_validation_set --full_size_data writes such a list.  For PNG and TIFF sources
+the run is the run on the cropped tree, byte for byte; JPEG sources are decoded whole, and that equality is not claimed for them.
+
 Long runs: --g_clip_norm X clips the gradient by its global norm and --skip_nonfinite_steps leaves a step with a non-finite
 gradient unapplied, both decided on the device (train._GuardedStep); --max_skipped_steps N ends a run that keeps skipping.
 --save_state writes train_state.pt after every epoch and --resume RUN_DIR continues that run to the bits the uninterrupted run
@@ -640,6 +647,13 @@ def run(args, process_group=None, argv=None):
     steps = all_steps = pool.n_groups // args.batch_size // world
     frames = f' (windows into {pool.n_frames} frames)' if pool.windowed else ''
     p.print(f'Crop pool: {pool.n_groups} groups, {pool.n_images} images{frames}, {pool.nbytes / 1e6:.1f} MB in HBM; {steps} steps per epoch')
+    validation_set = None
+    if full_size_data and args.validation_interval > 0 and args.validation_set_yaml is not None:
+        # the crop files the list names are windows into the full-size images of the reserved sets: their names decide which
+        # (crop_pool.crop_source), never what happens to exist on disk; every rank builds its own copy
+        validation_set = ValidationSet.from_full_size(args.validation_set_yaml, full_size_data, ds_cs, ds_stride, device, cs=args.cs)
+        p.print(f'Validation set: {len(validation_set)} pairs, {validation_set.n_windows} of them windows into '
+                f'{validation_set.n_full_size_images} full-size images')
     if resume_dir is not None:
         if world > 1:       # the small fields; the trainer's buffers follow once the trainer exists
             small = from_rank0({k: v for k, v in state.items() if k != 'trainer'} if rank == 0 else None, process_group)
@@ -679,7 +693,8 @@ def run(args, process_group=None, argv=None):
     if args.validation_interval > 0:
         if args.validation_set_yaml is None:
             raise ValueError('nn_train: --validation_set_yaml is not set (or give --validation_interval 0)')
-        validation_set = ValidationSet(args.validation_set_yaml, device=device, cs=args.cs)
+        if validation_set is None:
+            validation_set = ValidationSet(args.validation_set_yaml, device=device, cs=args.cs)
 
         def get_validation_dpath(epoch):
             return os.path.join(model_dir, 'val', str(epoch)) if 'output_val_images' in args.debug_options else None

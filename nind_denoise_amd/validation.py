@@ -6,6 +6,12 @@ Restates validate_generator (nn_train.py:51-71) and ValidationDataset (dataset_t
 validate one image at a time and read every file again every epoch: the loss of a validation pass is the mean over the images of
 each image's own weighted loss (Generator.compute_loss on a batch of one, nn_common.py:226-241), so the batched pass needs the
 criteria per sample, not per batch.
+
+The set is read once, on the host: ValidationSet(val_tuples, device, cs) opens each path of the list as a crop file;
+ValidationSet.from_full_size(val_tuples, dsdirs, ds_cs, ds_stride, device, cs) needs no crop file: it cuts the pairs whose paths
+name crops of the full-size dataset dsdirs (crop_pool.crop_source) out of the full-size images, each decoded once, and gives the
+same tensors bit for bit for PNG and TIFF sources (JPEG sources are decoded whole; equality with a jpegtran-cropped tree is not
+claimed).  Neither runs a kernel: 300 pairs of 256 x 256 are no hot path.
 """
 import os
 
@@ -117,6 +123,69 @@ class ValidationSet:
             clean[i], noisy[i] = center_crop_pair(ximg, yimg, self.cs, (xpath, ypath))
         self.clean = torch.from_numpy(clean).to(self.device)
         self.noisy = torch.from_numpy(noisy).to(self.device)
+
+    @classmethod
+    def from_full_size(cls, val_tuples, dsdirs, ds_cs=256, ds_stride=192, device=None, cs=None, crops_dir=None):
+        """The set ValidationSet(val_tuples, device, cs) would read from the tree the reference's cropper (tools/crop_ds.py --cs
+        ds_cs --stride ds_stride) writes for the full-size dataset(s) dsdirs, without that tree.  A pair whose two paths name
+        crops of dsdirs (crop_pool.crop_source: by the last four components of the path, never by what exists on disk) is cut out
+        of its two full-size images: each read with np_imgops.img_path_to_np_flt, rows [ybeg, ybeg + ds_cs), columns
+        [xbeg, xbeg + ds_cs), then center_crop_pair to cs (default ds_cs).  A pair of two other paths is read from disk as the
+        constructor reads it; a pair of one of each is ValueError.  A path that names a crop of dsdirs the cropper does not write
+        is FileNotFoundError (crop_source), before any image is decoded.
+        The pairs are taken file by file: sorted by (clean file, noisy file), two images at most in host memory, so a full-size
+        file is decoded once -- once per clean partner, should a noisy file have several.  .clean[i], .noisy[i] and val_tuples
+        keep the order and the paths given; n_windows pairs are windows into n_full_size_images files.
+        For PNG and TIFF sources a crop file is a rectangle of its image and the float conversion is per sample: the two tensors
+        are the constructor's on the cropped tree, bit for bit.  JPEG sources are decoded whole: equality with a jpegtran-cropped
+        tree is not claimed, since a decoder upsamples chroma differently at the border of a crop file than inside the whole
+        image (CropPool.from_full_size says the same)."""
+        from .crop_pool import CropSources
+        if isinstance(val_tuples, (str, os.PathLike)):
+            with open(val_tuples, 'r') as fp:
+                val_tuples = yaml.safe_load(fp)
+        if not val_tuples:
+            raise ValueError("ValidationSet: no validation pair")
+        self = cls.__new__(cls)
+        self.val_tuples = [list(pair) for pair in val_tuples]
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        ds_cs = int(ds_cs)
+        self.cs = ds_cs if cs is None else int(cs)
+        sources = CropSources(dsdirs, ds_cs, ds_stride, crops_dir)
+        windows = []                                # (clean file, noisy file, pair, clean (ybeg, xbeg), noisy (ybeg, xbeg))
+        clean = np.empty((len(self.val_tuples), 3, self.cs, self.cs), dtype=np.float32)
+        noisy = np.empty_like(clean)
+        for i, (xpath, ypath) in enumerate(self.val_tuples):
+            xsrc, ysrc = sources.source(xpath), sources.source(ypath)
+            if (xsrc is None) != (ysrc is None):
+                raise ValueError(f"ValidationSet.from_full_size: of the pair {xpath}, {ypath} one path names a crop of {dsdirs} "
+                                 f"and the other ({ypath if ysrc is None else xpath}) does not")
+            if xsrc is not None:
+                windows.append((xsrc[0], ysrc[0], i, xsrc[1:], ysrc[1:]))
+        # path -> float32 [3,H,W]: the images of the pair being cut, and none but them (beside any that crop_source had to decode for
+        # its size, which stay until they are used: no file is decoded twice)
+        held, mine = sources.decoded, set()
+        for xfile, yfile, i, (xy, xx), (yy, yx) in sorted(windows):
+            for fpath in mine - {xfile, yfile}:
+                del held[fpath]
+            mine &= {xfile, yfile}
+            for fpath in (xfile, yfile):
+                if fpath not in held:
+                    held[fpath] = np_imgops.img_path_to_np_flt(fpath)
+                mine.add(fpath)
+            clean[i], noisy[i] = center_crop_pair(held[xfile][:, xy:xy + ds_cs, xx:xx + ds_cs],
+                                                  held[yfile][:, yy:yy + ds_cs, yx:yx + ds_cs], self.cs, tuple(self.val_tuples[i]))
+        held.clear()
+        inside = {w[2] for w in windows}
+        for i, (xpath, ypath) in enumerate(self.val_tuples):
+            if i not in inside:
+                clean[i], noisy[i] = center_crop_pair(np_imgops.img_path_to_np_flt(xpath), np_imgops.img_path_to_np_flt(ypath),
+                                                      self.cs, (xpath, ypath))
+        self.n_windows = len(windows)
+        self.n_full_size_images = len({f for w in windows for f in w[:2]})
+        self.clean = torch.from_numpy(clean).to(self.device)
+        self.noisy = torch.from_numpy(noisy).to(self.device)
+        return self
 
     @classmethod
     def from_tensors(cls, clean, noisy, device=None):

@@ -18,7 +18,12 @@ Images are seeded noise: the kernel's traffic does not depend on the picture.
 until there are `groups` crops; one pool holds the frames and takes the crops as windows (nd_crop_batch_windows), the other holds
 the cut-out crops (nd_crop_batch).  (a) and (b) are then measured for both, in alternating rounds, and (d) writes `build_frames`
 frames as a PNG dataset of sets of one clean and one noisy image, crops it into a second tree, and times CropPool.from_full_size
-on the first against CropPool.from_directories on the second (host-bound: decode and upload), with the bytes each holds."""
+on the first against CropPool.from_directories on the second (host-bound: decode and upload), with the bytes each holds.
+
+    python tools/bench_crop_pool.py --validation [--val_pairs 300] [--frame 3000x2000] [--build_frames 24] [--out profiles/val_full_size.json]
+
+--validation, alone: the dataset of (d), `val_pairs` pairs picked from it as tools.pick_validation_set picks them, and the seconds
+to build the validation set from the full-size images (ValidationSet.from_full_size) against building it from the crop files."""
 import argparse
 import json
 import os
@@ -59,23 +64,67 @@ def time_batches(pool, args, kw):
     return ms_launch, 1e3 * (time.perf_counter() - t0) / args.iters
 
 
+def write_png_dataset(tmp, args):
+    """(dsdir, cropped tree, grid): args.build_frames frames as a PNG dataset of sets of one clean and one noisy image under tmp, and the
+    tree a cropper writes for it at args.side / args.ds_stride"""
+    fw, fh = (int(v) for v in args.frame.split("x"))
+    rng = np.random.default_rng(2)
+    dsdir = os.path.join(tmp, "SYN")
+    cropped = os.path.join(tmp, "cropped", f"SYN_{args.side}_{args.ds_stride}")
+    grid = crop_grid(fw, fh, args.side, args.ds_stride)
+    for k in range(args.build_frames // 2):
+        clean = rng.integers(0, 256, (fh, fw, 3), dtype=np.uint8)
+        for iso, img in (("ISO100", clean), ("ISO6400", clean ^ rng.integers(0, 16, clean.shape, dtype=np.uint8))):
+            os.makedirs(os.path.join(dsdir, f"set{k}"), exist_ok=True)
+            os.makedirs(os.path.join(cropped, f"set{k}", iso), exist_ok=True)
+            imgcodec.write_png(os.path.join(dsdir, f"set{k}", f"SYN_set{k}_{iso}.png"), img)
+            for xc, yc, xb, yb in grid:
+                imgcodec.write_png(os.path.join(cropped, f"set{k}", iso, f"SYN_set{k}_{iso}_{xc}_{yc}_{args.ds_stride}.png"),
+                                   np.ascontiguousarray(img[yb:yb + args.side, xb:xb + args.side]))
+    return dsdir, cropped, grid
+
+
+def time_validation(args, dev):
+    """--validation: ValidationSet.from_full_size on the PNG dataset of (d) against ValidationSet on its cropped tree, for
+    args.val_pairs pairs that tools.pick_validation_set's candidates give under one seed.  Host-bound (decode, slicing, one upload);
+    the files were just written, so both read from the page cache; alternating runs, the median of args.rounds."""
+    import random
+    from nind_denoise_amd.tools.pick_validation_set import candidates_of_full_size
+    from nind_denoise_amd.validation import ValidationSet
+    fw, fh = (int(v) for v in args.frame.split("x"))
+    with tempfile.TemporaryDirectory() as tmp:
+        dsdir, cropped, grid = write_png_dataset(tmp, args)
+        candidates, _ = candidates_of_full_size([dsdir], [cropped], args.side, args.ds_stride, sorted(os.listdir(dsdir)))
+        pairs = random.Random(3).sample(candidates, args.val_pairs)
+        legs = {"from_crop_files": lambda: ValidationSet(pairs, dev, args.cs),
+                "from_full_size": lambda: ValidationSet.from_full_size(pairs, dsdir, args.side, args.ds_stride, dev, args.cs)}
+        secs, sets = {name: [] for name in legs}, {}
+        for _ in range(args.rounds):
+            for name, make in legs.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                sets[name] = make()
+                torch.cuda.synchronize()
+                secs[name].append(round(time.perf_counter() - t0, 3))
+        same = bool(torch.equal(sets["from_crop_files"].clean, sets["from_full_size"].clean)
+                    and torch.equal(sets["from_crop_files"].noisy, sets["from_full_size"].noisy))
+        res = {"device": torch.cuda.get_device_name(0),
+               "dataset": f"{args.build_frames} frames of {fw}x{fh} u8 PNG at {args.side}/{args.ds_stride}: {len(grid)} crops per frame, "
+                          f"{len(candidates)} candidate pairs",
+               "pairs": len(pairs), "cs": args.cs, "rounds": args.rounds, "tensors_equal": same,
+               "from_crop_files": {"build_s": secs["from_crop_files"], "build_s_median": statistics.median(secs["from_crop_files"]),
+                                   "files_decoded": 2 * len(pairs)},
+               "from_full_size": {"build_s": secs["from_full_size"], "build_s_median": statistics.median(secs["from_full_size"]),
+                                  "files_decoded": sets["from_full_size"].n_full_size_images}}
+        res["full_size_over_crop_files"] = round(res["from_full_size"]["build_s_median"] / res["from_crop_files"]["build_s_median"], 3)
+    return res
+
+
 def time_builds(args, dev):
     """(d): from_full_size on a PNG dataset of args.build_frames frames against from_directories on the same dataset, cropped"""
     fw, fh = (int(v) for v in args.frame.split("x"))
-    rng = np.random.default_rng(2)
     with tempfile.TemporaryDirectory() as tmp:
-        dsdir = os.path.join(tmp, "SYN")
-        cropped = os.path.join(tmp, "cropped", f"SYN_{args.side}_{args.ds_stride}")
-        grid = crop_grid(fw, fh, args.side, args.ds_stride)
-        for k in range(args.build_frames // 2):
-            clean = rng.integers(0, 256, (fh, fw, 3), dtype=np.uint8)
-            for iso, img in (("ISO100", clean), ("ISO6400", clean ^ rng.integers(0, 16, clean.shape, dtype=np.uint8))):
-                os.makedirs(os.path.join(dsdir, f"set{k}"), exist_ok=True)
-                os.makedirs(os.path.join(cropped, f"set{k}", iso), exist_ok=True)
-                imgcodec.write_png(os.path.join(dsdir, f"set{k}", f"SYN_set{k}_{iso}.png"), img)
-                for xc, yc, xb, yb in grid:
-                    imgcodec.write_png(os.path.join(cropped, f"set{k}", iso, f"SYN_set{k}_{iso}_{xc}_{yc}_{args.ds_stride}.png"),
-                                       np.ascontiguousarray(img[yb:yb + args.side, xb:xb + args.side]))
+        dsdir, cropped, grid = write_png_dataset(tmp, args)
         res = {}
         for name, make in (("from_directories", lambda: CropPool.from_directories(cropped, device=dev)),
                            ("from_full_size", lambda: CropPool.from_full_size(dsdir, ds_cs=args.side, ds_stride=args.ds_stride, device=dev))):
@@ -198,19 +247,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--funit", type=int, default=64)
-    ap.add_argument("--out", default=None, help="default: profiles/crop_pool.json, with --windows profiles/crop_pool_windows.json")
+    ap.add_argument("--out", default=None, help="default: profiles/crop_pool.json, with --windows profiles/crop_pool_windows.json, with --validation profiles/val_full_size.json")
     ap.add_argument("--windows", action="store_true", help="the same data as frames: windows against the cut-out crops")
     ap.add_argument("--frame", default="3000x2000", help="--windows: WxH of a frame")
     ap.add_argument("--ds_stride", type=int, default=192, help="--windows: the cropper's stride (its crop size is --side)")
     ap.add_argument("--build_frames", type=int, default=24, help="--windows: frames of the PNG dataset whose pool builds are timed (0: skip)")
+    ap.add_argument("--validation", action="store_true", help="time the validation set from the full-size images against the one from crop files, alone")
+    ap.add_argument("--val_pairs", type=int, default=300, help="--validation: picked pairs")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join("profiles", "crop_pool_windows.json" if args.windows else "crop_pool.json")
+        args.out = os.path.join("profiles", "val_full_size.json" if args.validation else
+                                "crop_pool_windows.json" if args.windows else "crop_pool.json")
     if not torch.cuda.is_available():
         sys.exit("bench_crop_pool needs a GPU")
     dev = torch.device("cuda", 0)
-    if args.windows:
-        result = main_windows(args, dev)
+    if args.validation or args.windows:
+        result = time_validation(args, dev) if args.validation else main_windows(args, dev)
         print(json.dumps(result))
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
