@@ -194,6 +194,22 @@ def stream_ptr(device=None):
     return c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def make_workspace(size_fn, init_fn, args, device, what, drop=None):
+    """An initialised workspace: size_fn(*args) bytes of uint8 on `device`, handed to init_fn(pointer, bytes, *args, stream).  A size of
+    0 means the library refuses `args`: init_fn is then called with nulls so that it names what is wrong (raised with `what` in
+    front).  drop: called once the size is known and before the allocation -- the caller lets go of the workspace this one
+    replaces, so the two never have to fit side by side.  Caching is the caller's."""
+    import torch
+    nbytes = size_fn(*args)
+    if nbytes == 0:
+        check(init_fn(None, 0, *args, None), what)
+    if drop is not None:
+        drop()
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    check(init_fn(ws.data_ptr(), nbytes, *args, stream_ptr(device)), init_fn.__name__)
+    return ws
+
+
 def ptr(t):
     """Raw data pointer of a torch tensor (must be contiguous)."""
     assert t.is_contiguous(), "tensor must be contiguous"
@@ -219,3 +235,24 @@ def tile_geom(i, width, height, cs, ucs, ol):
 def utnet_tensor_names():
     lib = load()
     return [lib.nd_utnet_tensor_name(i).decode() for i in range(lib.nd_utnet_num_tensors())]
+
+
+def _ranges(names, range_of):
+    ranges = {}
+    for i, name in enumerate(names):
+        off, cnt = c_size_t(), c_size_t()
+        check(range_of(i, off, cnt))
+        ranges[name] = (off.value, cnt.value)
+    return ranges
+
+
+def utnet_ranges(funit):
+    """{tensor name: (offset, count)} of the flat UtNet layout (nd_utnet_param_range), PReLU slopes included."""
+    lib = load()
+    return _ranges(utnet_tensor_names(), lambda i, off, cnt: lib.nd_utnet_param_range(funit, i, off, cnt))
+
+
+def unet_ranges():
+    """{tensor name: (offset, count)} of the flat UNet layout (nd_unet_param_range): parameters and running statistics."""
+    lib = load()
+    return _ranges([lib.nd_unet_tensor_name(i).decode() for i in range(lib.nd_unet_num_tensors())], lib.nd_unet_param_range)

@@ -332,7 +332,7 @@ int nd_launch_splice(const QpBuf &src, int src_p0, const QpBuf &dst, int dst_p0,
                      long slot_elems = 0, int dst_img0 = 0);
 
 // ------------------------------------------------------------------ gradient kernels shared by the two networks' backward passes
-// (wgrad.hip, train.hip, utnet_train.hip): no atomics, fixed summation order
+// (wgrad.hip, train.hip, utnet_train.hip, unet_grad.hip): no atomics, fixed summation order
 // dst (its own grid) = zeros except dst[c][img][y + oy][x + ox] = src[c][img][y * ss + sy][x * ss + sx] for y < h, x < w (interior coordinates)
 int nd_launch_repitch(const QpBuf &src, int src_plane0, int planes, int ss, int sy, int sx, const QpBuf &dst, int oy, int ox, int h, int w,
                       hipStream_t s);
@@ -346,3 +346,13 @@ int nd_launch_maxpool_bwd_add(const QpBuf &gpool, const QpBuf &fwd, int fwd_plan
 int nd_launch_final_wgrad(const float *gy, int H, int W, const QpBuf &act, int cin, int crop, float *red, float *dw, float *db,
                           hipStream_t s);
 int nd_launch_final_bwd_data(const float *gy, int H, int W, const float *w, int cin, int crop, const QpBuf &g, hipStream_t s);
+
+// ------------------------------------------------------------------ BatchNorm on the statistics of the batch (unet_bn.hip)
+// z: the pre-norm conv output (no border), a / g: the layer's activation / gradient buffer from plane0, stat: 3 * cout floats the
+// forward leaves for the backward, red: reduction scratch of red_floats floats, coef: 2 * cout floats.
+// forward: statistics of z -> stat, running statistics rm / rv moved by momentum, a = ReLU(gamma xhat + beta)
+int nd_launch_bn_train_fwd(const QpBuf &z, const QpBuf &a, int plane0, int cout, float momentum, const float *gamma, const float *beta,
+                           float *rm, float *rv, float *stat, float *red, long red_floats, hipStream_t s);
+// backward: g_a -> g_z in place in g; dgamma / dbeta (nullable together) get the BatchNorm's parameter gradients
+int nd_launch_bn_train_bwd(const QpBuf &g, const QpBuf &a, int plane0, const QpBuf &z, int cout, const float *gamma, const float *stat,
+                           float *coef, float *dgamma, float *dbeta, float *red, long red_floats, hipStream_t s);

@@ -1,5 +1,5 @@
 // The UNet stack as data: layers, tensor names, packed-blob layout, activation plan, step list and the useful-region plan.
-// Shared by the inference executor (unet.hip) and the autograd halves (unet_grad.hip); host code only.
+// Shared by the inference executor (unet.hip) and the autograd halves of both BatchNorm modes (unet_grad.hip); host code only.
 #pragma once
 #include <math.h>
 #include <string.h>

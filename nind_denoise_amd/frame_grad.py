@@ -136,9 +136,7 @@ class _UtNetFrame(torch.autograd.Function):
         height, width = img.size(1), img.size(2)
         lib = _lib.load()
         st = model._train_state(dev)
-        for n, p in zip(names, params):
-            off, cnt = st.ranges[n]
-            st.flat[off:off + cnt].copy_(p.detach().reshape(-1))
+        st.load(dict(zip(names, params)))
         gcanvas = gcanvas.to(torch.float32).contiguous()
         gimg = torch.zeros_like(img) if want_img else None
         acc = torch.zeros_like(st.grads) if any(want_p) else None
@@ -149,7 +147,7 @@ class _UtNetFrame(torch.autograd.Function):
         act, flags = _lib.ACT[model.activation], model.flags
         with torch.cuda.device(dev):
             s = _lib.stream_ptr(dev)
-            ws = st.workspace(model, cs, cs, batch)
+            ws = st.workspace(cs, cs, batch)
             laid_out = batch                      # the launch size the workspace's zero borders are laid out for
             for t0 in range(begin, end, batch):
                 cnt = min(batch, end - t0)

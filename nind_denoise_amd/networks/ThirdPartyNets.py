@@ -14,6 +14,7 @@ import torch
 from torch import nn
 
 from .. import _lib
+from ._autograd import FlatState, NetFunction
 from .UtNet import canonical_compute_dtype
 
 
@@ -29,94 +30,6 @@ class _Box(nn.Module):
 def _double_conv(in_ch, out_ch):
     return _Box(conv=nn.Sequential(nn.Conv2d(in_ch, out_ch, 3, padding=1), nn.BatchNorm2d(out_ch), nn.ReLU(inplace=True),
                                    nn.Conv2d(out_ch, out_ch, 3, padding=1), nn.BatchNorm2d(out_ch), nn.ReLU(inplace=True)))
-
-
-class _GradState:
-    """Flat parameter / gradient buffers (parameters AND BatchNorm buffers, nd_unet_tensor_name order), the packed-weight blobs and the
-    gradient workspace of one module on one device (nd_unet_grad_forward / nd_unet_grad_backward of include/nind_hip.h)."""
-
-    def __init__(self, device):
-        lib = _lib.load()
-        self.device = device
-        n = lib.nd_unet_param_count()
-        self.flat = torch.zeros(n, dtype=torch.float32, device=device)
-        self.grads = torch.zeros(n, dtype=torch.float32, device=device)
-        self.blobs = torch.empty(lib.nd_unet_grad_blob_bytes(), dtype=torch.uint8, device=device)
-        self.ranges = {}
-        for i in range(lib.nd_unet_num_tensors()):
-            off, cnt = ctypes.c_size_t(), ctypes.c_size_t()
-            _lib.check(lib.nd_unet_param_range(i, off, cnt))
-            self.ranges[lib.nd_unet_tensor_name(i).decode()] = (off.value, cnt.value)
-        self.ws, self.ws_key = None, None
-        self.generation = 0          # bumped by every forward: a backward must follow ITS forward
-
-    def load(self, tensors):
-        """Copy {name: tensor} (parameters and buffers) into the flat buffer; num_batches_tracked has no slot."""
-        with torch.no_grad():
-            for n, t in tensors.items():
-                if n.endswith("num_batches_tracked"):
-                    continue
-                off, cnt = self.ranges[n]
-                self.flat[off:off + cnt].copy_(t.detach().reshape(-1))
-
-    def workspace(self, h, w, batch):
-        if self.ws_key != (h, w, batch):
-            lib = _lib.load()
-            nbytes = lib.nd_unet_grad_workspace_bytes(h, w, batch)
-            if nbytes == 0:
-                _lib.check(lib.nd_unet_grad_workspace_init(None, 0, h, w, batch, None), "UNet under autograd")
-            self.ws = None
-            self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(lib.nd_unet_grad_workspace_init(self.ws.data_ptr(), nbytes, h, w, batch, _lib.stream_ptr(self.device)),
-                       "nd_unet_grad_workspace_init")
-            self.ws_key = (h, w, batch)
-        return self.ws
-
-
-class _UNetFunction(torch.autograd.Function):
-    """UNet.forward under autograd (eval mode): forward = BatchNorm fold + device-side packing in both roles + the conv stack with every
-    activation kept (nd_unet_grad_forward), backward = nd_unet_grad_backward.  The backward computes only what autograd asks for:
-    the parameter gradients (no weight-gradient launch at all when no parameter requires one) and the input's gradient."""
-
-    @staticmethod
-    def forward(ctx, model, names, x, *params):
-        st = model._grad_state(x.device)
-        st.load(dict(zip(names, params)))
-        st.load(dict(model.named_buffers()))
-        batch, h, w = x.size(0), x.size(2), x.size(3)
-        y = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            ws = st.workspace(h, w, batch)
-            _lib.check(_lib.load().nd_unet_grad_forward(model.grad_flags, st.flat.data_ptr(), st.blobs.data_ptr(), x.data_ptr(),
-                                                        y.data_ptr(), batch, h, w, ws.data_ptr(), ws.numel(),
-                                                        _lib.stream_ptr(x.device)), "nd_unet_grad_forward")
-        st.generation += 1
-        ctx.model, ctx.names, ctx.geom, ctx.generation, ctx.flags = model, names, (batch, h, w), st.generation, model.grad_flags
-        ctx.shapes = [p.shape for p in params]
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        model = ctx.model
-        st = model._grad_state(gy.device)
-        if st.generation != ctx.generation:
-            raise RuntimeError("UNet backward: another forward of this module ran under autograd since this graph was built; its "
-                               "activations are gone (one forward/backward in flight per module)")
-        batch, h, w = ctx.geom
-        want_dx, want_p = ctx.needs_input_grad[2], ctx.needs_input_grad[3:]
-        gy = gy.to(torch.float32).contiguous()
-        dx = torch.empty(batch, 3, h, w, dtype=torch.float32, device=gy.device) if want_dx else None
-        if want_dx or any(want_p):
-            with torch.cuda.device(gy.device):
-                _lib.check(_lib.load().nd_unet_grad_backward(ctx.flags, st.flat.data_ptr(), st.grads.data_ptr() if any(want_p) else None,
-                                                             st.blobs.data_ptr(), gy.data_ptr(), dx.data_ptr() if want_dx else None,
-                                                             batch, h, w, st.ws.data_ptr(), st.ws.numel(), _lib.stream_ptr(gy.device)),
-                           "nd_unet_grad_backward")
-        grads = []
-        for n, shape, want in zip(ctx.names, ctx.shapes, want_p):
-            off, cnt = st.ranges[n]
-            grads.append(st.grads[off:off + cnt].view(shape).clone() if want else None)
-        return (None, None, dx) + tuple(grads)
 
 
 class UNet(nn.Module):
@@ -181,24 +94,40 @@ class UNet(nn.Module):
         """flags of nd_unet_grad_forward / nd_unet_grad_backward"""
         return (0 if self.split_k else _lib.FLAG_NO_SPLITK) | (_lib.FLAG_FIND_NOISE if self.find_noise else 0)
 
+    # ------------------------------------------------------------------ under autograd in eval mode (NetFunction): BatchNorm fold +
+    # device-side packing in both roles + the conv stack with every activation kept, then nd_unet_grad_backward
+    _autograd_buffers = True       # the running statistics have slots in the flat layout: the fold reads one array
+    _autograd_stale = ("UNet backward: another forward of this module ran under autograd since this graph was built; its "
+                       "activations are gone (one forward/backward in flight per module)")
+
     def _grad_state(self, device):
         st = getattr(self, "_gstate", None)
         if st is None or st.device != device:
-            st = self._gstate = _GradState(device)
+            lib = _lib.load()
+            st = self._gstate = FlatState(device, _lib.unet_ranges(), lib.nd_unet_param_count(), lib.nd_unet_grad_blob_bytes(),
+                                          (lib.nd_unet_grad_workspace_bytes, lib.nd_unet_grad_workspace_init, (), "UNet under autograd"))
         return st
+
+    _autograd_state = _grad_state
+
+    def _abi_forward(self, st, x, y, geom, ws):
+        flags = self.grad_flags         # recorded: the backward repeats them whatever the module's switches say by then
+        _lib.check(_lib.load().nd_unet_grad_forward(flags, st.flat.data_ptr(), st.blobs.data_ptr(), x.data_ptr(), y.data_ptr(), *geom,
+                                                    ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device)), "nd_unet_grad_forward")
+        return flags
+
+    def _abi_backward(self, st, flags, grads, gy, dx, geom):
+        _lib.check(_lib.load().nd_unet_grad_backward(flags, st.flat.data_ptr(), grads, st.blobs.data_ptr(), gy.data_ptr(), dx, *geom,
+                                                     st.ws.data_ptr(), st.ws.numel(), _lib.stream_ptr(gy.device)),
+                   "nd_unet_grad_backward")
 
     def workspace(self, h, w, batch, device):
         key = (str(device), h, w, batch)
         ws = self._workspaces.get(key)
         if ws is None:
             lib = _lib.load()
-            nbytes = lib.nd_unet_workspace_bytes(h, w, batch, _lib.ND_F32)
-            if nbytes == 0:
-                _lib.check(lib.nd_unet_workspace_init(None, 0, h, w, batch, _lib.ND_F32, None), "UNet")
-            self._workspaces.clear()
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            _lib.check(lib.nd_unet_workspace_init(ws.data_ptr(), nbytes, h, w, batch, _lib.ND_F32, _lib.stream_ptr(device)),
-                       "nd_unet_workspace_init")
+            ws = _lib.make_workspace(lib.nd_unet_workspace_bytes, lib.nd_unet_workspace_init, (h, w, batch, _lib.ND_F32), device, "UNet",
+                                     drop=self._workspaces.clear)
             self._workspaces[key] = ws
         return ws
 
@@ -214,7 +143,7 @@ class UNet(nn.Module):
             # get one -- fine-tuning with frozen statistics; an input that needs no gradient takes the inference path below,
             # whose output carries no graph
             named = list(self.named_parameters())
-            return _UNetFunction.apply(self, tuple(n for n, _ in named), x.to(torch.float32).contiguous(), *[p for _, p in named])
+            return NetFunction.apply(self, tuple(n for n, _ in named), x.to(torch.float32).contiguous(), *[p for _, p in named])
         x = x.detach().to(torch.float32).contiguous()
         b, _, h, w = x.shape
         lib = _lib.load()

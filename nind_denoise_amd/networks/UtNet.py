@@ -13,6 +13,7 @@ import torch
 from torch import nn
 
 from .. import _lib
+from ._autograd import FlatState, NetFunction
 from ..synth import utnet_layer_table, utnet_prelu_keys
 
 _ACTIVATIONS = {"PReLU": nn.PReLU, "ELU": nn.ELU, "Hardswish": nn.Hardswish}
@@ -34,92 +35,6 @@ def valid_cs(cs):
 def nearest_valid_cs(cs):
     k = (cs - 56 + 8) // 16          # ties go up: 256 -> 264, 512 -> 520, 128 -> 136
     return max(104, 16 * k + 56)
-
-
-class _TrainState:
-    """Flat parameter / gradient buffers, packed-weight blobs and the training workspace of one module on one device
-    (nd_utnet_train_forward_hw / nd_utnet_train_backward_hw of include/nind_hip.h)."""
-
-    def __init__(self, model, device):
-        lib = _lib.load()
-        self.device = device
-        n = lib.nd_utnet_param_count(model.funit)
-        if n == 0:
-            raise ValueError(f"UtNet: funit={model.funit} is not supported by the HIP training path (multiple of 8)")
-        self.flat = torch.zeros(n, dtype=torch.float32, device=device)
-        self.grads = torch.zeros(n, dtype=torch.float32, device=device)
-        self.blobs = torch.empty(lib.nd_utnet_train_blob_bytes(model.funit), dtype=torch.uint8, device=device)
-        self.ranges = {}
-        for i, name in enumerate(_lib.utnet_tensor_names()):
-            off, cnt = ctypes.c_size_t(), ctypes.c_size_t()
-            _lib.check(lib.nd_utnet_param_range(model.funit, i, off, cnt))
-            self.ranges[name] = (off.value, cnt.value)
-        self.ws, self.ws_key = None, None
-        self.generation = 0          # bumped by every forward: a backward must follow ITS forward
-
-    def workspace(self, model, h, w, batch):
-        if self.ws_key != (h, w, batch):
-            lib = _lib.load()
-            nbytes = lib.nd_utnet_train_workspace_bytes_hw(model.funit, h, w, batch)
-            if nbytes == 0:
-                _lib.check(lib.nd_utnet_train_workspace_init_hw(None, 0, model.funit, h, w, batch, None), "UtNet training")
-            self.ws = None
-            self.ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(lib.nd_utnet_train_workspace_init_hw(self.ws.data_ptr(), nbytes, model.funit, h, w, batch,
-                                                            _lib.stream_ptr(self.device)), "nd_utnet_train_workspace_init_hw")
-            self.ws_key = (h, w, batch)
-        return self.ws
-
-
-class _UtNetFunction(torch.autograd.Function):
-    """UtNet.forward under autograd: forward = device-side weight packing + the conv stack with the pre-activations kept
-    (nd_utnet_train_forward_hw), backward = activation / bias / weight / data gradients of every layer
-    (nd_utnet_train_backward_hw), the kernels of the fused training step (csrc/utnet_train.hip).  The backward computes only
-    what autograd asks for: the parameter gradients (skipped when no parameter requires one) and the input image's gradient
-    (the first layer's data gradient through the input's reflection padding, when x requires one)."""
-
-    @staticmethod
-    def forward(ctx, model, names, x, *params):
-        st = model._train_state(x.device)
-        with torch.no_grad():
-            for n, p in zip(names, params):
-                off, cnt = st.ranges[n]
-                st.flat[off:off + cnt].copy_(p.detach().reshape(-1))
-        batch, h, w = x.size(0), x.size(2), x.size(3)
-        y = torch.empty_like(x)
-        with torch.cuda.device(x.device):
-            ws = st.workspace(model, h, w, batch)
-            _lib.check(_lib.load().nd_utnet_train_forward_hw(model.funit, _lib.ACT[model.activation], model.flags,
-                                                             st.flat.data_ptr(), st.blobs.data_ptr(), x.data_ptr(), y.data_ptr(),
-                                                             batch, h, w, ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device)),
-                       "nd_utnet_train_forward_hw")
-        st.generation += 1
-        ctx.model, ctx.names, ctx.geom, ctx.generation = model, names, (batch, h, w), st.generation
-        ctx.shapes = [p.shape for p in params]
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        model = ctx.model
-        st = model._train_state(gy.device)
-        if st.generation != ctx.generation:
-            raise RuntimeError("UtNet backward: another forward of this module ran under autograd since this graph was built; its "
-                               "activations are gone (one forward/backward in flight per module -- as the reference's training loop runs)")
-        batch, h, w = ctx.geom
-        want_dx, want_p = ctx.needs_input_grad[2], ctx.needs_input_grad[3:]
-        gy = gy.to(torch.float32).contiguous()
-        dx = torch.empty(batch, 3, h, w, dtype=torch.float32, device=gy.device) if want_dx else None
-        with torch.cuda.device(gy.device):
-            _lib.check(_lib.load().nd_utnet_train_backward_hw(model.funit, _lib.ACT[model.activation], model.flags,
-                                                              st.flat.data_ptr(), st.grads.data_ptr() if any(want_p) else None,
-                                                              st.blobs.data_ptr(), gy.data_ptr(), dx.data_ptr() if want_dx else None,
-                                                              batch, h, w, st.ws.data_ptr(), st.ws.numel(), _lib.stream_ptr(gy.device),
-                                                              None, 0), "nd_utnet_train_backward_hw")
-        grads = []
-        for n, shape, want in zip(ctx.names, ctx.shapes, want_p):
-            off, cnt = st.ranges[n]
-            grads.append(st.grads[off:off + cnt].view(shape).clone() if want else None)
-        return (None, None, dx) + tuple(grads)
 
 
 class UtNet(nn.Module):
@@ -257,14 +172,12 @@ class UtNet(nn.Module):
         ws = self._workspaces.get(key)
         if ws is None:
             lib = _lib.load()
-            nbytes = lib.nd_utnet_workspace_bytes_hw(self.funit, h, w, batch, self._dt)
-            if nbytes == 0:
-                _lib.check(lib.nd_utnet_workspace_init_hw(None, 0, self.funit, h, w, batch, self._dt, None), "UtNet")
-            while len(self._workspaces) >= self.max_cached_workspaces:
-                self._workspaces.pop(next(iter(self._workspaces)))
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            _lib.check(lib.nd_utnet_workspace_init_hw(ws.data_ptr(), nbytes, self.funit, h, w, batch, self._dt,
-                                                      _lib.stream_ptr(device)), "nd_utnet_workspace_init_hw")
+
+            def drop():
+                while len(self._workspaces) >= self.max_cached_workspaces:
+                    self._workspaces.pop(next(iter(self._workspaces)))
+            ws = _lib.make_workspace(lib.nd_utnet_workspace_bytes_hw, lib.nd_utnet_workspace_init_hw, (self.funit, h, w, batch, self._dt),
+                                     device, "UtNet", drop=drop)
             self._workspaces[key] = ws
         return ws
 
@@ -306,8 +219,7 @@ class UtNet(nn.Module):
             if self.compute_dtype != "f32":
                 raise NotImplementedError("UtNet under autograd runs in fp32 (the training step's arithmetic)")
             named = [(n, p) for n, p in self.named_parameters()]
-            return _UtNetFunction.apply(self, tuple(n for n, _ in named), l.to(torch.float32).contiguous(),
-                                        *[p for _, p in named])
+            return NetFunction.apply(self, tuple(n for n, _ in named), l.to(torch.float32).contiguous(), *[p for _, p in named])
         x = l.detach().to(torch.float32).contiguous()
         lib = _lib.load()
         with torch.cuda.device(x.device):
@@ -319,11 +231,36 @@ class UtNet(nn.Module):
                                                _lib.stream_ptr(x.device)), "nd_utnet_forward_hw")
         return y
 
+    # ------------------------------------------------------------------ under autograd (NetFunction): the kernels of the fused
+    # training step (csrc/utnet_train.hip); the input's gradient runs through the input's reflection padding
+    _autograd_buffers = False
+    _autograd_stale = ("UtNet backward: another forward of this module ran under autograd since this graph was built; its "
+                       "activations are gone (one forward/backward in flight per module -- as the reference's training loop runs)")
+
     def _train_state(self, device):
         st = getattr(self, "_tstate", None)
         if st is None or st.device != device:
-            st = self._tstate = _TrainState(self, device)
+            lib = _lib.load()
+            n = lib.nd_utnet_param_count(self.funit)
+            if n == 0:
+                raise ValueError(f"UtNet: funit={self.funit} is not supported by the HIP training path (multiple of 8)")
+            st = self._tstate = FlatState(device, _lib.utnet_ranges(self.funit), n, lib.nd_utnet_train_blob_bytes(self.funit),
+                                          (lib.nd_utnet_train_workspace_bytes_hw, lib.nd_utnet_train_workspace_init_hw, (self.funit,),
+                                           "UtNet training"))
         return st
+
+    _autograd_state = _train_state
+
+    def _abi_forward(self, st, x, y, geom, ws):
+        _lib.check(_lib.load().nd_utnet_train_forward_hw(self.funit, _lib.ACT[self.activation], self.flags, st.flat.data_ptr(),
+                                                         st.blobs.data_ptr(), x.data_ptr(), y.data_ptr(), *geom, ws.data_ptr(),
+                                                         ws.numel(), _lib.stream_ptr(x.device)), "nd_utnet_train_forward_hw")
+
+    def _abi_backward(self, st, flags, grads, gy, dx, geom):      # flags: None, the module's are read now; no bucket events
+        _lib.check(_lib.load().nd_utnet_train_backward_hw(self.funit, _lib.ACT[self.activation], self.flags, st.flat.data_ptr(), grads,
+                                                          st.blobs.data_ptr(), gy.data_ptr(), dx, *geom, st.ws.data_ptr(),
+                                                          st.ws.numel(), _lib.stream_ptr(gy.device), None, 0),
+                   "nd_utnet_train_backward_hw")
 
     def flops_per_tile(self, cs):
         return _lib.load().nd_utnet_flops(self.funit, cs)

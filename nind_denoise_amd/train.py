@@ -13,10 +13,9 @@ The module's parameters are views into ONE flat fp32 buffer in state-dict order;
 buffer with the same layout, so the optimizer is one kernel and the data-parallel reduction runs on nine contiguous level
 buckets of that buffer, each all-reduced as soon as the backward pass has finished it (dist.BucketedGradientAverager).
 
-UNetTrainer, below, is the same surface for UNet: BatchNorm on the statistics of the batch (csrc/unet_train.hip), one GPU.
+UNetTrainer, below, is the same surface for UNet: BatchNorm on the statistics of the batch (csrc/unet_grad.hip in train mode,
+csrc/unet_bn.hip), one GPU.  Both stand on _GuardedStep: the optimizer (csrc/optim.hip), its guard and the trainer's state dict.
 """
-import ctypes
-
 import torch
 
 from . import _lib
@@ -25,7 +24,9 @@ from .networks.UtNet import UtNet, valid_cs
 
 
 class _GuardedStep:
-    """What UtNetTrainer and UNetTrainer share behind the optimizer: the guarded step and the trainer's state dict.
+    """The base of UtNetTrainer and UNetTrainer: device and loss-weight checks, Adam's buffers and step (plain or guarded), learn,
+    the learning rate, grad_of and the trainer's state dict.  A subclass lays out self.flat and supplies forward_backward and
+    _weights_written.
 
     max_grad_norm (None: off): the gradient is clipped to this global L2 norm, torch.nn.utils.clip_grad_norm_'s coefficient.
     skip_nonfinite: a step whose gradient holds a NaN or an infinity is not applied -- parameters, m, v and vmax keep their bits.
@@ -35,7 +36,42 @@ class _GuardedStep:
     Nothing is read back: `steps` counts attempts, so a skipped step still advances Adam's bias-correction index (unlike
     torch.cuda.amp.GradScaler, which skips optimizer.step()).  The clipped gradient is never stored: self.grads and grad_of keep
     the unclipped one."""
-    kind = None
+    kind, data_parallel = None, True
+
+    def _init_base(self, model, device, process_group, weights, lr, betas, eps, amsgrad, loss_cs):
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{self.kind} needs a GPU (no CPU fallback)")
+        if process_group is not None and not self.data_parallel:      # (refused, like the weights, before the device is touched)
+            raise NotImplementedError(f"{self.kind}: data-parallel UNet training is not available (the bucketed gradient averager "
+                                      "is laid out for UtNet)")
+        self.group = process_group
+        self.weights = {"L1": 0.0, "MSE": 1.0} if weights is None else dict(weights)
+        unknown = set(k for k, v in self.weights.items() if v) - {"L1", "MSE", "SSIM", "MSSSIM"}
+        if unknown:   # D1 / D2: the discriminator terms of the reference's GAN mode (nn_common.py:178-182)
+            raise NotImplementedError(f"loss terms {sorted(unknown)} are not available (generator losses: L1, MSE, SSIM, MSSSIM)")
+        self.model = model.to(self.device)
+        self.lib = _lib.load()
+        self.lr, self.betas, self.eps, self.amsgrad = lr, betas, eps, amsgrad
+        self.loss_cs = loss_cs        # centre crop the criteria see (nn_train.py:319-323 --loss_cs); None: the whole crop
+
+    def _init_optimizer(self, max_grad_norm, skip_nonfinite):
+        """Everything sized by self.flat: the gradient buffer (slots nothing writes stay 0), Adam's moments, the guard."""
+        self.grads = torch.zeros_like(self.flat)
+        self.m = torch.zeros_like(self.flat)
+        self.v = torch.zeros_like(self.flat)
+        self.vmax = torch.zeros_like(self.flat)
+        self.steps = 0
+        self._ws = {}
+        self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._init_guard(max_grad_norm, skip_nonfinite)
+
+    def _workspace(self, key, size_fn, init_fn, args, what):
+        """The training workspace for `key` (initialised once, then cached; another key replaces it)."""
+        ws = self._ws.get(key)
+        if ws is None:
+            ws = self._ws[key] = _lib.make_workspace(size_fn, init_fn, args, self.device, what, drop=self._ws.clear)
+        return ws
 
     def _init_guard(self, max_grad_norm, skip_nonfinite):
         if max_grad_norm is not None:
@@ -65,8 +101,25 @@ class _GuardedStep:
         _lib.check(self.lib.nd_adam_step_guarded(*adam, self.guard_state.data_ptr(), _lib.stream_ptr(self.device)),
                    "nd_adam_step_guarded")
 
-    def _weights_written(self):
-        raise NotImplementedError
+    def optimizer_step(self):
+        self.steps += 1
+        with torch.cuda.device(self.device):
+            self._adam()      # (UNet's running statistics: gradient and moments 0 -> an update of exactly 0, the slots keep their bits)
+        self._weights_written()
+
+    def learn(self, noisy, clean):
+        """One generator update (Generator.denoise_batch + learn of the reference); returns the loss as a float tensor."""
+        _, loss = self.forward_backward(noisy, clean)
+        self.optimizer_step()
+        return loss
+
+    def grad_of(self, name):
+        off, cnt = self.ranges[name]
+        return self.grads[off:off + cnt].view_as(self.model.state_dict()[name])
+
+    def update_learning_rate(self, lr_decay):
+        self.lr *= lr_decay
+        return self.lr
 
     def state_dict(self):
         """Everything the next step reads, as CPU copies: the flat parameter buffer (UNet: with the running statistics), Adam's
@@ -104,63 +157,33 @@ class UtNetTrainer(_GuardedStep):
 
     def __init__(self, model: UtNet, lr=1e-4, beta1=0.75, beta2=0.999, eps=1e-8, amsgrad=True,
                  weights=None, device=None, process_group=None, loss_cs=None, max_grad_norm=None, skip_nonfinite=False):
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise RuntimeError("UtNetTrainer needs a GPU (no CPU fallback)")
-        self.model = model.to(self.device)
-        self.lib = _lib.load()
+        self._init_base(model, device, process_group, weights, lr, (beta1, beta2), eps, amsgrad, loss_cs)
         self.funit = model.funit
-        self.weights = {"L1": 0.0, "MSE": 1.0} if weights is None else dict(weights)
-        unknown = set(k for k, v in self.weights.items() if v) - {"L1", "MSE", "SSIM", "MSSSIM"}
-        if unknown:   # D1 / D2: the discriminator terms of the reference's GAN mode (nn_common.py:178-182)
-            raise NotImplementedError(f"loss terms {sorted(unknown)} are not available (generator losses: L1, MSE, SSIM, MSSSIM)")
-        self.lr, self.betas, self.eps, self.amsgrad = lr, (beta1, beta2), eps, amsgrad
-        self.group = process_group
-        self.loss_cs = loss_cs        # centre crop the criteria see (nn_train.py:319-323 --loss_cs); None: the whole crop
         n = self.lib.nd_utnet_param_count(self.funit)
         if n == 0:
             raise ValueError(f"funit={self.funit} is not supported")
         self.flat = torch.zeros(n, dtype=torch.float32, device=self.device)
-        self.grads = torch.zeros_like(self.flat)
         sd = dict(model.named_parameters())
         self.ranges = {}
-        for i, name in enumerate(_lib.utnet_tensor_names()):
-            off, cnt = ctypes.c_size_t(), ctypes.c_size_t()
-            _lib.check(self.lib.nd_utnet_param_range(self.funit, i, off, cnt))
+        for name, (off, cnt) in _lib.utnet_ranges(self.funit).items():
             if name not in sd:                 # a PReLU slope of a network with another activation: the step ignores its slot
                 continue
             p = sd[name]
-            assert p.numel() == cnt.value, (name, p.numel(), cnt.value)
-            view = self.flat[off.value:off.value + cnt.value].view_as(p)
+            assert p.numel() == cnt, (name, p.numel(), cnt)
+            view = self.flat[off:off + cnt].view_as(p)
             view.copy_(p.data)
             p.data = view                      # the module now reads / writes the flat buffer
-            self.ranges[name] = (off.value, cnt.value)
-        self.m = torch.zeros_like(self.flat)
-        self.v = torch.zeros_like(self.flat)
-        self.vmax = torch.zeros_like(self.flat)
-        self.steps = 0
+            self.ranges[name] = (off, cnt)
         self.blobs = torch.empty(self.lib.nd_utnet_train_blob_bytes(self.funit), dtype=torch.uint8, device=self.device)
-        self._ws = {}
-        self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._init_optimizer(max_grad_norm, skip_nonfinite)
         # data parallel: the gradient mean runs bucket by bucket (one per network level) under the rest of the backward pass
         self.averager = BucketedGradientAverager(self.funit, self.grads, self.group)
-        self._init_guard(max_grad_norm, skip_nonfinite)
 
     def workspace(self, h, batch, w=None):
         """Training workspace for [batch,3,h,w or h] crops (zero borders initialised once, then cached)."""
         w = h if w is None else w
-        key = (h, w, batch)
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = self.lib.nd_utnet_train_workspace_bytes_hw(self.funit, h, w, batch)
-            if nbytes == 0:
-                _lib.check(self.lib.nd_utnet_train_workspace_init_hw(None, 0, self.funit, h, w, batch, None), "UtNet training")
-            self._ws.clear()
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(self.lib.nd_utnet_train_workspace_init_hw(ws.data_ptr(), nbytes, self.funit, h, w, batch,
-                                                                 _lib.stream_ptr(self.device)), "nd_utnet_train_workspace_init_hw")
-            self._ws[key] = ws
-        return ws
+        return self._workspace((h, w, batch), self.lib.nd_utnet_train_workspace_bytes_hw, self.lib.nd_utnet_train_workspace_init_hw,
+                               (self.funit, h, w, batch), "UtNet training")
 
     def forward_backward(self, noisy, clean):
         """Forward + loss + backward; fills self.grads (averaged over the process group).  Returns (output, loss tensor)."""
@@ -195,41 +218,13 @@ class UtNetTrainer(_GuardedStep):
         return validate(self.model, validation_set, self.weights, self.loss_cs, batch_size=batch_size, output_to_dir=output_to_dir,
                         also=also, group=self.group)
 
-    def optimizer_step(self):
-        self.steps += 1
-        with torch.cuda.device(self.device):
-            self._adam()
-        self._weights_written()
-
     def _weights_written(self):
         # the parameters were rewritten through raw pointers (torch's version counters did not move): the inference blob the
         # module cached before this step is stale
         self.model.weights_generation += 1
 
-    def learn(self, noisy, clean):
-        """One generator update (Generator.denoise_batch + learn of the reference); returns the loss as a float tensor."""
-        _, loss = self.forward_backward(noisy, clean)
-        self.optimizer_step()
-        return loss
 
-    def grad_of(self, name):
-        off, cnt = self.ranges[name]
-        return self.grads[off:off + cnt].view_as(dict(self.model.named_parameters())[name])
-
-    def update_learning_rate(self, lr_decay):
-        self.lr *= lr_decay
-        return self.lr
-
-
-def unet_ranges():
-    """{tensor name: (offset, count)} of the flat UNet layout (nd_unet_param_range): parameters and running statistics."""
-    lib = _lib.load()
-    ranges = {}
-    for i in range(lib.nd_unet_num_tensors()):
-        off, cnt = ctypes.c_size_t(), ctypes.c_size_t()
-        _lib.check(lib.nd_unet_param_range(i, off, cnt))
-        ranges[lib.nd_unet_tensor_name(i).decode()] = (off.value, cnt.value)
-    return ranges
+unet_ranges = _lib.unet_ranges
 
 
 def unet_flatten(model, flat, ranges):
@@ -273,25 +268,11 @@ class UNetTrainer(_GuardedStep):
 
     max_grad_norm / skip_nonfinite (_GuardedStep) protect the parameter update only: a non-finite forward has already moved the
     BatchNorm running statistics and num_batches_tracked by the time the gradient is looked at."""
-    kind = "UNetTrainer"
+    kind, data_parallel = "UNetTrainer", False
 
     def __init__(self, model, lr=1e-4, beta1=0.75, beta2=0.999, eps=1e-8, amsgrad=True,
                  weights=None, device=None, process_group=None, loss_cs=None, max_grad_norm=None, skip_nonfinite=False):
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type != "cuda":
-            raise RuntimeError("UNetTrainer needs a GPU (no CPU fallback)")
-        if process_group is not None:
-            raise NotImplementedError("UNetTrainer: data-parallel UNet training is not available (the bucketed gradient averager "
-                                      "is laid out for UtNet)")
-        self.weights = {"L1": 0.0, "MSE": 1.0} if weights is None else dict(weights)
-        unknown = set(k for k, v in self.weights.items() if v) - {"L1", "MSE", "SSIM", "MSSSIM"}
-        if unknown:
-            raise NotImplementedError(f"loss terms {sorted(unknown)} are not available (generator losses: L1, MSE, SSIM, MSSSIM)")
-        self.model = model.to(self.device)
-        self.lib = _lib.load()
-        self.lr, self.betas, self.eps, self.amsgrad = lr, (beta1, beta2), eps, amsgrad
-        self.group = None
-        self.loss_cs = loss_cs
+        self._init_base(model, device, process_group, weights, lr, (beta1, beta2), eps, amsgrad, loss_cs)
         bns = [m for m in self.model.modules() if isinstance(m, torch.nn.BatchNorm2d)]
         momenta = {m.momentum for m in bns}
         if len(momenta) != 1 or None in momenta:
@@ -301,16 +282,9 @@ class UNetTrainer(_GuardedStep):
         self.ranges = unet_ranges()
         self.flat = torch.zeros(self.lib.nd_unet_param_count(), dtype=torch.float32, device=self.device)
         unet_flatten(self.model, self.flat, self.ranges)
-        self.grads = torch.zeros_like(self.flat)      # the slots of running statistics are never written: they stay 0
-        self.m = torch.zeros_like(self.flat)
-        self.v = torch.zeros_like(self.flat)
-        self.vmax = torch.zeros_like(self.flat)
-        self.steps = 0
         self.blobs = torch.empty(self.lib.nd_unet_train_blob_bytes(), dtype=torch.uint8, device=self.device)
-        self._ws = {}
         self._loss_ws = None
-        self.loss = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self._init_guard(max_grad_norm, skip_nonfinite)
+        self._init_optimizer(max_grad_norm, skip_nonfinite)      # (grads: the slots of running statistics are never written)
 
     @property
     def flags(self):
@@ -318,18 +292,8 @@ class UNetTrainer(_GuardedStep):
 
     def workspace(self, h, w, batch):
         """Training workspace for [batch,3,h,w] crops (zeroed once, then cached; another shape replaces it)."""
-        key = (h, w, batch)
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = self.lib.nd_unet_train_workspace_bytes(h, w, batch)
-            if nbytes == 0:
-                _lib.check(self.lib.nd_unet_train_workspace_init(None, 0, h, w, batch, None), "UNet training")
-            self._ws.clear()
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            _lib.check(self.lib.nd_unet_train_workspace_init(ws.data_ptr(), nbytes, h, w, batch, _lib.stream_ptr(self.device)),
-                       "nd_unet_train_workspace_init")
-            self._ws[key] = ws
-        return ws
+        return self._workspace((h, w, batch), self.lib.nd_unet_train_workspace_bytes, self.lib.nd_unet_train_workspace_init, (h, w, batch),
+                               "UNet training")
 
     def _loss_workspace(self, batch, h, w):
         nbytes = self.lib.nd_criteria_grad_workspace_bytes(batch, h, w, int(self.loss_cs or 0))
@@ -392,13 +356,6 @@ class UNetTrainer(_GuardedStep):
             self.backward(gy)
         return y, self.loss
 
-    def optimizer_step(self):
-        self.steps += 1
-        with torch.cuda.device(self.device):
-            # running statistics: gradient and moments 0 -> an update of exactly 0, the slots keep their bits
-            self._adam()
-        self._weights_written()
-
     def _weights_written(self):
         self.model._packed = None      # written through raw pointers: see forward
 
@@ -412,17 +369,3 @@ class UNetTrainer(_GuardedStep):
         with torch.no_grad():
             for t, value in zip(self._tracked, state["num_batches_tracked"]):
                 t.fill_(value)
-
-    def learn(self, noisy, clean):
-        """One generator update; returns the loss as a float tensor."""
-        _, loss = self.forward_backward(noisy, clean)
-        self.optimizer_step()
-        return loss
-
-    def grad_of(self, name):
-        off, cnt = self.ranges[name]
-        return self.grads[off:off + cnt].view_as(self.model.state_dict()[name])
-
-    def update_learning_rate(self, lr_decay):
-        self.lr *= lr_decay
-        return self.lr

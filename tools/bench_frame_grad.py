@@ -71,7 +71,7 @@ def main():
 
     frame_leg(True)                       # warm-up: packs the weights, allocates the workspaces, fills the flat parameters
     st = net._train_state(dev)
-    ws = st.workspace(net, cs, cs, batch)
+    ws = st.workspace(cs, cs, batch)
     s = _lib.stream_ptr(dev)
     act, flags = _lib.ACT[net.activation], net.flags
     xb = pipeline.gather_tiles(img, cs, ucs, ol, total // 2, batch)
