@@ -114,18 +114,6 @@ extern "C" int nd_utnet_workspace_init_hw(void *ws, size_t ws_bytes, int funit, 
     return ND_OK;
 }
 
-static int forward_common(int funit, int act, int dtype, const void *packed, int batch_cap, int nimg, int h, int w,
-                          void *ws, size_t ws_bytes, Plan *out_plan) {
-    ND_TRY(check_net(funit, h, w, batch_cap, dtype));
-    if (act < ND_ACT_PRELU || act > ND_ACT_HARDSWISH) ND_FAIL(ND_EINVAL, "UtNet: unknown activation %d", act);
-    if (nimg <= 0 || nimg > batch_cap) ND_FAIL(ND_EINVAL, "UtNet: %d images with a workspace batch of %d", nimg, batch_cap);
-    if (!packed || !ws) ND_FAIL(ND_EINVAL, "UtNet: null pointer");
-    if (((uintptr_t)ws & 15) || ((uintptr_t)packed & 15)) ND_FAIL(ND_EINVAL, "UtNet: workspace / weights must be 16-byte aligned");
-    *out_plan = make_plan(funit, h, w, batch_cap, nimg, (char *)ws, dtype);
-    if (ws_bytes < out_plan->bytes) ND_FAIL(ND_ENOMEM, "UtNet workspace: %zu B given, %zu B needed", ws_bytes, out_plan->bytes);
-    return ND_OK;
-}
-
 extern "C" int nd_utnet_forward_hw(int funit, int act, int dtype, int flags, const void *packed, const float *x, float *y,
                                    int batch, int h, int w, void *ws, size_t ws_bytes, void *stream) {
     ND_TRY(nd_check_flags(flags));
@@ -166,298 +154,6 @@ extern "C" int nd_utnet_denoise_tiles(int funit, int act, int dtype, int flags, 
     const float *fw = blob + bl.off[kNumLayers - 1];
     ND_TRY(nd_launch_final1x1_stitch(pl.buf[T4B], funit, fw, fw + 3 * funit, 2, canvas, width, height, cs, ucs, ol,
                                      tile_begin, tile_count, s));
-    return ND_OK;
-}
-
-// ------------------------------------------------------------------ frame loop with the shared encoder (utnet_net.h: frame_plan)
-extern "C" size_t nd_utnet_frame_workspace_bytes(int funit, int dtype, int flags, int width, int height, int cs, int ucs, int ol,
-                                                 int batch) {
-    FramePlan fp;
-    if (nd_check_flags(flags, true) != ND_OK || frame_plan(funit, dtype, flags, width, height, cs, ucs, ol, batch, &fp) != ND_OK) return 0;
-    return fp.bytes;
-}
-
-extern "C" int nd_utnet_frame_plan(int funit, int dtype, int flags, int width, int height, int cs, int ucs, int ol, int *out) {
-    ND_TRY(nd_check_flags(flags, true));
-    if (!out) ND_FAIL(ND_EINVAL, "nd_utnet_frame_plan: null output");
-    FramePlan fp;
-    ND_TRY(frame_plan(funit, dtype, flags, width, height, cs, ucs, ol, 1, &fp));
-    const int v[8] = {fp.D, fp.aligned, fp.R, fp.nbands, fp.S, fp.cols, fp.rows, fp.hx};
-    memcpy(out, v, sizeof(v));
-    return ND_OK;
-}
-
-extern "C" int nd_utnet_frame_levels(int funit, int dtype, int flags, int width, int height, int cs, int ucs, int ol, int *levels) {
-    ND_TRY(nd_check_flags(flags, true));
-    if (!levels) ND_FAIL(ND_EINVAL, "nd_utnet_frame_levels: null output");
-    FramePlan fp;
-    ND_TRY(frame_plan(funit, dtype, flags, width, height, cs, ucs, ol, 1, &fp));
-    *levels = fp.levels;
-    return ND_OK;
-}
-
-extern "C" int nd_utnet_frame_folds(int funit, int dtype, int flags, int width, int height, int cs, int ucs, int ol, int *mask) {
-    ND_TRY(nd_check_flags(flags, true));
-    if (!mask) ND_FAIL(ND_EINVAL, "nd_utnet_frame_folds: null output");
-    FramePlan fp;
-    ND_TRY(frame_plan(funit, dtype, flags, width, height, cs, ucs, ol, 1, &fp));
-    *mask = fp.folds;
-    return ND_OK;
-}
-
-extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, const void *packed, const float *img, float *canvas,
-                                      int width, int height, int cs, int ucs, int ol, int tile_begin, int tile_count, int batch,
-                                      void *ws, size_t ws_bytes, void *fws, size_t fws_bytes, void *stream, nd_progress_fn progress,
-                                      void *progress_ctx) {
-    ND_TRY(nd_check_flags(flags, true));
-    FramePlan fp;
-    ND_TRY(frame_plan(funit, dtype, flags, width, height, cs, ucs, ol, batch, &fp));
-    if (tile_begin < 0 || tile_count < 0 || tile_begin + tile_count > fp.cols * fp.rows)
-        ND_FAIL(ND_EINVAL, "nd_utnet_denoise_frame: tiles [%d,+%d) outside the grid of %d", tile_begin, tile_count, fp.cols * fp.rows);
-    const int end = tile_begin + tile_count;
-    Plan pl;
-    ND_TRY(forward_common(funit, act, dtype, packed, batch, batch, cs, cs, ws, ws_bytes, &pl));
-    const BlobLayout bl = blob_layout(funit, dtype);
-    Roi rois[kNumSteps];
-    const int crop = (cs - ucs) / 2;
-    if (fp.D && !(plan_rois(pl, crop, crop, rois) && rois_supported(funit, dtype, flags, pl, bl, rois))) fp.D = 0;
-    if (fp.D == 0) {   // every tile runs its whole encoder: launches of `batch` tiles from tile_begin
-        int n = 0;
-        for (int t0 = tile_begin; t0 < end; t0 += batch, ++n) {
-            const int cnt = end - t0 < batch ? end - t0 : batch;
-            if (progress) progress(progress_ctx, n, t0, cnt);
-            ND_TRY(nd_utnet_denoise_tiles(funit, act, dtype, flags & ~(ND_FLAG_TILE_LEVEL2 | ND_FLAG_TILE_SKIPS), packed, img, canvas, width, height, cs, ucs, ol, t0, cnt, batch, ws,
-                                          ws_bytes, stream));
-        }
-        return ND_OK;
-    }
-    if (!img || !canvas) ND_FAIL(ND_EINVAL, "UtNet: null image");
-    if (!fws || fws_bytes < fp.bytes || ((uintptr_t)fws & 255))
-        ND_FAIL(ND_ENOMEM, "nd_utnet_denoise_frame: frame workspace %zu B given, %zu B needed (256-byte aligned)", fws_bytes, fp.bytes);
-    hipStream_t s = (hipStream_t)stream;
-    const float *blob = (const float *)packed;
-    const float *fw = blob + bl.off[kNumLayers - 1];
-    char *const band_base = (char *)fws, *const rows_base = band_base + fp.band_bytes, *const cols_base = rows_base + fp.row_edge_bytes;
-    char *const corner_base = cols_base + fp.col_edge_bytes;
-    int *const origins = (int *)(corner_base + fp.corner_bytes);
-    // level 2 (utnet_net.h: frame_plan_level2): a third origin table, then its band, line image and corner patch tensors and scratch
-    const bool l2 = fp.levels == 3;
-    char *const l2_band_base = (char *)origins + 3 * fp.origin_bytes, *const l2_rows_base = l2_band_base + fp.l2_band_bytes;
-    char *const l2_cols_base = l2_rows_base + fp.l2_row_bytes, *const l2_corner_base = l2_cols_base + fp.l2_col_bytes;
-    char *const l2_wino = l2_corner_base + fp.l2_corner_bytes;
-    const int f4 = funit / 4, cols = fp.cols, S = fp.S;
-    const int n2 = enc_extent(cs + 4, P2), n3 = l2_extent(n2, P3);
-    // the shared steps of a band / a set of edge images; level 2 of a band / a set of its images; the rest of a tile's stack, on
-    // the useful regions
-    StackOpts enc, enc2, dec;
-    enc.flags = enc2.flags = dec.flags = flags;
-    enc.step_end = enc2.step_begin = kSharedSteps;
-    enc2.step_end = kLevel2End;
-    dec.step_begin = l2 ? kLevel2End : kSharedSteps;
-    dec.rois = rois;
-    auto l2_scratch = [&](Plan p) {
-        p.split = pl.split;
-        p.wino = l2_wino;
-        p.wino_bytes = fp.l2_wino_bytes;
-        return p;
-    };
-    // The two decoder steps that read a skip half (tconvs4.0: CAT4, tconvs3.0: CAT3) take it from the band where their kernel has a
-    // second input source; else the window is copied into the tile buffer as the layer expects it (k_splice)
-    // (with level 2 also tconvs2.0: CAT2)
-    // A step the plan folds (utnet_net.h: frame_plan_folds) reads no skip at all: its window of the band's P is its addend
-    struct Skip { Buf cat; int planes, step, tstep; const int *win; int *table; bool in_place, fold; Form form; } skips[3] = {
-        {CAT4, f4, -1, S, fp.win4, origins, false, false, FORM_DIRECT},
-        {CAT3, 2 * f4, -1, S / 2, fp.win3, origins + fp.origin_bytes / sizeof(int), false, false, FORM_DIRECT},
-        {CAT2, 4 * f4, -1, S / 4, fp.win2, origins + 2 * fp.origin_bytes / sizeof(int), false, false, FORM_DIRECT}};
-    char *const fold_wino = (char *)fws + fp.bytes - fp.fold_wino_bytes;
-    const int nskips = l2 ? 3 : 2;
-    for (int ki = 0; ki < 3; ++ki)
-        for (int i = kSharedSteps; i < kNumSteps; ++i) {
-            Skip &k = skips[ki];
-            if (kSteps[i].layer >= 0 && kSteps[i].src == k.cat) {
-                const Form form = step_form(kSteps[i], funit, dtype, flags, pl, bl);
-                k.step = i;
-                k.in_place = form_takes_src2(kSteps[i], form, funit, flags, pl);
-                k.form = form;
-                k.fold = ki < nskips && ((fp.folds >> ki) & 1) && k.in_place;
-            }
-        }
-    StepSrc2 src2[3];
-    dec.src2 = src2;
-    // Bands are computed as the launches reach them, band b into slot b & 1 of the tensors the launches read (the P2 lines of its
-    // row and column edge images among them: a function of the frame geometry alone, as the band is); a launch takes `batch`
-    // tiles across a band seam and is cut at its second seam, so it reads two slots at most.  One stream: band b + 2 overwrites
-    // slot b & 1 only after the launches that read band b.  bf: the band plan at full height (slot 0) -- what a launch addresses,
-    // with each tile's band row and slot folded into its origin / its splice
-    const int per_band = fp.R * cols;
-    const Plan bf = make_enc_plan(funit, fp.hx, fp.wx, 1, fp.hx, fp.wx, 1, band_base, dtype, fp.slots);
-    const Plan bf2 = l2 ? l2_band_plan(fp, funit, dtype, fp.R, cs, l2_band_base) : Plan();
-    int band_done = tile_begin / per_band - 1;
-    for (int t0 = tile_begin, n = 0; t0 < end; ++n) {
-        const int b0 = t0 / per_band;
-        int cnt = end - t0 < batch ? end - t0 : batch;
-        if (t0 + cnt > (b0 + 2) * per_band) cnt = (b0 + 2) * per_band - t0;
-        for (int b = band_done + 1; b <= (t0 + cnt - 1) / per_band; ++b) {
-            // the band: its rows of tiles on the mirrored frame, steps [0, kSharedSteps) once
-            const int row0 = b * fp.R, nrows = fp.rows - row0 < fp.R ? fp.rows - row0 : fp.R;
-            Plan bp = band_slot(make_enc_plan(funit, band_hx(fp, nrows, cs), fp.wx, 1, fp.hx, fp.wx, 1, band_base, dtype, fp.slots), b & 1, fp.slots);
-            bp.split = pl.split;
-            ND_TRY(nd_launch_gather_band(img, width, height, cs, ucs, ol, row0, bp.buf[X0], s));
-            ND_TRY(run_stack(funit, act, dtype, blob, bp, s, enc));
-            for (int ki = 0; ki < 2; ++ki)
-                if (skips[ki].fold)
-                    ND_TRY(launch_skip_fold(funit, flags, blob, bl, skips[ki].step, skips[ki].form, bp.buf[skips[ki].cat], skips[ki].planes,
-                                            rois[skips[ki].step], skips[ki].tstep, nrows, cols, pl.split, fold_wino, fp.fold_wino_bytes, s));
-            // its edge images, the same steps: top / bottom rows of every tile row, left / right columns of every tile column
-            Plan re = band_slot(row_edge_plan(fp, funit, dtype, nrows, rows_base), b & 1, fp.slots, P2);
-            Plan ce = band_slot(col_edge_plan(fp, funit, dtype, nrows, cs, cols_base), b & 1, fp.slots, P2);
-            re.split = ce.split = pl.split;
-            ND_TRY(nd_launch_gather_edges(img, width, height, cs, ucs, ol, ND_EDGE_ROWS, row0, nrows, re.buf[X0], s));
-            ND_TRY(nd_launch_gather_edges(img, width, height, cs, ucs, ol, ND_EDGE_COLS, row0, nrows, ce.buf[X0], s));
-            ND_TRY(run_stack(funit, act, dtype, blob, re, s, enc));
-            ND_TRY(run_stack(funit, act, dtype, blob, ce, s, enc));
-            if (l2) {
-                // level 2 of the band on its P2, then of its line images: the P2 edge line of a tile row (column) next to the five
-                // clean band rows (columns) inside it
-                Plan b2 = l2_scratch(l2_slot(l2_band_plan(fp, funit, dtype, nrows, cs, l2_band_base), b & 1, fp.slots));
-                b2.buf[P2] = bp.buf[P2];
-                ND_TRY(run_stack(funit, act, dtype, blob, b2, s, enc2));
-                if (skips[2].fold)
-                    ND_TRY(launch_skip_fold(funit, flags, blob, bl, skips[2].step, skips[2].form, b2.buf[CAT2], skips[2].planes, rois[skips[2].step],
-                                            skips[2].tstep, nrows, cols, pl.split, fold_wino, fp.fold_wino_bytes, s));
-                const Plan r2 = l2_scratch(l2_slot(l2_row_plan(fp, funit, dtype, nrows, l2_rows_base), b & 1, fp.slots, P3));
-                const Plan c2 = l2_scratch(l2_slot(l2_col_plan(fp, funit, dtype, nrows, cs, l2_cols_base), b & 1, fp.slots, P3));
-                const int h2 = bp.buf[P2].Hb, w2 = bp.buf[P2].Wb;
-                for (int side = 0; side < 2; ++side) {
-                    // (splice: "tile" t = tile row t of the band on a grid of one column / tile column t on a grid of one row)
-                    const int at = side * (kStrip2 - 1), in0 = 1 - side, in1 = kStrip2 - side;
-                    SpliceMap br, lr, bc, lc;
-                    br.step_y = bc.step_x = S / 4;
-                    br.oy = bc.ox = side * (n2 - kStrip2);
-                    lr.img_y = lc.img_x = 2;
-                    lr.img_add = lc.img_add = side;
-                    lr.oy = lc.ox = -at;
-                    ND_TRY(nd_launch_splice(bp.buf[P2], 0, r2.buf[P2], 0, 2 * f4, 0, nrows, 1, 0, br, in0, in1, 0, w2, s, 0, 0, side * nrows));
-                    ND_TRY(nd_launch_splice(re.buf[P2], 0, r2.buf[P2], 0, 2 * f4, 0, nrows, 1, 0, lr, at, at + 1, 0, w2, s, 0, 0, side * nrows));
-                    ND_TRY(nd_launch_splice(bp.buf[P2], 0, c2.buf[P2], 0, 2 * f4, 0, cols, cols, 0, bc, 0, h2, in0, in1, s, 0, 0, side * cols));
-                    ND_TRY(nd_launch_splice(ce.buf[P2], 0, c2.buf[P2], 0, 2 * f4, 0, cols, cols, 0, lc, 0, h2, at, at + 1, s, 0, 0, side * cols));
-                }
-                ND_TRY(run_stack(funit, act, dtype, blob, r2, s, enc2));
-                ND_TRY(run_stack(funit, act, dtype, blob, c2, s, enc2));
-            }
-            band_done = b;
-        }
-        if (progress) progress(progress_ctx, n, t0, cnt);
-        // corner patches: images 4t ... 4t + 3 = top-left, top-right, bottom-left, bottom-right kStrip x kStrip pixels of tile t's input
-        Plan cp = corner_plan(funit, dtype, cnt, batch, corner_base);
-        cp.split = pl.split;
-        ND_TRY(nd_launch_gather_edges(img, width, height, cs, ucs, ol, ND_EDGE_CORNERS, t0, cnt, cp.buf[X0], s));
-        ND_TRY(run_stack(funit, act, dtype, blob, cp, s, enc));
-        // per tile: the skip halves where the decoder reads them, P2 whole, then P2's border lines and corner pixels
-        const Plan tp = make_plan(funit, cs, cs, batch, cnt, (char *)ws, dtype);
-        dec.nsrc2 = 0;
-        for (int ki = 0; ki < nskips; ++ki) {
-            const Skip &k = skips[ki];
-            const QpBuf &src = k.cat == CAT2 ? bf2.buf[k.cat] : bf.buf[k.cat];
-            if (!k.in_place && !k.fold) {
-                SpliceMap m;
-                m.step_y = m.step_x = k.tstep;
-                ND_TRY(nd_launch_splice(src, k.planes, tp.buf[k.cat], k.planes, k.planes, t0, cnt, cols, 0, m, k.win[0], k.win[1], k.win[0],
-                                        k.win[1], s, fp.R, slot_elems(src, fp.slots)));
-                continue;
-            }
-            StepSrc2 &q = src2[dec.nsrc2++];
-            q.step = k.step;
-            q.buf = src;
-            q.plane0 = q.from = k.planes;   // the skip is the upper half of the concat in the band as in the tile
-            q.addend = k.fold;
-            if (k.fold) {   // P: the lower half, an n + 2 output inside the n + 4 bordered plane
-                q.plane0 = 0;
-                q.buf.pad = 1;
-            }
-            q.origin = k.table;
-            ND_TRY(nd_launch_skip_origins(src, tp.buf[k.cat].pad, t0, cnt, cols, fp.R, k.tstep, slot_elems(src, fp.slots), k.table,
-                                          &q.origin_max, s));
-        }
-        SpliceMap whole;
-        whole.step_y = whole.step_x = S / 4;
-        ND_TRY(nd_launch_splice(bf.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, whole, 0, n2, 0, n2, s, fp.R,
-                                slot_elems(bf.buf[P2], fp.slots)));
-        // rows 0 / n2 - 1 and columns 0 / n2 - 1: the tile's window of its tile row's / tile column's lines (side 0 / 1), band by
-        // band of the launch -- the column images of a short last band are shorter
-        for (int b = b0; b <= (t0 + cnt - 1) / per_band; ++b) {
-            const int lo = t0 > b * per_band ? t0 : b * per_band, hi = t0 + cnt < (b + 1) * per_band ? t0 + cnt : (b + 1) * per_band;
-            const int row0 = b * fp.R, nrows = fp.rows - row0 < fp.R ? fp.rows - row0 : fp.R;
-            const QpBuf rl = band_slot(row_edge_plan(fp, funit, dtype, nrows, rows_base), b & 1, fp.slots, P2).buf[P2];
-            const QpBuf cl = band_slot(col_edge_plan(fp, funit, dtype, nrows, cs, cols_base), b & 1, fp.slots, P2).buf[P2];
-            for (int side = 0; side < 2; ++side) {
-                const int at = side * (n2 - 1);
-                SpliceMap mr, mc;
-                mr.step_x = mc.step_y = S / 4;
-                mr.img_y = mc.img_x = 2;
-                mr.img_add = mc.img_add = side;
-                mr.oy = mc.ox = -at;
-                ND_TRY(nd_launch_splice(rl, 0, tp.buf[P2], 0, 2 * f4, lo, hi - lo, cols, row0, mr, at, at + 1, 0, n2, s, 0, 0, lo - t0));
-                ND_TRY(nd_launch_splice(cl, 0, tp.buf[P2], 0, 2 * f4, lo, hi - lo, cols, row0, mc, 0, n2, at, at + 1, s, 0, 0, lo - t0));
-            }
-        }
-        // the four corner pixels last: both reflections of the tile reach them
-        for (int k = 0; k < 4; ++k) {
-            const int r = (k >> 1) * (n2 - 1), c = (k & 1) * (n2 - 1);
-            SpliceMap m;
-            m.img_t = 4;
-            m.img_add = k;
-            m.oy = -r;
-            m.ox = -c;
-            ND_TRY(nd_launch_splice(cp.buf[P2], 0, tp.buf[P2], 0, 2 * f4, t0, cnt, cols, 0, m, r, r + 1, c, c + 1, s));
-        }
-        if (l2) {
-            // level 2 of the four 6 x 6 corner patches of every tile's P2 (image k * cnt + t): the P3 corner pixels
-            const Plan k2 = l2_scratch(l2_corner_plan(funit, dtype, cnt, batch, l2_corner_base));
-            for (int k = 0; k < 4; ++k) {
-                SpliceMap m;   // ("tile" t of a grid of one row: image t of the launch)
-                m.img_t = 1;
-                m.oy = (k >> 1) * (n2 - kStrip2);
-                m.ox = (k & 1) * (n2 - kStrip2);
-                ND_TRY(nd_launch_splice(tp.buf[P2], 0, k2.buf[P2], 0, 2 * f4, 0, cnt, cnt, 0, m, 0, kStrip2, 0, kStrip2, s, 0, 0, k * cnt));
-            }
-            ND_TRY(run_stack(funit, act, dtype, blob, k2, s, enc2));
-            // P3 as P2 above: the window of the band's, its four lines from the band's line images, its corner pixels last
-            SpliceMap whole3;
-            whole3.step_y = whole3.step_x = S / 8;
-            ND_TRY(nd_launch_splice(bf2.buf[P3], 0, tp.buf[P3], 0, 4 * f4, t0, cnt, cols, 0, whole3, 0, n3, 0, n3, s, fp.R,
-                                    slot_elems(bf2.buf[P3], fp.slots)));
-            for (int b = b0; b <= (t0 + cnt - 1) / per_band; ++b) {
-                const int lo = t0 > b * per_band ? t0 : b * per_band, hi = t0 + cnt < (b + 1) * per_band ? t0 + cnt : (b + 1) * per_band;
-                const int row0 = b * fp.R, nrows = fp.rows - row0 < fp.R ? fp.rows - row0 : fp.R;
-                const QpBuf rl = l2_slot(l2_row_plan(fp, funit, dtype, nrows, l2_rows_base), b & 1, fp.slots, P3).buf[P3];
-                const QpBuf cl = l2_slot(l2_col_plan(fp, funit, dtype, nrows, cs, l2_cols_base), b & 1, fp.slots, P3).buf[P3];
-                for (int side = 0; side < 2; ++side) {
-                    const int at = side * (n3 - 1);
-                    SpliceMap mr, mc;
-                    mr.step_x = mc.step_y = S / 8;
-                    mr.img_y = mc.img_x = 1;
-                    mr.img_add = side * nrows;
-                    mc.img_add = side * cols;
-                    mr.oy = mc.ox = -at;
-                    ND_TRY(nd_launch_splice(rl, 0, tp.buf[P3], 0, 4 * f4, lo, hi - lo, cols, row0, mr, at, at + 1, 0, n3, s, 0, 0, lo - t0));
-                    ND_TRY(nd_launch_splice(cl, 0, tp.buf[P3], 0, 4 * f4, lo, hi - lo, cols, row0, mc, 0, n3, at, at + 1, s, 0, 0, lo - t0));
-                }
-            }
-            for (int k = 0; k < 4; ++k) {
-                const int r = (k >> 1) * (n3 - 1), c = (k & 1) * (n3 - 1);
-                SpliceMap m;
-                m.img_t = 1;
-                m.img_add = k * cnt;
-                m.oy = -r;
-                m.ox = -c;
-                ND_TRY(nd_launch_splice(k2.buf[P3], 0, tp.buf[P3], 0, 4 * f4, t0, cnt, cols, 0, m, r, r + 1, c, c + 1, s));
-            }
-        }
-        ND_TRY(run_stack(funit, act, dtype, blob, tp, s, dec));
-        ND_TRY(nd_launch_final1x1_stitch(tp.buf[T4B], funit, fw, fw + 3 * funit, 2, canvas, width, height, cs, ucs, ol, t0, cnt, s));
-        t0 += cnt;
-    }
     return ND_OK;
 }
 

@@ -1,4 +1,4 @@
-// UtNet description shared by the inference executor (utnet.hip) and the training step (utnet_train.hip):
+// UtNet description shared by the inference executor (utnet.hip), its fused frame loop (utnet_frame.hip) and the training step (utnet_train.hip):
 // layer table, state-dict tensor order, packed-blob layout, activation-buffer plan and the forward launch sequence.
 // Everything lives in an unnamed namespace: each translation unit gets its own copy.
 #pragma once
@@ -177,57 +177,55 @@ struct Plan {
     size_t bytes;
 };
 
+// channels (a multiple of funit; 0: the packed input) and zero border of every buffer
+struct BufSpec { int ch_mul, pad; };
+const BufSpec kBufs[NBUF] = {{0, 0}, {1, 0}, {2, 2}, {1, 0}, {2, 0}, {4, 2}, {2, 0}, {4, 0}, {8, 2}, {4, 0}, {8, 0}, {16, 2},
+                             {8, 0}, {16, 2}, {16, 0}, {8, 2}, {8, 0}, {4, 2}, {4, 0}, {2, 2}, {2, 0}, {1, 2}, {1, 0}};
+
+// The extent (rows or columns, without border) of every buffer that kSteps reaches from buffer `from` of extent x: a valid 3x3
+// layer takes 2, a pool halves (floor), a transposed 3x3 layer adds 2, a 2x2 stride-2 transpose doubles.  A concat buffer keeps
+// the extent of its first writer, the encoder.  Buffers not reached (and those a small input does not reach) stay negative
+struct Extents {
+    int v[NBUF];
+    int operator[](int b) const { return v[b]; }
+};
+inline Extents extents_from(Buf from, int x) {
+    Extents e;
+    for (int &v : e.v) v = -1;
+    e.v[from] = x;
+    for (const Step &st : kSteps) {
+        const int s = e.v[st.src], kind = st.layer < 0 ? -1 : kLayers[st.layer].kind;
+        if (s < 0 || e.v[st.dst] >= 0) continue;
+        e.v[st.dst] = kind < 0 ? s / 2 : kind == ND_CONV3 ? s - 2 : kind == ND_CONVT3 ? s + 2 : kind == ND_CONVT2S2 ? 2 * s : s;
+    }
+    return e;
+}
+
+// Buffer `id` of plan p at base + *off: B images of h x w in planes sized for `slots` times cap images of hcap x wcap (the plane
+// stride does not move when fewer or smaller images are in use), the slack behind the last plane (reads past it: the halo of the
+// last tile / strip), rounded to 256 bytes
+inline void place_buf(Plan &p, Buf id, int f, int dt, int B, int h, int w, int cap, int hcap, int wcap, int slots, char *base,
+                      size_t *off) {
+    QpBuf &q = p.buf[id];
+    const int pad = kBufs[id].pad;
+    q.planes = id == X0 ? 2 : (kBufs[id].ch_mul * f + nd_cpp(dt) - 1) / nd_cpp(dt);   // X0, one K block: plane 0 = (r,g,b,0..), plane 1 = zeros
+    q.dt = dt;
+    q.B = B;
+    q.Hb = h + 2 * pad;
+    q.Wb = w + 2 * pad;
+    q.pad = pad;
+    q.pstride = (long)cap * (hcap + 2 * pad) * (wcap + 2 * pad) * slots;
+    q.base = (float *)(base + *off);
+    *off += ((size_t)q.planes * q.pstride + nd_buf_slack(wcap + 2 * pad)) * 16;
+    *off = (*off + 255) & ~(size_t)255;
+}
+
 // cap = batch the workspace was sized for; nimg = images in use (<= cap)
 Plan make_plan(int f, int ch_, int cw_, int cap, int nimg, char *base, int dt) {
     Plan p;
     size_t off = 0;
-    // `size` is the extent of the tensor for a SQUARE cs x cs input; the other dimension follows the same chain
-    auto chain = [](int cs, int which) {
-        const int l1 = cs, l2 = cs / 2 - 4, l3 = l2 / 2 - 4, l4 = l3 / 2 - 4, p4 = l4 / 2;
-        const int v[] = {cs + 4, cs + 2, l1, l1 / 2, l1 / 2 - 2, l2, l2 / 2, l2 / 2 - 2, l3, l3 / 2, l3 / 2 - 2, l4, p4,
-                         p4 - 2, p4, l4 + 2, l4 + 4, l3 + 2, l3 + 4, l2 + 2, l2 + 4, l1 + 2, l1 + 4};
-        return v[which];
-    };
-    auto add = [&](Buf id, int ch, int /*size*/, int pad) {
-        QpBuf &q = p.buf[id];
-        q.planes = (ch + nd_cpp(dt) - 1) / nd_cpp(dt);
-        if (id == X0) q.planes = 2;   // one K block: plane 0 = (r,g,b,0..), plane 1 = zeros
-        q.dt = dt;
-        q.B = nimg;
-        q.Hb = chain(ch_, (int)id) + 2 * pad;
-        q.Wb = chain(cw_, (int)id) + 2 * pad;
-        q.pad = pad;
-        q.pstride = (long)cap * q.Hb * q.Wb;
-        q.base = (float *)(base + off);
-        const size_t slack = nd_buf_slack(q.Wb);   // reads past the last plane (halo of the last tile / strip)
-        off += ((size_t)q.planes * q.pstride + slack) * 16;
-        off = (off + 255) & ~(size_t)255;
-    };
-    const int cs = ch_;
-    const int l1 = cs, l2 = cs / 2 - 4, l3 = l2 / 2 - 4, l4 = l3 / 2 - 4, p4 = l4 / 2;
-    add(X0, 8, cs + 4, 0);
-    add(A1, f, cs + 2, 0);
-    add(CAT4, 2 * f, l1, 2);
-    add(P1, f, l1 / 2, 0);
-    add(A2, 2 * f, l1 / 2 - 2, 0);
-    add(CAT3, 4 * f, l2, 2);
-    add(P2, 2 * f, l2 / 2, 0);
-    add(A3, 4 * f, l2 / 2 - 2, 0);
-    add(CAT2, 8 * f, l3, 2);
-    add(P3, 4 * f, l3 / 2, 0);
-    add(A4, 8 * f, l3 / 2 - 2, 0);
-    add(CAT1, 16 * f, l4, 2);
-    add(P4, 8 * f, p4, 0);
-    add(BT0, 16 * f, p4 - 2, 2);
-    add(BT1, 16 * f, p4, 0);
-    add(T1A, 8 * f, l4 + 2, 2);
-    add(T1B, 8 * f, l4 + 4, 0);
-    add(T2A, 4 * f, l3 + 2, 2);
-    add(T2B, 4 * f, l3 + 4, 0);
-    add(T3A, 2 * f, l2 + 2, 2);
-    add(T3B, 2 * f, l2 + 4, 0);
-    add(T4A, f, l1 + 2, 2);
-    add(T4B, f, l1 + 4, 0);
+    const Extents eh = extents_from(X0, ch_ + 4), ew = extents_from(X0, cw_ + 4);
+    for (int id = 0; id < NBUF; ++id) place_buf(p, (Buf)id, f, dt, nimg, eh[id], ew[id], cap, eh[id], ew[id], 1, base, &off);
     p.split = (float *)(base + off);
     off += kSplitScratchBytes;
     p.wino = base + off;
@@ -243,6 +241,20 @@ Plan make_plan(int f, int ch_, int cw_, int cap, int nimg, char *base, int dt) {
     p.bytes = off;
     return p;
 }
+
+// the checks and the plan that every entry point that runs the net on a workspace starts with
+inline int forward_common(int funit, int act, int dtype, const void *packed, int batch_cap, int nimg, int h, int w, void *ws,
+                          size_t ws_bytes, Plan *out_plan) {
+    ND_TRY(check_net(funit, h, w, batch_cap, dtype));
+    if (act < ND_ACT_PRELU || act > ND_ACT_HARDSWISH) ND_FAIL(ND_EINVAL, "UtNet: unknown activation %d", act);
+    if (nimg <= 0 || nimg > batch_cap) ND_FAIL(ND_EINVAL, "UtNet: %d images with a workspace batch of %d", nimg, batch_cap);
+    if (!packed || !ws) ND_FAIL(ND_EINVAL, "UtNet: null pointer");
+    if (((uintptr_t)ws & 15) || ((uintptr_t)packed & 15)) ND_FAIL(ND_EINVAL, "UtNet: workspace / weights must be 16-byte aligned");
+    *out_plan = make_plan(funit, h, w, batch_cap, nimg, (char *)ws, dtype);
+    if (ws_bytes < out_plan->bytes) ND_FAIL(ND_ENOMEM, "UtNet workspace: %zu B given, %zu B needed", ws_bytes, out_plan->bytes);
+    return ND_OK;
+}
+
 
 // which kernel family runs step `st` of the stack (pl = the plan of the call: the fused 1-D form needs the row's LDS images to fit;
 // train_w1: null for inference, else the training forward's per-layer choice, 1 = fused 1-D Winograd)
@@ -509,402 +521,6 @@ int run_stack(int f, int act, int dt, const float *blob, const Plan &pl, hipStre
         ND_TRY(nd_launch_conv(d, s));
     }
     if (o.ev) ND_HIP(hipEventRecord(o.ev[si], s));
-    return ND_OK;
-}
-
-// ---------------------------------------------------------------- shared encoder of the fused denoise loop
-// Tiles lie on a grid of stride S = ucs - ol, and every gathered tile is the window of one symmetric-padded frame at its origin.
-// The encoder is a chain of valid 3x3 convolutions and 2x2 pools, so a tile's encoder tensors are windows of the same layers run
-// on a band of tile rows -- where the tile's origin falls on a whole pixel of the level (and a pool's 2x2 phase agrees) -- except
-// on the lines that its own ReflectionPad2d(2) reaches: rows / cols {0, 1, n-2, n-1} of the level-0 outputs, {0, n-1} below.
-// fp32 useful-region mode shares levels 0 and 1 (convs1.0 ... the second pool: the conv_w2d layers, 64 % of the encoder's time at
-// G24) when S % 4 == 0:
-//   * the band runs steps [0, kSharedSteps) once on its window of the mirrored frame;
-//   * the decoder reads neither the contaminated lines of CAT4 nor those of CAT3 (region plan) -- it reads the tile's skip halves
-//     where the band wrote them (ConvDesc::in2; a step whose kernel has no second input source gets a copy of the window);
-//   * P2 (the level-2 input, computed whole per tile) is copied from the band, and its contaminated rows / cols 0 and n-1 come
-//     from kStrip-pixel edge images (16 input rows yield one P2 row through the 6 steps).  All tiles of a tile row reflect about
-//     the same two frame lines, so their top / bottom rows are windows of two kStrip x wx images per tile row that follow the
-//     tile along y (its reflection included) and the band along x: row_edge_plan, computed with the band.  Likewise two
-//     hx x kStrip images per tile column of the band: col_edge_plan.  A windowed line is the tile's own except at its two end
-//     pixels, where the tile's reflection along the other axis reaches: P2's four corner pixels come from kStrip x kStrip
-//     patches reflected along both axes, four per tile of a launch (corner_plan).  Every image starts on the tile grid (S % 4 ==
-//     0), so an F(4,3) pixel group of its first level covers the same pixels as in a strip of the tile's own input: with 8 | S a
-//     windowed line has that strip's bits on pixels 2 ... n - 3; pixels 1 and n - 2 come from groups that also hold neighbours
-//     of the reflected pixels and differ from it by fp32 rounding;
-//   * launches take `batch` tiles across band seams: what they read of a band (CAT4, CAT3, P2 and the P2 lines of both edge
-//     sets) lives in two slots, band b in slot b & 1, and a launch is cut at its second seam.
-// The deeper levels stay per tile: their exact border lines would need strips of 36 / 76 input rows.
-constexpr int kSharedSteps = 6;
-constexpr int kStrip = 16;
-constexpr double kBandBytes = 8.0 * (1 << 30);   // band tensors per launch of the shared steps (fixes the tile rows per band)
-
-// extent of encoder buffer b (X0 ... P2) for a first-layer input of extent x (X0 = x, valid convs -2, pools /2)
-inline int enc_extent(int x, int b) {
-    const int p1 = (x - 4) / 2;
-    switch (b) {
-        case X0: return x;
-        case A1: return x - 2;
-        case CAT4: return x - 4;
-        case P1: return p1;
-        case A2: return p1 - 2;
-        case CAT3: return p1 - 4;
-        default: return (p1 - 4) / 2;   // P2
-    }
-}
-// X0 ... P2 for B images of hx x wx first-layer input; planes sized for cap images of hcap x wcap (the plane stride does not move
-// when a band or a batch is smaller: plane 1 of X0 and the slack stay zero from the one fill of the workspace).  slots > 1 (bands):
-// the tensors the per-tile launches read -- CAT4, CAT3, P2 from `slotted` on (a band: all three, its edge images: P2) -- hold
-// `slots` times the capacity, so that band b + 1 can be computed (into slot (b + 1) & 1: band_slot) while launches still read band b
-Plan make_enc_plan(int f, int hx, int wx, int B, int hcap, int wcap, int cap, char *base, int dt, int slots = 1, Buf slotted = CAT4) {
-    Plan p = {};
-    size_t off = 0;
-    auto add = [&](Buf id, int ch, int pad) {
-        QpBuf &q = p.buf[id];
-        q.planes = id == X0 ? 2 : (ch + nd_cpp(dt) - 1) / nd_cpp(dt);
-        q.dt = dt;
-        q.B = B;
-        q.Hb = enc_extent(hx, id) + 2 * pad;
-        q.Wb = enc_extent(wx, id) + 2 * pad;
-        q.pad = pad;
-        q.pstride = (long)cap * (enc_extent(hcap, id) + 2 * pad) * (enc_extent(wcap, id) + 2 * pad);
-        if ((id == CAT4 || id == CAT3 || id == P2) && id >= slotted) q.pstride *= slots;
-        q.base = (float *)(base + off);
-        off += ((size_t)q.planes * q.pstride + nd_buf_slack(enc_extent(wcap, id) + 2 * pad)) * 16;
-        off = (off + 255) & ~(size_t)255;
-    };
-    add(X0, 8, 0);
-    add(A1, f, 0);
-    add(CAT4, 2 * f, 2);
-    add(P1, f, 0);
-    add(A2, 2 * f, 0);
-    add(CAT3, 4 * f, 2);
-    add(P2, 2 * f, 0);
-    p.split = nullptr;
-    p.wino = nullptr;
-    p.bytes = off;
-    return p;
-}
-
-// 16-byte elements between the slots of a two-slot band tensor, and the view of a plan whose slotted tensors are slot `slot`
-inline long slot_elems(const QpBuf &q, int slots) { return q.pstride / slots; }
-inline Plan band_slot(Plan p, int slot, int slots, Buf slotted = CAT4) {
-    for (Buf id : {CAT4, CAT3, P2})
-        if (id >= slotted) p.buf[id].base += (size_t)slot * slot_elems(p.buf[id], slots) * 4;
-    return p;
-}
-
-struct FramePlan {
-    int D = 0;         // shared encoder levels (2, or 0: every tile runs its whole encoder)
-    int aligned = 0;   // levels on which every tile origin is a whole pixel: 1 + the power of 2 in S, at most 4
-    int S = 0, cols = 0, rows = 0, pad = 0;
-    int R = 0, nbands = 0;   // tile rows per band, bands
-    int slots = 1;           // slots of the band tensors the per-tile launches read (2 when there is more than one band)
-    int hx = 0, wx = 0;      // first-layer input of a full band
-    int win4[2] = {0, 0}, win3[2] = {0, 0};   // [lo, hi) of the CAT4 / CAT3 skip pixels the decoder reads (both axes)
-    // frame workspace: band | row edges | column edges | corners | origins
-    size_t band_bytes = 0, row_edge_bytes = 0, col_edge_bytes = 0, corner_bytes = 0, origin_bytes = 0, bytes = 0;
-    // level 2 (levels == 3): behind the above, a third origin table | band | row images | column images | corner patches | Winograd scratch
-    int levels = 0;          // encoder levels shared in all: D, or 3 with level 2
-    int h2 = 0, w2 = 0;      // P2 of a full band
-    int win2[2] = {0, 0};    // [lo, hi) of the CAT2 skip pixels the decoder reads
-    size_t l2_band_bytes = 0, l2_row_bytes = 0, l2_col_bytes = 0, l2_corner_bytes = 0, l2_wino_bytes = 0;
-    // bit k: the skip half of tconvs(4 - k).0 is folded out of the per-tile sums (frame_plan_folds); behind everything else in the
-    // frame workspace, the Winograd scratch of the band launches of the folded three-pass steps (kFoldRows rows at a time)
-    int folds = 0;
-    size_t fold_wino_bytes = 0;
-};
-inline int band_hx(const FramePlan &fp, int nrows, int cs) { return (nrows - 1) * fp.S + cs + 4; }
-// the edge images of a band of nrows tile rows (planes sized for a full band; P2 in the band's slots) and the corner patches of a
-// launch of ntiles tiles (planes sized for cap): see the comment block above
-inline Plan row_edge_plan(const FramePlan &fp, int f, int dt, int nrows, char *base) {
-    return make_enc_plan(f, kStrip, fp.wx, 2 * nrows, kStrip, fp.wx, 2 * fp.R, base, dt, fp.slots, P2);
-}
-inline Plan col_edge_plan(const FramePlan &fp, int f, int dt, int nrows, int cs, char *base) {
-    return make_enc_plan(f, band_hx(fp, nrows, cs), kStrip, 2 * fp.cols, fp.hx, kStrip, 2 * fp.cols, base, dt, fp.slots, P2);
-}
-inline Plan corner_plan(int f, int dt, int ntiles, int cap, char *base) {
-    return make_enc_plan(f, kStrip, kStrip, 4 * ntiles, kStrip, kStrip, 4 * cap, base, dt);
-}
-
-// ---------------------------------------------------------------- level 2 of the shared encoder
-// With 8 | S a tile origin is a whole P3 pixel too, and level 2 (convs3.0, convs3.2, the third pool: steps [kSharedSteps, kLevel2End))
-// is shared the same way one level down:
-//   * the band runs the three steps once on its P2.  A tile's reflection reaches only lines 0 and n - 1 of every level-2 tensor;
-//   * tconvs2.0 leaves lines 0 and n - 1 of the CAT2 skip unread (region plan) and reads it where the band wrote it;
-//   * a tile's P3 is its window of the band's P3, and its border lines come from kStrip2-line images at P2 resolution (6 P2 rows
-//     yield one P3 row): the tile row's P2 edge line, which the level-0/1 row-edge images already produce, next to the five clean
-//     band rows below (above) it -- two 6 x w2 images per tile row of a band, image side * nrows + row.  Likewise two h2 x 6 images
-//     per tile column, image side * cols + column.  The four P3 corner pixels come from the 6 x 6 corner patches of the tile's own
-//     assembled P2, image k * ntiles + t of a launch (k = 2 * bottom + right);
-//   * the per-tile stack starts at convs4.0.
-// Level 3 stays per tile: its border images would be one F(6x6) tile row of a 30-pixel tile side.
-constexpr int kLevel2End = 9;
-constexpr int kStrip2 = 6;
-
-// extent of level-2 buffer b (P2 ... P3) for a P2 of extent x
-inline int l2_extent(int x, int b) {
-    switch (b) {
-        case P2: return x;
-        case A3: return x - 2;
-        case CAT2: return x - 4;
-        default: return (x - 4) / 2;   // P3
-    }
-}
-// (P2) A3 CAT2 P3 for B images with a P2 of h2 x w2; planes sized for cap images of hcap x wcap.  The tensors the per-tile launches
-// read -- CAT2 and P3 from `slotted` on (a band: both, its edge images: P3) -- hold `slots` times the capacity (make_enc_plan).
-// own_p2 = false: P2 is the caller's (a band's, from its level-0/1 plan)
-Plan make_l2_plan(int f, int h2, int w2, int B, int hcap, int wcap, int cap, char *base, int dt, int slots = 1, Buf slotted = CAT2,
-                  bool own_p2 = true) {
-    Plan p = {};
-    size_t off = 0;
-    auto add = [&](Buf id, int ch, int pad) {
-        QpBuf &q = p.buf[id];
-        q.planes = (ch + nd_cpp(dt) - 1) / nd_cpp(dt);
-        q.dt = dt;
-        q.B = B;
-        q.Hb = l2_extent(h2, id) + 2 * pad;
-        q.Wb = l2_extent(w2, id) + 2 * pad;
-        q.pad = pad;
-        q.pstride = (long)cap * (l2_extent(hcap, id) + 2 * pad) * (l2_extent(wcap, id) + 2 * pad);
-        if ((id == CAT2 || id == P3) && id >= slotted) q.pstride *= slots;
-        q.base = (float *)(base + off);
-        off += ((size_t)q.planes * q.pstride + nd_buf_slack(l2_extent(wcap, id) + 2 * pad)) * 16;
-        off = (off + 255) & ~(size_t)255;
-    };
-    if (own_p2) add(P2, 2 * f, 0);
-    add(A3, 4 * f, 0);
-    add(CAT2, 8 * f, 2);
-    add(P3, 4 * f, 0);
-    p.split = nullptr;
-    p.wino = nullptr;
-    p.bytes = off;
-    return p;
-}
-inline Plan l2_slot(Plan p, int slot, int slots, Buf slotted = CAT2) {
-    for (Buf id : {CAT2, P3})
-        if (id >= slotted) p.buf[id].base += (size_t)slot * slot_elems(p.buf[id], slots) * 4;
-    return p;
-}
-
-extern "C" int nd_tile_grid(int W, int H, int cs, int ucs, int ol, int *cols, int *rows, int *pad);
-
-inline int band_h2(const FramePlan &fp, int nrows, int cs) { return enc_extent(band_hx(fp, nrows, cs), P2); }
-inline Plan l2_band_plan(const FramePlan &fp, int f, int dt, int nrows, int cs, char *base) {
-    return make_l2_plan(f, band_h2(fp, nrows, cs), fp.w2, 1, fp.h2, fp.w2, 1, base, dt, fp.slots, CAT2, false);
-}
-inline Plan l2_row_plan(const FramePlan &fp, int f, int dt, int nrows, char *base) {
-    return make_l2_plan(f, kStrip2, fp.w2, 2 * nrows, kStrip2, fp.w2, 2 * fp.R, base, dt, fp.slots, P3);
-}
-inline Plan l2_col_plan(const FramePlan &fp, int f, int dt, int nrows, int cs, char *base) {
-    return make_l2_plan(f, band_h2(fp, nrows, cs), kStrip2, 2 * fp.cols, fp.h2, kStrip2, 2 * fp.cols, base, dt, fp.slots, P3);
-}
-inline Plan l2_corner_plan(int f, int dt, int ntiles, int cap, char *base) {
-    return make_l2_plan(f, kStrip2, kStrip2, 4 * ntiles, kStrip2, kStrip2, 4 * cap, base, dt);
-}
-
-// Level 2 on top of a level-0/1 plan (fp->D == 2): shared when 8 | S, the decoder leaves lines 0 and n - 1 of the CAT2 skip unread,
-// and every level-2 step of the band, the two line image shapes and the corner patches runs in a kernel that takes any image
-// shape and pools in its epilogue (conv_w2d, three-pass F(6x6)).  rois: the region plan of a tile
-inline void frame_plan_level2(int f, int dt, int flags, int cs, int batch, const BlobLayout &bl, const Roi *rois, FramePlan *fp) {
-    fp->levels = fp->D;
-    if ((flags & ND_FLAG_TILE_LEVEL2) || fp->S % 8) return;
-    const int n2 = enc_extent(cs + 4, P2), n = l2_extent(n2, CAT2);
-    if (n2 < kStrip2 + 2 || l2_extent(n2, P3) < 3) return;
-    bool reads_cat2 = false;
-    for (int i = kLevel2End; i < kNumSteps; ++i) {
-        const Step &st = kSteps[i];
-        if (st.layer < 0 || st.src != CAT2 || kLayers[st.layer].kind != ND_CONVT3) continue;
-        if (rois[i].rows <= 0 || rois[i].r0 != rois[i].c0 || rois[i].rows != rois[i].cols) return;
-        fp->win2[0] = rois[i].r0 - 2 < 0 ? 0 : rois[i].r0 - 2;
-        fp->win2[1] = rois[i].r0 + rois[i].rows > n ? n : rois[i].r0 + rois[i].rows;
-        if (fp->win2[0] < 1 || fp->win2[1] > n - 1 || fp->win2[1] <= fp->win2[0]) return;
-        reads_cat2 = true;
-    }
-    if (!reads_cat2) return;
-    fp->h2 = enc_extent(fp->hx, P2);
-    fp->w2 = enc_extent(fp->wx, P2);
-    Plan plans[4] = {l2_band_plan(*fp, f, dt, fp->R, cs, nullptr), l2_row_plan(*fp, f, dt, fp->R, nullptr),
-                     l2_col_plan(*fp, f, dt, fp->R, cs, nullptr), l2_corner_plan(f, dt, batch, batch, nullptr)};
-    plans[0].buf[P2] = make_enc_plan(f, fp->hx, fp->wx, 1, fp->hx, fp->wx, 1, nullptr, dt).buf[P2];
-    size_t wino = 0;
-    for (const Plan &pp : plans)
-        for (int i = kSharedSteps; i < kLevel2End; ++i) {
-            const Step &st = kSteps[i];
-            if (st.layer < 0) continue;
-            const LayerSpec &l = kLayers[st.layer];
-            const Form form = step_form(st, f, dt, flags, pp, bl);
-            if (form == FORM_WINO3P) {
-                // (the tile workspace's scratch is sized for the tiles of a launch: level 2 carries its own, for any batch)
-                QpBuf v = pp.buf[st.src];
-                v.B = v.B < kWinoChunk ? v.B : kWinoChunk;
-                const size_t need = nd_wino_scratch_bytes(kWinoTile, v, lcin(l, f), lcout(l, f));
-                wino = need > wino ? need : wino;
-            } else if (form != FORM_W1D4 || !nd_f43_w2d(pp.buf[st.src], lcout(l, f), false, flags)) {
-                return;
-            }
-        }
-    fp->l2_band_bytes = plans[0].bytes;
-    fp->l2_row_bytes = plans[1].bytes;
-    fp->l2_col_bytes = plans[2].bytes;
-    fp->l2_corner_bytes = plans[3].bytes;
-    fp->l2_wino_bytes = (wino + 255) & ~(size_t)255;
-    fp->bytes += fp->origin_bytes + fp->l2_band_bytes + fp->l2_row_bytes + fp->l2_col_bytes + fp->l2_corner_bytes + fp->l2_wino_bytes;
-    fp->levels = 3;
-}
-
-// ---------------------------------------------------------------- skip halves of the decoder, once per band
-// The first layer of a decoder level is a ConvTranspose2d(3) on cat([up, skip]), linear in its input channels:
-//     act(b + W_up * up + W_skip * skip) = act(W_up * up + P),   P = W_skip * skip + b.
-// Where the skip is a band tensor, P is a band tensor too: the same values for every tile that overlaps a pixel (2.0 / 2.1 / 2.6
-// tiles on average at levels 0 / 1 / 2 of G24).  A folded step's P is computed with the band, right behind the concat tensor it
-// derives from, into that tensor's up-sampled half -- which no band launch writes, has the skip half's plane geometry, and holds
-// the n + 2 output of a ConvTranspose2d(3) inside its n + 4 bordered plane at border 1 -- restricted to the rows and columns some
-// tile's region reads; the per-tile step then runs on the K blocks of its up-sampled half alone and takes its window of P as the
-// addend of its epilogue (ConvDesc::add; the window starts where the in-place skip read starts: the same origin table).  The bias
-// is part of P.  Both launches use the layer's one packed blob, each its K-block sub-range (ConvDesc::w_kb).
-// Which steps fold: those that read a band skip and run in a kernel that takes an addend (conv_w2d, three-pass F(6x6)) -- the
-// plan's decision, a function of geometry, dtype and flags; ND_FLAG_TILE_SKIPS folds none.  A three-pass step's band launch runs
-// kFoldRows output rows at a time on Winograd scratch of its own in the frame workspace (a band is one image of any size; the tile
-// workspace's scratch is sized for the tiles of a launch).
-constexpr int kFoldRows = 48;
-inline void frame_plan_folds(int f, int dt, int flags, const Plan &tp, const BlobLayout &bl, FramePlan *fp) {
-    fp->folds = 0;
-    fp->fold_wino_bytes = 0;
-    if (!fp->D || (flags & ND_FLAG_TILE_SKIPS)) return;
-    const Buf cats[3] = {CAT4, CAT3, CAT2};
-    for (int k = 0; k < (fp->levels == 3 ? 3 : 2); ++k)
-        for (int i = kSharedSteps; i < kNumSteps; ++i) {
-            const Step &st = kSteps[i];
-            if (st.layer < 0 || st.src != cats[k] || kLayers[st.layer].kind != ND_CONVT3) continue;
-            const Form form = step_form(st, f, dt, flags, tp, bl);
-            if (!form_takes_src2(st, form, f, flags, tp)) continue;
-            fp->folds |= 1 << k;
-            if (form != FORM_WINO3P) continue;
-            QpBuf v = {};
-            v.B = 1;
-            v.Hb = kFoldRows + 2;
-            v.Wb = (k == 2 ? l2_extent(fp->w2, CAT2) : enc_extent(fp->wx, cats[k])) + 4;
-            const size_t need = nd_wino_scratch_bytes(kWinoTile, v, lcin(kLayers[st.layer], f) / 2, lcout(kLayers[st.layer], f));
-            if (need > fp->fold_wino_bytes) fp->fold_wino_bytes = need;
-        }
-    fp->fold_wino_bytes = (fp->fold_wino_bytes + 255) & ~(size_t)255;
-    fp->bytes += fp->fold_wino_bytes;
-}
-// P of decoder step `step` for a band of nrows tile rows whose concat tensor is `cat` (skip half: planes [planes, 2 * planes)):
-// roi = the step's region on a tile, tstep = the tile stride at the level; form = the step's kernel family (conv_w2d, or the
-// three-pass form on `wino`, kFoldRows rows of the band at a time)
-inline int launch_skip_fold(int f, int flags, const float *blob, const BlobLayout &bl, int step, Form form, const QpBuf &cat, int planes,
-                            const Roi &roi, int tstep, int nrows, int cols, float *split, char *wino, size_t wino_bytes, hipStream_t s) {
-    const LayerSpec &l = kLayers[kSteps[step].layer];
-    const int cin = lcin(l, f);
-    ConvDesc d;
-    d.kind = l.kind;
-    d.act = ND_ACT_NONE;
-    d.cin = planes * 4;
-    d.cout = lcout(l, f);
-    d.wpk = blob + bl.w1off[kSteps[step].layer];
-    d.bias = d.wpk + nd_bias_offset(l.kind, cin, d.cout, ND_F32, kW1dTile);
-    d.w_kb = nd_kblocks(cin);
-    d.w_kb0 = planes / 2;
-    d.in = cat;
-    d.in_plane0 = planes;
-    d.out = cat;
-    d.out.pad = 1;
-    d.out_plane0 = 0;
-    d.part = split;
-    d.part_bytes = split ? kSplitScratchBytes : 0;
-    d.nosplit = (flags & ND_FLAG_NO_SPLITK) != 0;
-    d.roi_r0 = roi.r0;
-    d.roi_c0 = roi.c0;
-    d.roi_rows = (nrows - 1) * tstep + roi.rows;
-    d.roi_cols = (cols - 1) * tstep + roi.cols;
-    if (form != FORM_WINO3P) return nd_launch_conv_w2d(d, s);
-    d.wpk = blob + bl.woff[kSteps[step].layer];
-    d.bias = nullptr;
-    const int r_end = d.roi_r0 + d.roi_rows;
-    for (int r0 = d.roi_r0; r0 < r_end; r0 += kFoldRows) {
-        // rows [r0, r0 + rows) of the region as a view of rows + 2 bordered input rows (the scratch follows the view's extent)
-        ConvDesc c = d;
-        const int rows = r_end - r0 < kFoldRows ? r_end - r0 : kFoldRows;
-        c.in.base = c.out.base = cat.base + (size_t)r0 * cat.Wb * 4;
-        c.in.Hb = c.out.Hb = rows + 2;
-        c.roi_r0 = 0;
-        c.roi_rows = rows;
-        ND_TRY(nd_launch_conv_wino(kWinoTile, c, wino, wino_bytes, s));
-    }
-    return ND_OK;
-}
-
-// the band plan: a function of the frame geometry, the dtype and the flags (batch only sizes the corner buffers and the tables)
-int frame_plan(int f, int dt, int flags, int W, int H, int cs, int ucs, int ol, int batch, FramePlan *fp) {
-    *fp = FramePlan();
-    ND_TRY(check_funit(f, dt));
-    if (!valid_cs(cs)) ND_FAIL(ND_EINVAL, "frame plan: tile size %d", cs);
-    ND_TRY(nd_tile_grid(W, H, cs, ucs, ol, &fp->cols, &fp->rows, &fp->pad));
-    fp->S = ucs - ol;
-    fp->aligned = 1;
-    while (fp->aligned < 4 && fp->S % (1 << fp->aligned) == 0) ++fp->aligned;
-    // a tile origin must fall on a whole pixel of level 2 (the pooled input P2 is copied from the band), the arithmetic must be
-    // the fp32 F(4,3) layers this plan was built for, and the decoder must leave the contaminated skip lines unread
-    if (dt != ND_F32 || (flags & (ND_FLAG_FULL_TILES | ND_FLAG_TILE_ENCODER | ND_FLAG_DIRECT_CONV | ND_FLAG_W1D_REGS)) ||
-        fp->S % 4 || W < cs || H < cs || batch <= 0)
-        return ND_OK;
-    const Plan tp = make_plan(f, cs, cs, 1, 1, nullptr, dt);
-    const BlobLayout bl = blob_layout(f, dt);
-    Roi rois[kNumSteps];
-    const int crop = (cs - ucs) / 2;
-    if (!plan_rois(tp, crop, crop, rois)) return ND_OK;   // (the executor also checks that the kernels take them: rois_supported)
-    for (int i = 0; i < kNumSteps; ++i) {
-        const Step &st = kSteps[i];
-        if (st.layer < 0 || (st.src != CAT4 && st.src != CAT3) || kLayers[st.layer].kind != ND_CONVT3) continue;
-        const int n = enc_extent(cs + 4, st.src), edge = st.src == CAT4 ? 2 : 1;
-        if (rois[i].rows <= 0 || rois[i].r0 != rois[i].c0 || rois[i].rows != rois[i].cols) return ND_OK;
-        int *w = st.src == CAT4 ? fp->win4 : fp->win3;
-        w[0] = rois[i].r0 - 2 < 0 ? 0 : rois[i].r0 - 2;   // a transposed 3x3 layer reads input rows [lo - 2, hi) for output rows [lo, hi)
-        w[1] = rois[i].r0 + rois[i].rows > n ? n : rois[i].r0 + rois[i].rows;
-        if (w[0] < edge || w[1] > n - edge) return ND_OK;
-    }
-    if (fp->win4[1] <= fp->win4[0] || fp->win3[1] <= fp->win3[0]) return ND_OK;
-    // tile rows per band: as many as kBandBytes holds
-    fp->wx = (fp->cols - 1) * fp->S + cs + 4;
-    for (int R = fp->rows; R >= 1; --R) {
-        const int hx = band_hx(*fp, R, cs);
-        const size_t b = make_enc_plan(f, hx, fp->wx, 1, hx, fp->wx, 1, nullptr, dt).bytes;
-        if (b <= kBandBytes || R == 1) {
-            fp->R = R;
-            fp->hx = hx;
-            fp->band_bytes = b;
-            break;
-        }
-    }
-    // as few bands as that allows, of near-equal height (a short last band would repeat the band border for few tiles)
-    fp->nbands = (fp->rows + fp->R - 1) / fp->R;
-    fp->R = (fp->rows + fp->nbands - 1) / fp->nbands;
-    fp->hx = band_hx(*fp, fp->R, cs);
-    // (the rows per band are fixed by one slot of every tensor: the second slot is memory on top of kBandBytes)
-    fp->slots = fp->nbands > 1 ? 2 : 1;
-    fp->band_bytes = make_enc_plan(f, fp->hx, fp->wx, 1, fp->hx, fp->wx, 1, nullptr, dt, fp->slots).bytes;
-    if ((long)fp->hx * fp->wx >= (1L << 26)) return ND_OK;   // (32-bit offsets of the conv kernels on a band image)
-    // every shared step of the band and of the three edge shapes must run in conv_w2d (its pool epilogue included)
-    const Plan plans[4] = {make_enc_plan(f, fp->hx, fp->wx, 1, fp->hx, fp->wx, 1, nullptr, dt), row_edge_plan(*fp, f, dt, fp->R, nullptr),
-                           col_edge_plan(*fp, f, dt, fp->R, cs, nullptr), corner_plan(f, dt, batch, batch, nullptr)};
-    for (const Plan &pp : plans)
-        for (int i = 0; i < kSharedSteps; ++i) {
-            const Step &st = kSteps[i];
-            if (st.layer < 0) continue;
-            if (step_form(st, f, dt, flags, pp, bl) != FORM_W1D4 || !nd_f43_w2d(pp.buf[st.src], lcout(kLayers[st.layer], f), false, flags))
-                return ND_OK;
-        }
-    fp->row_edge_bytes = plans[1].bytes;
-    fp->col_edge_bytes = plans[2].bytes;
-    fp->corner_bytes = plans[3].bytes;
-    // where each tile of a launch lies in the band's CAT4 / CAT3 planes (the decoder reads the skip halves in place): two tables
-    fp->origin_bytes = ((size_t)batch * sizeof(int) + 255) & ~(size_t)255;
-    fp->bytes = fp->band_bytes + fp->row_edge_bytes + fp->col_edge_bytes + fp->corner_bytes + 2 * fp->origin_bytes;
-    fp->D = 2;
-    frame_plan_level2(f, dt, flags, cs, batch, bl, rois, fp);
-    frame_plan_folds(f, dt, flags, tp, bl, fp);
     return ND_OK;
 }
 

@@ -1,5 +1,5 @@
 """P2's border lines in the shared encoder: one pair of row-edge images per tile row and one pair of column-edge images per tile
-column of a band, and four corner patches per tile (utnet_net.h: row_edge_plan, col_edge_plan, corner_plan).
+column of a band, and four corner patches per tile (utnet_frame.hip: row_plan, col_plan, corner_plan).
 
 CPU: the identity it rests on, in float64 with the oracle's tiler -- the P2 line of the long edge image, windowed at a tile, is the
 tile's own border line except at its two end pixels, and the corner patch gives those.  GPU: the frame loop against the per-tile

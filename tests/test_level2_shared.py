@@ -1,6 +1,6 @@
 """Level 2 of the shared encoder (convs3.0, convs3.2, the third pool) in the fused frame loop: once per band of tile rows on the band's
 P2, with a tile's P3 border lines from 6-line images at P2 resolution and its P3 corner pixels from 6 x 6 patches of its own P2
-(utnet_net.h: frame_plan_level2; UtNet.share_level2 = False keeps level 2 per tile).
+(utnet_frame.hip: kLevels, plan_level; UtNet.share_level2 = False keeps level 2 per tile).
 
 CPU: the identity it rests on, in float64 with the oracle's tiler, and a gate proving that the bars reused from
 tests/test_shared_encoder.py see a skipped P3 border fix-up.  GPU: the loop against the per-tile path and float64 in conv_w2d

@@ -2,8 +2,8 @@
 
 The first layer of a decoder level is a ConvTranspose2d(3) on cat([up, skip]) and linear in its input channels:
 act(b + W_up * up + W_skip * skip) = act(W_up * up + P) with P = W_skip * skip + b.  Where the skip is a band tensor of the shared
-encoder, P is computed once per band and the per-tile layer takes its window of P as the addend of its epilogue (utnet_net.h:
-frame_plan_folds, launch_skip_fold; ConvDesc::add; UtNet.fold_skips = False / ND_FLAG_TILE_SKIPS keeps the skip halves per tile).
+encoder, P is computed once per band and the per-tile layer takes its window of P as the addend of its epilogue (utnet_frame.hip:
+plan_folds, launch_skip_fold; ConvDesc::add; UtNet.fold_skips = False / ND_FLAG_TILE_SKIPS keeps the skip halves per tile).
 
 CPU: the identity in float64 against the oracle network, with a gate proving that the bars reused from tests/test_shared_encoder.py
 see an addend window read one pixel off; the host query.  GPU: the conv_w2d addend path on every folded layer (UtNet(16)), the

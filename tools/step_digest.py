@@ -1,15 +1,26 @@
 #!/usr/bin/env python3
-"""SHA-256 digests of what the training step, the criteria and the scores compute, to compare two revisions bit for bit.
+"""SHA-256 digests of what the training step, the criteria, the scores and the fused frame loop compute, to compare two revisions
+bit for bit.
 
-    python tools/step_digest.py [--out digests.json]
+    python tools/step_digest.py [--out digests.json] [--host]
 
 Every case runs twice on fixed seeds: two equal lines per case mean the revision is deterministic there, and equal files from two
 revisions mean they compute the same bits.  Step cases (funit 8): the output, the loss bits and the flat gradient buffer of
 UtNetTrainer.forward_backward; then validation.criteria, and nd_ssim / nd_ms_ssim / nd_ssim_padded on one pair.  UNet cases, on
 weights with planted BatchNorm (gamma = 0 and gamma < 0 channels), each with the library's four byte counts for its shape: eval mode
 under autograd (y, dx, every parameter gradient), UNetTrainer (y, loss, grads, flat with its running statistics; dx of backward(gy,
-want_dx=True)), and three learn steps of both trainers, plain and guarded (flat, m, v, vmax, guard_state)."""
+want_dx=True)), and three learn steps of both trainers, plain and guarded (flat, m, v, vmax, guard_state).
+
+Frame cases: the canvas of pipeline.denoise_frame on the smallest frames at which each stanza of the shared-encoder loop runs (the
+geometries of tests/test_shared_encoder.py ... test_skip_fold.py), under the default flags and with each of split_k, share_level2,
+fold_skips, mosaic_wino, share_encoder off.  UtNet(16) seed 9 at gain 2.2 on frame seed 3 at batch 5 and 256; UtNet(64) seed 123 on
+the two-band frame FRAME64 (a one-row last band, three-pass level 2) at batch 256 (a launch over the band seam), at batch 11 and on
+the tile range (191, 193).  Each run follows a frame of another seed through the same net object and workspaces.
+
+Plan rows (--host prints only these; they need no GPU): per geometry, funit 16 / 64, flag set and dtype, the eight values of
+nd_utnet_frame_plan, the levels, the folds, nd_utnet_frame_workspace_bytes and nd_utnet_workspace_bytes_hw."""
 import argparse
+import ctypes
 import hashlib
 import json
 import os
@@ -18,7 +29,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
-from nind_denoise_amd import _lib, synth  # noqa: E402
+from nind_denoise_amd import _lib, pipeline, synth  # noqa: E402
 from nind_denoise_amd.common.libs import pt_losses  # noqa: E402
 from nind_denoise_amd.libs import pytorch_ssim  # noqa: E402
 from nind_denoise_amd.networks.UtNet import UtNet  # noqa: E402
@@ -37,6 +48,19 @@ UNET_EVAL_SHAPES = [(3, 33, 47), (2, 32, 32)]
 UNET_EVAL_MODES = [  # name, find_noise, split_k, parameters frozen
     ("plain", False, True, False), ("find-noise", True, True, False), ("no-split-k", False, False, False), ("frozen", False, True, True)]
 UNET_TRAIN_SHAPES = [(3, 33, 47), (8, 16, 16), (2, 64, 16)]      # (8, 16, 16): a 1x1 bottom level
+FRAMES16 = [(333, 290, 120, 56, 16),      # levels 3, folds 7, 8 x 7 tiles
+            (120, 290, 120, 56, 16),      # one column
+            (333, 120, 120, 56, 16),      # one row
+            (300, 170, 136, 56, 24),      # pad > stride
+            (333, 290, 120, 88, 16),      # level 2 per tile, folds 3
+            (333, 290, 120, 88, 20),      # S = 4 * odd
+            (120, 120, 120, 88, 20),      # one tile
+            (333, 290, 120, 88, 18)]      # D = 0
+FRAME64 = (13000, 400, 264, 200, 64)
+FRAME_SWITCHES = [None, "split_k", "share_level2", "fold_skips", "mosaic_wino", "share_encoder"]      # None: the default flags
+PLAN_GEOMS = ([((6000, 4000, 264, 200, 64), 256), (FRAME64, 256), ((6000, 4000, 504, 480, 24), 64), ((6000, 4000, 520, 496, 22), 10)]
+              + [(g, b) for g in FRAMES16 for b in (5, 256)])
+PLAN_FLAGS = [0, _lib.FLAG_TILE_LEVEL2, _lib.FLAG_TILE_SKIPS, _lib.FLAG_TILE_ENCODER, _lib.FLAG_NO_SPLITK, _lib.FLAG_TILE_WINO]
 GUARDS = [("plain", {}), ("guarded", {"max_grad_norm": 1e-6, "skip_nonfinite": True})]      # 1e-6: every step clips
 
 
@@ -113,12 +137,59 @@ def unet_cases(dev, res):
                 res[f"optimizer {kind} {gname} run {rep}"] = sha(*state)
 
 
+def plan_rows(res):
+    lib = _lib.load()
+    for geom, batch in PLAN_GEOMS:
+        for funit in (16, 64):
+            for flags in PLAN_FLAGS:
+                for dt in (_lib.ND_F32, _lib.ND_BF16):
+                    plan, one = (ctypes.c_int * 8)(), ctypes.c_int()
+                    row = {"rc": [lib.nd_utnet_frame_plan(funit, dt, flags, *geom, plan)], "plan": list(plan)}
+                    for key, fn in (("levels", lib.nd_utnet_frame_levels), ("folds", lib.nd_utnet_frame_folds)):
+                        row["rc"].append(fn(funit, dt, flags, *geom, ctypes.byref(one)))
+                        row[key] = one.value
+                    row["frame_bytes"] = int(lib.nd_utnet_frame_workspace_bytes(funit, dt, flags, *geom, batch))
+                    row["tile_bytes"] = int(lib.nd_utnet_workspace_bytes_hw(funit, geom[2], geom[2], batch, dt))
+                    res[f"plan {geom}@{batch} funit {funit} flags {flags} dtype {dt}"] = row
+
+
+def frame_cases(dev, res):
+    runs = [(16, 9, 3, [(g, b, None) for g in FRAMES16 for b in (5, 256)]),
+            (64, 123, 24, [(FRAME64, 256, None), (FRAME64, 11, None), (FRAME64, 256, (191, 193))])]
+    for funit, seed, frame_seed, cases in runs:
+        for switch in FRAME_SWITCHES:
+            net = UtNet(funit=funit)
+            net.load_state_dict(synth.make_utnet_state_dict(funit=funit, seed=seed, gain=2.2))
+            net = net.eval().to(dev)
+            if switch:
+                setattr(net, switch, False)
+            for geom, batch, tiles in cases:
+                imgs = [torch.from_numpy(synth.make_frame(geom[0], geom[1], seed=sd)).to(dev) for sd in (frame_seed + 4, frame_seed)]
+                for rep in range(2):
+                    for img in imgs:
+                        canvas = torch.zeros_like(img)
+                        pipeline.denoise_frame(net, img, *geom[2:], batch=batch, tile_range=tiles, canvas=canvas)
+                    res[f"frame UtNet({funit}) {geom} batch {batch} tiles {tiles} {switch or 'default'} off run {rep}"] = sha(canvas)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--host", action="store_true", help="only the plan rows: no GPU needed")
     args = ap.parse_args()
-    dev = torch.device("cuda", 0)
     res = {}
+    plan_rows(res)
+    if not args.host:
+        gpu_cases(torch.device("cuda", 0), res)
+        torch.cuda.synchronize()
+    for k, v in res.items():
+        print(k, json.dumps(v))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+def gpu_cases(dev, res):
     for name, h, w, batch, loss_cs, weights, act in STEP_CASES:
         net = UtNet(funit=8, activation=act)
         net.load_state_dict(synth.make_utnet_state_dict(funit=8, seed=31, gain=1.8, activation=act), strict=True)
@@ -135,12 +206,7 @@ def main():
         res[f"scores run {rep}"] = {"ssim": sha(pt_losses.SSIM_loss()(g, t)), "ms_ssim": sha(pt_losses.MS_SSIM_loss()(g, t)),
                                     "ssim_padded": sha(pytorch_ssim.ssim(g, t, 11, size_average=False)), "mse": sha(pt_losses.mse(g, t))}
     unet_cases(dev, res)
-    torch.cuda.synchronize()
-    for k, v in res.items():
-        print(k, json.dumps(v))
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
+    frame_cases(dev, res)
 
 
 if __name__ == "__main__":
