@@ -234,7 +234,7 @@ int nd_launch_gather_edges(const float *img, int W, int H, int cs, int ucs, int 
     return ND_OK;
 }
 
-// dst image dst_img0 + t, plane dst_p0 + p, interior pixel (r, c) of [r0, r1) x [c0, c1)  <-  src plane src_p0 + p, image
+// One job: dst image dst_img0 + t, plane dst_p0 + p, interior pixel (r, c) of [r0, r1) x [c0, c1)  <-  src plane src_p0 + p, image
 // m.img_t * t + m.img_y * yrel + m.img_x * xi + m.img_add, interior pixel (yrel * m.step_y + r + m.oy, xi * m.step_x + c + m.ox),
 // (yi, xi) = grid position of tile tile_begin + t, yrel = yi - row0 (SpliceMap: nd_common.h).  band_rows > 0: the source holds bands
 // of band_rows tile rows in two slots, slot_elems apart -- a tile reads band yi / band_rows in slot (band & 1), row0 = the band's
@@ -244,16 +244,29 @@ struct SpliceArgs {
     f32x4 *dst;
     long src_np, dst_np;
     int src_Hb, src_Wb, src_pad, dst_Hb, dst_Wb, dst_pad;
-    int tile_begin, cols, row0, r0, c0, rows, ccols, planes, dst_img0;
+    int tile_begin, tiles, cols, row0, r0, c0, rows, ccols, planes, dst_img0;
     SpliceMap m;
     int band_rows;
     long slot_elems;
 };
-__global__ void k_splice(SpliceArgs a) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;   // pixel of the region, row-major (a region may be one column wide)
-    if (k >= a.rows * a.ccols) return;
+// Up to kSpliceJobs jobs in one launch, by value in the kernel arguments.  A job's elements -- pixel of the region (row-major; a
+// region may be one column wide) under plane under tile -- are dealt to consecutive threads, and job j owns blocks [first[j],
+// first[j + 1]): a one-pixel or one-line job takes the blocks its elements fill, not a block per pixel, and no block is empty.
+struct SpliceJobArgs {
+    SpliceArgs job[kSpliceJobs];
+    int first[kSpliceJobs + 1];
+    int n;
+};
+__global__ __launch_bounds__(256) void k_splice_jobs(SpliceJobArgs ja) {
+    int j = 0;
+    while (j + 1 < ja.n && (int)blockIdx.x >= ja.first[j + 1]) ++j;   // (wave-uniform)
+    const SpliceArgs &a = ja.job[j];
+    const int npix = a.rows * a.ccols;
+    const int e = ((int)blockIdx.x - ja.first[j]) * 256 + (int)threadIdx.x;
+    const int y = e / npix, k = e - y * npix;
+    const int t = y / a.planes, p = y - t * a.planes;
+    if (t >= a.tiles) return;
     const int r = a.r0 + k / a.ccols, c = a.c0 + k % a.ccols;
-    const int t = blockIdx.y / a.planes, p = blockIdx.y - t * a.planes;
     const int i = a.tile_begin + t;
     const int yi = i / a.cols, xi = i - yi * a.cols;
     const int band = a.band_rows > 0 ? yi / a.band_rows : 0, yrel = yi - (a.band_rows > 0 ? band * a.band_rows : a.row0);
@@ -263,38 +276,77 @@ __global__ void k_splice(SpliceArgs a) {
     a.dst[(long)p * a.dst_np + ((long)(a.dst_img0 + t) * a.dst_Hb + r + a.dst_pad) * a.dst_Wb + c + a.dst_pad] = a.src[si];
 }
 
+// two jobs write a common element: regions of one destination tensor that meet in planes, images, rows and columns; jobs on
+// different views are held apart by the byte extents of their planes
+static bool splice_jobs_overlap(const SpliceJob &a, const SpliceJob &b) {
+    auto meet = [](long a0, long a1, long b0, long b1) { return a0 < b1 && b0 < a1; };
+    const QpBuf &p = a.dst, &q = b.dst;
+    if (p.base == q.base && p.Hb == q.Hb && p.Wb == q.Wb && p.pad == q.pad && p.np() == q.np())
+        return meet(a.dst_p0, a.dst_p0 + a.planes, b.dst_p0, b.dst_p0 + b.planes) &&
+               meet(a.dst_img0, a.dst_img0 + a.tile_count, b.dst_img0, b.dst_img0 + b.tile_count) && meet(a.r0, a.r1, b.r0, b.r1) &&
+               meet(a.c0, a.c1, b.c0, b.c1);
+    const uintptr_t pa = (uintptr_t)p.base, pb = (uintptr_t)q.base;
+    return meet(pa + (size_t)a.dst_p0 * p.np() * 16, pa + (size_t)(a.dst_p0 + a.planes) * p.np() * 16, pb + (size_t)b.dst_p0 * q.np() * 16,
+                pb + (size_t)(b.dst_p0 + b.planes) * q.np() * 16);
+}
+
+int nd_launch_splices(const SpliceJob *jobs, int n, hipStream_t s) {
+    if (!jobs || n < 1 || n > kSpliceJobs) ND_FAIL(ND_EINVAL, "splice: %d jobs in one launch (1 ... %d)", n, kSpliceJobs);
+    SpliceJobArgs ja;
+    long blocks = 0;
+    for (int j = 0; j < n; ++j) {
+        const SpliceJob &q = jobs[j];
+        const QpBuf &src = q.src, &dst = q.dst;
+        const int sH = src.Hb - 2 * src.pad, sW = src.Wb - 2 * src.pad, dH = dst.Hb - 2 * dst.pad, dW = dst.Wb - 2 * dst.pad;
+        bool ok = src.base && dst.base && src.dt == ND_F32 && dst.dt == ND_F32 && q.tile_begin >= 0 && q.cols > 0 && q.tile_count > 0 &&
+                  q.dst_img0 >= 0 && q.dst_img0 + q.tile_count <= dst.B && dst.used() <= dst.np() && src.used() <= src.np() && q.planes > 0 &&
+                  q.src_p0 >= 0 && q.src_p0 + q.planes <= src.planes && q.dst_p0 >= 0 && q.dst_p0 + q.planes <= dst.planes &&
+                  q.r0 >= 0 && q.c0 >= 0 && q.r1 > q.r0 && q.c1 > q.c0 && q.r1 <= dH && q.c1 <= dW && q.band_rows >= 0 &&
+                  (q.band_rows == 0 || q.slot_elems >= 0);
+        // the elements of a job are numbered in 32 bits
+        const long elems = ok ? (long)q.tile_count * q.planes * (q.r1 - q.r0) * (q.c1 - q.c0) : 0;
+        ok = ok && elems <= 0x7fffffffL - 256;
+        // the source image and window of every tile of the job (a launch has at most a few hundred tiles)
+        for (int t = 0; t < q.tile_count && ok; ++t) {
+            const int yi = (q.tile_begin + t) / q.cols, xi = (q.tile_begin + t) % q.cols;
+            const int yrel = yi - (q.band_rows > 0 ? yi / q.band_rows * q.band_rows : q.row0);
+            const int simg = q.m.img_t * t + q.m.img_y * yrel + q.m.img_x * xi + q.m.img_add, y = yrel * q.m.step_y + q.m.oy,
+                      x = xi * q.m.step_x + q.m.ox;
+            if (q.band_rows > 0 && (yi / q.band_rows & 1)) ok = q.slot_elems >= src.used() && q.slot_elems + src.used() <= src.np();
+            ok = ok && yrel >= 0 && simg >= 0 && simg < src.B && y + q.r0 >= 0 && y + q.r1 - 1 < sH && x + q.c0 >= 0 && x + q.c1 - 1 < sW;
+        }
+        if (!ok) ND_FAIL(ND_EINVAL, "splice: job %d, region [%d,%d) x [%d,%d) of %d tiles x %d planes outside its source / destination", j,
+                         q.r0, q.r1, q.c0, q.c1, q.tile_count, q.planes);
+        for (int i = 0; i < j; ++i)
+            if (splice_jobs_overlap(jobs[i], q)) ND_FAIL(ND_EINVAL, "splice: jobs %d and %d write overlapping regions", i, j);
+        SpliceArgs &a = ja.job[j];
+        a.src = (const f32x4 *)src.base + (long)q.src_p0 * src.np();
+        a.dst = (f32x4 *)dst.base + (long)q.dst_p0 * dst.np();
+        a.src_np = src.np(); a.dst_np = dst.np();
+        a.src_Hb = src.Hb; a.src_Wb = src.Wb; a.src_pad = src.pad;
+        a.dst_Hb = dst.Hb; a.dst_Wb = dst.Wb; a.dst_pad = dst.pad;
+        a.tile_begin = q.tile_begin; a.tiles = q.tile_count; a.cols = q.cols; a.row0 = q.row0; a.m = q.m; a.dst_img0 = q.dst_img0;
+        a.r0 = q.r0; a.c0 = q.c0; a.rows = q.r1 - q.r0; a.ccols = q.c1 - q.c0; a.planes = q.planes;
+        a.band_rows = q.band_rows; a.slot_elems = q.slot_elems;
+        ja.first[j] = (int)blocks;
+        blocks += (elems + 255) / 256;
+        // (a grid holds fewer than 2^32 threads)
+        if (blocks * 256 >= (1L << 32)) ND_FAIL(ND_EINVAL, "splice: %ld blocks of 256 threads in one launch", blocks);
+    }
+    for (int j = n; j < kSpliceJobs; ++j) ja.job[j] = ja.job[0];   // (never read)
+    for (int j = n; j <= kSpliceJobs; ++j) ja.first[j] = (int)blocks;
+    ja.n = n;
+    hipLaunchKernelGGL(k_splice_jobs, dim3((unsigned)blocks), dim3(256), 0, s, ja);
+    ND_HIP(hipGetLastError());
+    return ND_OK;
+}
+
 int nd_launch_splice(const QpBuf &src, int src_p0, const QpBuf &dst, int dst_p0, int planes, int tile_begin, int tile_count, int cols,
                      int row0, const SpliceMap &m, int r0, int r1, int c0, int c1, hipStream_t s, int band_rows, long slot_elems,
                      int dst_img0) {
-    const int sH = src.Hb - 2 * src.pad, sW = src.Wb - 2 * src.pad, dH = dst.Hb - 2 * dst.pad, dW = dst.Wb - 2 * dst.pad;
-    bool ok = src.dt == ND_F32 && dst.dt == ND_F32 && tile_begin >= 0 && cols > 0 && tile_count > 0 && dst_img0 >= 0 &&
-              dst_img0 + tile_count <= dst.B && dst.used() <= dst.np() && src.used() <= src.np() && planes > 0 &&
-              src_p0 >= 0 && src_p0 + planes <= src.planes && dst_p0 >= 0 && dst_p0 + planes <= dst.planes &&
-              r0 >= 0 && c0 >= 0 && r1 > r0 && c1 > c0 && r1 <= dH && c1 <= dW && band_rows >= 0 &&
-              (band_rows == 0 || slot_elems >= 0) && (long)tile_count * planes <= 65535;
-    // the source image and window of every tile of the launch (a launch has at most a few hundred tiles)
-    for (int t = 0; t < tile_count && ok; ++t) {
-        const int yi = (tile_begin + t) / cols, xi = (tile_begin + t) % cols;
-        const int yrel = yi - (band_rows > 0 ? yi / band_rows * band_rows : row0);
-        const int simg = m.img_t * t + m.img_y * yrel + m.img_x * xi + m.img_add, y = yrel * m.step_y + m.oy, x = xi * m.step_x + m.ox;
-        if (band_rows > 0 && (yi / band_rows & 1)) ok = slot_elems >= src.used() && slot_elems + src.used() <= src.np();
-        ok = ok && yrel >= 0 && simg >= 0 && simg < src.B && y + r0 >= 0 && y + r1 - 1 < sH && x + c0 >= 0 && x + c1 - 1 < sW;
-    }
-    if (!ok) ND_FAIL(ND_EINVAL, "splice: region [%d,%d) x [%d,%d) of %d tiles x %d planes outside its source / destination", r0, r1, c0, c1,
-                     tile_count, planes);
-    SpliceArgs a;
-    a.src = (const f32x4 *)src.base + (long)src_p0 * src.np();
-    a.dst = (f32x4 *)dst.base + (long)dst_p0 * dst.np();
-    a.src_np = src.np(); a.dst_np = dst.np();
-    a.src_Hb = src.Hb; a.src_Wb = src.Wb; a.src_pad = src.pad;
-    a.dst_Hb = dst.Hb; a.dst_Wb = dst.Wb; a.dst_pad = dst.pad;
-    a.tile_begin = tile_begin; a.cols = cols; a.row0 = row0; a.m = m; a.dst_img0 = dst_img0;
-    a.r0 = r0; a.c0 = c0; a.rows = r1 - r0; a.ccols = c1 - c0; a.planes = planes;
-    a.band_rows = band_rows; a.slot_elems = slot_elems;
-    dim3 grid(((r1 - r0) * (c1 - c0) + 255) / 256, tile_count * planes);
-    hipLaunchKernelGGL(k_splice, grid, dim3(256), 0, s, a);
-    ND_HIP(hipGetLastError());
-    return ND_OK;
+    const SpliceJob q = nd_splice_job(src, src_p0, dst, dst_p0, planes, tile_begin, tile_count, cols, row0, m, r0, r1, c0, c1, band_rows,
+                                      slot_elems, dst_img0);
+    return nd_launch_splices(&q, 1, s);
 }
 
 // The conv kernels that read a skip half in place (ConvDesc::in2) take the tile's place in the band plane from a table in HBM: the

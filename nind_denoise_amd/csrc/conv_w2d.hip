@@ -76,6 +76,9 @@ __device__ __forceinline__ unsigned long long stamp() {
     return t;
 }
 
+#ifdef ND_QP_STAMPS
+const char *const kStampNames[6] = {"issue loads + DMA", "MFMA loop", "wait vmcnt", "transform+publish (inside the loop)", "epilogue", "barrier"};
+#endif
 // decoded strip: image, first output row, first output column
 struct Strip { int img, y0, x0; bool ok; };
 
@@ -651,7 +654,8 @@ int nd_launch_conv_w2d(const ConvDesc &d, hipStream_t stream) {
 #ifdef ND_QP_STAMPS
     // diagnostic build only (make STAMPS=1; tools/w2d_ablate.sh): ND_W2D_DBG names one of the ablation masks / the stamped kernel
     static const int dbg_all = getenv("ND_W2D_DBG") ? atoi(getenv("ND_W2D_DBG")) : 0;
-    const int dbg_env = src2 || add ? 0 : dbg_all;   // (a layer with a second input or an addend source runs the production kernel)
+    // (a layer with a second input source runs the production kernel; one with an addend source has the stamped form alone)
+    const int dbg_env = src2 ? 0 : add ? (dbg_all == 128 ? 128 : 0) : dbg_all;
     switch (dbg_env) {
         case 1: fn = conv_w2d<1>; break;
         case 2: fn = conv_w2d<2>; break;
@@ -663,7 +667,7 @@ int nd_launch_conv_w2d(const ConvDesc &d, hipStream_t stream) {
         case 30: fn = conv_w2d<30>; break;
         case 32: fn = conv_w2d<32>; break;
         case 62: fn = conv_w2d<62>; break;
-        case 128: fn = conv_w2d<128>; break;
+        case 128: fn = add ? conv_w2d<128, false, true> : conv_w2d<128>; break;
         case 256: fn = conv_w2d<256>; break;
         default: break;
     }
@@ -712,9 +716,18 @@ int nd_launch_conv_w2d(const ConvDesc &d, hipStream_t stream) {
 #ifdef ND_QP_STAMPS
     if (dbg_env == 128) {
         // stamped diagnostic launch: prints the phase split per wave role
-        static int printed = 0;
-        static const char *const names[6] = {"issue loads + DMA", "MFMA loop", "wait vmcnt", "transform+publish (inside the loop)", "epilogue", "barrier"};
-        return nd_stamped_launch(fn, 512, kLds, p, ntiles, KB, ncus, stream, printed++ < 2, nullptr, "[w2d stamps] wave", names, 6, {0, 1, 4});
+        // ND_W2D_STAMP_KB=k: print only layers of k K blocks, the first four with and the first four without an addend, each under
+        // a header that names it (tconvs4.0's per-tile pass next to tconvs4.2: the same K, Cout and, within 2 %, tiles); else the
+        // first two launches
+        static const int only_kb = getenv("ND_W2D_STAMP_KB") ? atoi(getenv("ND_W2D_STAMP_KB")) : 0;
+        static int printed = 0, printed_kb[2] = {0, 0};
+        char header[160];
+        snprintf(header, sizeof(header), "[w2d stamps] kind %d cin %d cout %d KB %d tiles %ld%s", d.kind, d.cin, d.cout, KB, ntiles,
+                 add ? " ADDEND" : "");
+        if (only_kb)
+            return nd_stamped_launch(fn, 512, kLds, p, ntiles, KB, ncus, stream, KB == only_kb && ntiles >= 4 * ncus && printed_kb[add]++ < 4,
+                                     header, "[w2d stamps] wave", kStampNames, 6, {0, 1, 4});
+        return nd_stamped_launch(fn, 512, kLds, p, ntiles, KB, ncus, stream, printed++ < 2, nullptr, "[w2d stamps] wave", kStampNames, 6, {0, 1, 4});
     }
 #endif
     hipLaunchKernelGGL(fn, dim3((unsigned)grid), dim3(512), kLds, stream, p);

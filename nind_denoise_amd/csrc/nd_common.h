@@ -309,7 +309,7 @@ int nd_launch_gather_pack(const float *img, int width, int height, int cs, int u
 // shared encoder of the fused loop (fp32): band of tile rows from band_row0 as one first-layer input image (B = 1, no reflect
 // border); the images that yield P2's border lines (k_gather_edges: two row edges per tile row of a band, two column edges per
 // tile column of a band, four corners per tile of a launch); per-tile copy of a window of a band or edge tensor into a tile buffer
-// (see k_splice)
+// (see k_splice_jobs)
 int nd_launch_gather_band(const float *img, int width, int height, int cs, int ucs, int ol, int band_row0, const QpBuf &dst,
                           hipStream_t s);
 enum nd_edge_set { ND_EDGE_ROWS = 0, ND_EDGE_COLS = 1, ND_EDGE_CORNERS = 2 };
@@ -330,6 +330,23 @@ struct SpliceMap {
 int nd_launch_splice(const QpBuf &src, int src_p0, const QpBuf &dst, int dst_p0, int planes, int tile_begin, int tile_count, int cols,
                      int row0, const SpliceMap &m, int r0, int r1, int c0, int c1, hipStream_t s, int band_rows = 0,
                      long slot_elems = 0, int dst_img0 = 0);
+// the same copy as one job of a launch of several (k_splice_jobs): every job is checked as nd_launch_splice checks its one, and jobs
+// whose destination regions overlap are refused (ND_EINVAL) -- the order of the jobs of a launch means nothing
+struct SpliceJob {
+    QpBuf src, dst;
+    int src_p0, dst_p0, planes, tile_begin, tile_count, cols, row0;
+    SpliceMap m;
+    int r0, r1, c0, c1, band_rows;
+    long slot_elems;
+    int dst_img0;
+};
+constexpr int kSpliceJobs = 16;
+static inline SpliceJob nd_splice_job(const QpBuf &src, int src_p0, const QpBuf &dst, int dst_p0, int planes, int tile_begin, int tile_count,
+                                      int cols, int row0, const SpliceMap &m, int r0, int r1, int c0, int c1, int band_rows = 0,
+                                      long slot_elems = 0, int dst_img0 = 0) {
+    return SpliceJob{src, dst, src_p0, dst_p0, planes, tile_begin, tile_count, cols, row0, m, r0, r1, c0, c1, band_rows, slot_elems, dst_img0};
+}
+int nd_launch_splices(const SpliceJob *jobs, int n, hipStream_t s);
 
 // ------------------------------------------------------------------ gradient kernels shared by the two networks' backward passes
 // (wgrad.hip, train.hip, utnet_train.hip, unet_grad.hip): no atomics, fixed summation order

@@ -41,7 +41,8 @@ namespace {
 //     yield one P3 row): the tile row's P2 edge line, which the level-0/1 row-edge images already produce, next to the five clean
 //     band rows below (above) it -- two 6 x w2 images per tile row of a band, image side * nrows + row.  Likewise two h2 x 6 images
 //     per tile column, image side * cols + column.  The four P3 corner pixels come from the 6 x 6 corner patches of the tile's own
-//     assembled P2, image k * ntiles + t of a launch (k = 2 * bottom + right);
+//     assembled P2, image k * ntiles + t of a launch (k = 2 * bottom + right) -- the only reader of a tile's own P2 then, so
+//     only those corner windows of it are assembled (assemble_output);
 //   * the per-tile stack starts at convs4.0.
 // Level 3 stays per tile: its border images would be one F(6x6) tile row of a 30-pixel tile side.
 constexpr int kSharedSteps = 6, kLevel2End = 9;
@@ -394,6 +395,23 @@ inline void line_image(const Level &lv, int side, int count, int *step, int *add
     *add = lv.by_side ? side * count : side;
 }
 
+// the splices that fill one tensor, gathered into one launch (a full list goes out and a new one starts)
+struct SpliceList {
+    hipStream_t s;
+    SpliceJob job[kSpliceJobs];
+    int n = 0;
+    int flush() {
+        const int k = n;
+        n = 0;
+        return k ? nd_launch_splices(job, k, s) : ND_OK;
+    }
+    int add(const SpliceJob &j) {
+        if (n == kSpliceJobs) ND_TRY(flush());
+        job[n++] = j;
+        return ND_OK;
+    }
+};
+
 // The line images of level l > 0 for a band of nrows tile rows, from the band (band), row (re) and column (ce) images of the level
 // above: the edge line of a tile row (column), which the level above's line images produce, next to the strip - 1 clean band
 // rows (columns) inside it
@@ -401,6 +419,7 @@ int splice_line_inputs(const Frame &c, int l, int nrows, const Plan &band, const
     const Level &lv = kLevels[l], &up = kLevels[l - 1];
     const Buf in = lv.in;
     const int n = c.tile[in], planes = band.buf[in].planes, h = band.buf[in].Hb, w = band.buf[in].Wb;
+    SpliceList jobs = {c.s};
     for (int side = 0; side < 2; ++side) {
         // (splice: "tile" t = tile row t of the band on a grid of one column / tile column t on a grid of one row)
         const int at = side * (lv.strip - 1), in0 = 1 - side, in1 = lv.strip - side;
@@ -410,12 +429,12 @@ int splice_line_inputs(const Frame &c, int l, int nrows, const Plan &band, const
         line_image(up, side, nrows, &lr.img_y, &lr.img_add);
         line_image(up, side, c.fp.cols, &lc.img_x, &lc.img_add);
         lr.oy = lc.ox = -at;
-        ND_TRY(nd_launch_splice(band.buf[in], 0, rows.buf[in], 0, planes, 0, nrows, 1, 0, br, in0, in1, 0, w, c.s, 0, 0, side * nrows));
-        ND_TRY(nd_launch_splice(re.buf[in], 0, rows.buf[in], 0, planes, 0, nrows, 1, 0, lr, at, at + 1, 0, w, c.s, 0, 0, side * nrows));
-        ND_TRY(nd_launch_splice(band.buf[in], 0, cols.buf[in], 0, planes, 0, c.fp.cols, c.fp.cols, 0, bc, 0, h, in0, in1, c.s, 0, 0, side * c.fp.cols));
-        ND_TRY(nd_launch_splice(ce.buf[in], 0, cols.buf[in], 0, planes, 0, c.fp.cols, c.fp.cols, 0, lc, 0, h, at, at + 1, c.s, 0, 0, side * c.fp.cols));
+        ND_TRY(jobs.add(nd_splice_job(band.buf[in], 0, rows.buf[in], 0, planes, 0, nrows, 1, 0, br, in0, in1, 0, w, 0, 0, side * nrows)));
+        ND_TRY(jobs.add(nd_splice_job(re.buf[in], 0, rows.buf[in], 0, planes, 0, nrows, 1, 0, lr, at, at + 1, 0, w, 0, 0, side * nrows)));
+        ND_TRY(jobs.add(nd_splice_job(band.buf[in], 0, cols.buf[in], 0, planes, 0, c.fp.cols, c.fp.cols, 0, bc, 0, h, in0, in1, 0, 0, side * c.fp.cols)));
+        ND_TRY(jobs.add(nd_splice_job(ce.buf[in], 0, cols.buf[in], 0, planes, 0, c.fp.cols, c.fp.cols, 0, lc, 0, h, at, at + 1, 0, 0, side * c.fp.cols)));
     }
-    return ND_OK;
+    return jobs.flush();
 }
 
 // Band b, level by level: its rows of tiles on the mirrored frame, the folds of the level's skips, then its line images -- top /
@@ -459,13 +478,15 @@ int corner_patches(const Frame &c, int l, const Plan &tp, int t0, int cnt, Plan 
     const Level &lv = kLevels[l];
     *cp = level_scratch(c, l, corner_plan(l, c.f, c.dt, cnt, c.batch, c.ws.corners[l]));
     if (l == 0) ND_TRY(nd_launch_gather_edges(c.img, c.W, c.H, c.cs, c.ucs, c.ol, ND_EDGE_CORNERS, t0, cnt, cp->buf[lv.in], c.s));
+    SpliceList jobs = {c.s};
     for (int k = 0; l > 0 && k < 4; ++k) {
         SpliceMap m;   // ("tile" t of a grid of one row: image t of the launch)
         m.img_t = 1;
         m.oy = (k >> 1) * (c.tile[lv.in] - lv.strip);
         m.ox = (k & 1) * (c.tile[lv.in] - lv.strip);
-        ND_TRY(nd_launch_splice(tp.buf[lv.in], 0, cp->buf[lv.in], 0, tp.buf[lv.in].planes, 0, cnt, cnt, 0, m, 0, lv.strip, 0, lv.strip, c.s, 0, 0, k * cnt));
+        ND_TRY(jobs.add(nd_splice_job(tp.buf[lv.in], 0, cp->buf[lv.in], 0, tp.buf[lv.in].planes, 0, cnt, cnt, 0, m, 0, lv.strip, 0, lv.strip, 0, 0, k * cnt)));
     }
+    ND_TRY(jobs.flush());
     return run_level(c, l, *cp);
 }
 
@@ -502,16 +523,30 @@ int bind_skips(const Frame &c, const Plan &tp, int t0, int cnt, StepSrc2 *src2, 
     return ND_OK;
 }
 
-// The output of level l in the buffers of tiles [t0, t0 + cnt): each tile's window of the band tensor, then its border lines and
-// corner pixels from the line images and the corner patches cp
+// The output of level l in the buffers of tiles [t0, t0 + cnt): each tile's window of the band tensor, its border lines and
+// corner pixels from the line images and the corner patches cp -- one splice launch
 int assemble_output(const Frame &c, int l, const Plan &tp, const Plan &cp, int t0, int cnt) {
     const FramePlan &fp = c.fp;
     const Level &lv = kLevels[l];
     const QpBuf &dst = tp.buf[lv.out], &bt = c.full[l].buf[lv.out];
     const int n = c.tile[lv.out], step = fp.S >> lv.out_shift, per_band = fp.R * fp.cols;
+    // The pieces are disjoint and go out as one launch: the window of the band covers [1, n - 1)^2, a row line columns [1, n - 1),
+    // a column line rows [1, n - 1), and the corner pixels, which both reflections of the tile reach, stand alone.
+    SpliceList jobs = {c.s};
     SpliceMap whole;
     whole.step_y = whole.step_x = step;
-    ND_TRY(nd_launch_splice(bt, 0, dst, 0, dst.planes, t0, cnt, fp.cols, 0, whole, 0, n, 0, n, c.s, fp.R, slot_elems(bt, fp.slots)));
+    // Where the level below is shared too, the tile's own copy of this output has one reader, corner_patches(l + 1): its four
+    // strip x strip corner windows.  Only they are copied then (less the lines and corner pixels, which follow)
+    const int strip = l + 1 < c.nlev ? kLevels[l + 1].strip : 0;
+    if (strip > 0 && n >= 2 * strip) {
+        for (int k = 0; k < 4; ++k) {
+            const int r0 = (k >> 1) ? n - strip : 1, c0 = (k & 1) ? n - strip : 1;
+            ND_TRY(jobs.add(nd_splice_job(bt, 0, dst, 0, dst.planes, t0, cnt, fp.cols, 0, whole, r0, r0 + strip - 1, c0, c0 + strip - 1, fp.R,
+                                          slot_elems(bt, fp.slots))));
+        }
+    } else {
+        ND_TRY(jobs.add(nd_splice_job(bt, 0, dst, 0, dst.planes, t0, cnt, fp.cols, 0, whole, 1, n - 1, 1, n - 1, fp.R, slot_elems(bt, fp.slots))));
+    }
     // rows 0 / n - 1 and columns 0 / n - 1: the tile's window of its tile row's / tile column's lines (side 0 / 1), band by band
     // of the launch -- the column images of a short last band are shorter
     for (int b = t0 / per_band; b <= (t0 + cnt - 1) / per_band; ++b) {
@@ -526,11 +561,10 @@ int assemble_output(const Frame &c, int l, const Plan &tp, const Plan &cp, int t
             line_image(lv, side, nrows, &mr.img_y, &mr.img_add);
             line_image(lv, side, fp.cols, &mc.img_x, &mc.img_add);
             mr.oy = mc.ox = -at;
-            ND_TRY(nd_launch_splice(rl, 0, dst, 0, dst.planes, lo, hi - lo, fp.cols, row0, mr, at, at + 1, 0, n, c.s, 0, 0, lo - t0));
-            ND_TRY(nd_launch_splice(cl, 0, dst, 0, dst.planes, lo, hi - lo, fp.cols, row0, mc, 0, n, at, at + 1, c.s, 0, 0, lo - t0));
+            ND_TRY(jobs.add(nd_splice_job(rl, 0, dst, 0, dst.planes, lo, hi - lo, fp.cols, row0, mr, at, at + 1, 1, n - 1, 0, 0, lo - t0)));
+            ND_TRY(jobs.add(nd_splice_job(cl, 0, dst, 0, dst.planes, lo, hi - lo, fp.cols, row0, mc, 1, n - 1, at, at + 1, 0, 0, lo - t0)));
         }
     }
-    // the four corner pixels last: both reflections of the tile reach them
     for (int k = 0; k < 4; ++k) {
         const int r = (k >> 1) * (n - 1), col = (k & 1) * (n - 1);
         SpliceMap m;
@@ -538,9 +572,9 @@ int assemble_output(const Frame &c, int l, const Plan &tp, const Plan &cp, int t
         m.img_add = lv.by_side ? k * cnt : k;
         m.oy = -r;
         m.ox = -col;
-        ND_TRY(nd_launch_splice(cp.buf[lv.out], 0, dst, 0, dst.planes, t0, cnt, fp.cols, 0, m, r, r + 1, col, col + 1, c.s));
+        ND_TRY(jobs.add(nd_splice_job(cp.buf[lv.out], 0, dst, 0, dst.planes, t0, cnt, fp.cols, 0, m, r, r + 1, col, col + 1)));
     }
-    return ND_OK;
+    return jobs.flush();
 }
 
 }  // namespace

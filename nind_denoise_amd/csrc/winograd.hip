@@ -319,7 +319,8 @@ __global__ __launch_bounds__(NTL * (T + 2)) void k_wino_in2(const f32x4 *__restr
 //           pass 2 thread (row i < T, tile) row transform, bias, activation -> LDS row image [T][32 tiles x T pixels]
 //           pass 3 all threads              pixel-contiguous stores of the T rows (+ the 2x2 max pool of the tile rows, T even)
 // ADD: the layer has an addend source (ConvDesc::add) in place of its bias -- a variant of its own; pass 2 leaves the raw sums and
-// pass 3 adds the addend, read at the stored pixel's place in its window (as contiguous as the stores), then activates.  Output
+// pass 3 adds the addend, read at the stored pixel's place in its window (as contiguous as the stores; requested before pass 1 and
+// held in registers across the two barriers), then activates.  Output
 // pixel (y, x) of image b: element origin_add[b] + y * W_add + x of plane q of `add`
 // MOSAIC (see k_wino_in2): the tiles cover mby x mbx images of Hv x Wv = mp x mp outputs side by side; pass 3 maps a stored pixel to
 // its image and its place there, and skips the slots past the last image.  Neither pooled nor with an addend
@@ -352,6 +353,32 @@ __global__ __launch_bounds__(NTL * (T + 2)) void k_wino_out2(const f32x4 *__rest
         }
         return y;
     };
+    // the pixel of the T rows x NTL * T pixels row image that idx stands for: its image and its place there, or false (past the
+    // last tile or outside the output)
+    auto pixel_of = [&](int idx, int &i, int &pp, int &b, int &yy, int &xx) {
+        i = idx / (NTL * T);
+        pp = idx - i * (NTL * T);
+        const long tt = t0 + pp / T;
+        if (idx >= T * NTL * T || tt >= tiles) return false;
+        int tx, ty;
+        tile_pos(tt, TX, TY, tx, ty, b);
+        xx = T * tx + pp % T;
+        yy = T * ty + i;
+        return xx < Wv && yy < Hv;
+    };
+    // ADD: a thread's pass-3 pixels are a function of threadIdx.x, t0 and the geometry alone, so their addend values are requested
+    // here, ahead of pass 1's loads, and land under the two transforms (a pixel that stores nothing reads element 0 of the plane)
+    constexpr int NADD = ADD ? (T * NTL * T + NTH - 1) / NTH : 1;
+    f32x4 av[NADD];
+    if constexpr (ADD) {
+        const f32x4 *ap = add + (long)q * add_np;
+#pragma unroll
+        for (int it = 0; it < NADD; ++it) {
+            int i, pp, b, yy, xx;
+            const bool ok = pixel_of(threadIdx.x + it * NTH, i, pp, b, yy, xx);
+            av[it] = ap[ok ? (long)origin_add[b] + (long)yy * W_add + xx : 0L];
+        }
+    }
     {
         const int j = threadIdx.x / NTL, tl = threadIdx.x % NTL;
         const long t = t0 + tl;
@@ -381,21 +408,29 @@ __global__ __launch_bounds__(NTL * (T + 2)) void k_wino_out2(const f32x4 *__rest
     }
     __syncthreads();
     f32x4 *dst = out + (long)(out_plane0 + q) * onp;
-    for (int idx = threadIdx.x; idx < T * NTL * T; idx += NTH) {
-        const int i = idx / (NTL * T), pp = idx - i * (NTL * T);
-        const long tt = t0 + pp / T;
-        if (tt >= tiles) continue;
-        int tx, ty, b;
-        tile_pos(tt, TX, TY, tx, ty, b);
-        const int xx = T * tx + pp % T, yy = T * ty + i;
-        if constexpr (MOSAIC) {
-            const unsigned cx = (unsigned)xx / (unsigned)mp, cy = (unsigned)yy / (unsigned)mp;
-            const int lx = xx - (int)cx * mp, ly = yy - (int)cy * mp, bi = (int)cy * mbx + (int)cx;
-            if ((int)cx < mbx && (int)cy < mby && bi < B) dst[(long)bi * out_img_stride + (long)(ly + opad) * Wo + lx + opad] = so[i][pp];
-        } else if (xx < Wv && yy < Hv) {
-            f32x4 y = so[i][pp];
-            if constexpr (ADD) y = activate(y + add[(long)q * add_np + (long)origin_add[b] + (long)yy * W_add + xx]);
-            dst[(long)b * out_img_stride + (long)(yy + opad) * Wo + xx + opad] = y;
+    if constexpr (ADD) {
+#pragma unroll
+        for (int it = 0; it < NADD; ++it) {
+            int i, pp, b, yy, xx;
+            if (pixel_of(threadIdx.x + it * NTH, i, pp, b, yy, xx))
+                dst[(long)b * out_img_stride + (long)(yy + opad) * Wo + xx + opad] = activate(so[i][pp] + av[it]);
+        }
+    }
+    if constexpr (!ADD) {
+        for (int idx = threadIdx.x; idx < T * NTL * T; idx += NTH) {
+            const int i = idx / (NTL * T), pp = idx - i * (NTL * T);
+            const long tt = t0 + pp / T;
+            if (tt >= tiles) continue;
+            int tx, ty, b;
+            tile_pos(tt, TX, TY, tx, ty, b);
+            const int xx = T * tx + pp % T, yy = T * ty + i;
+            if constexpr (MOSAIC) {
+                const unsigned cx = (unsigned)xx / (unsigned)mp, cy = (unsigned)yy / (unsigned)mp;
+                const int lx = xx - (int)cx * mp, ly = yy - (int)cy * mp, bi = (int)cy * mbx + (int)cx;
+                if ((int)cx < mbx && (int)cy < mby && bi < B) dst[(long)bi * out_img_stride + (long)(ly + opad) * Wo + lx + opad] = so[i][pp];
+            } else if (xx < Wv && yy < Hv) {
+                dst[(long)b * out_img_stride + (long)(yy + opad) * Wo + xx + opad] = so[i][pp];
+            }
         }
     }
     if (!ADD && !MOSAIC && pool) {   // fused MaxPool2d(2): tiles start on even pixels and T is even, so every 2x2 block lies inside one tile
