@@ -219,6 +219,27 @@ int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, const void 
                            int cs, int ucs, int ol, int tile_begin, int tile_count, int batch,
                            void *workspace, size_t workspace_bytes, void *frame_ws, size_t frame_ws_bytes, void *stream,
                            nd_progress_fn progress, void *progress_ctx);
+/* The same loop with a verdict per tile, for callers that recompute overflowing 16-bit tiles in a type with more range
+ * (pipeline.denoise_frame with UtNet(fallback_dtype=...)).  Same arguments plus tile_ok: device memory, one byte per tile of the
+ * grid (cols * rows of nd_tile_grid), indexed by the tile's index in the frame; the caller presets the bytes of the range to 1.
+ * Every dtype is accepted, and every launch of the loop -- those of the shared-encoder path and those of nd_utnet_denoise_tiles alike
+ * -- ends as follows, on the same stream:
+ *   verdict: tile t of the launch is bad when any value the stitch would add for it is not finite -- the 1x1 head evaluated (not a
+ *     test of the stored activations' bits) on 3 channels x the tile's useful rectangle as truncated at the frame's edges, before
+ *     the seam factor.  The kernel stores 0 into tile_ok[t] for a bad tile and writes nothing for a good one; it reads what the
+ *     stitch reads of the launch's last activation buffer and nothing else;
+ *   guarded stitch: the stitch of nd_utnet_denoise_frame, except that a covering tile whose tile_ok is 0 is skipped and a pixel
+ *     that no good tile of the launch covers is not written.
+ * Contract: when every tile of the range is good the canvas is bit-identical to nd_utnet_denoise_frame with the same arguments;
+ * otherwise the good tiles contribute exactly what they would have, in the same (ascending) order, and the bad ones nothing.  A
+ * tile_ok of 0 is final for the call: a tile whose byte is 0 on entry is computed but not stitched.  Entries outside
+ * [tile_begin, tile_begin + tile_count) are neither read nor written.  No host read, no allocation, no atomics; stream-ordered
+ * and deterministic.  ND_EINVAL: a null tile_ok, else as nd_utnet_denoise_frame. */
+int nd_utnet_denoise_frame_checked(int funit, int act, int dtype, int flags, const void *packed_dev,
+                                   const float *img_chw, float *canvas_chw, int width, int height,
+                                   int cs, int ucs, int ol, int tile_begin, int tile_count, int batch,
+                                   void *workspace, size_t workspace_bytes, void *frame_ws, size_t frame_ws_bytes, void *stream,
+                                   nd_progress_fn progress, void *progress_ctx, unsigned char *tile_ok);
 /* Host-only query (no GPU call): the band plan of nd_utnet_denoise_frame.  out[8] = {D (shared encoder levels: 2 or 0),
  * aligned levels (tile origins on whole pixels of level 0 .. aligned-1: 1 + the power of 2 in the stride, at most 4), tile rows
  * per band, bands, stride, grid columns, grid rows, band input rows of a full band}.  A function of the frame geometry, the dtype

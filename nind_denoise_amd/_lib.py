@@ -101,6 +101,8 @@ _SIGNATURES = {
     "nd_utnet_frame_folds": (c_int, [c_int] * 8 + [POINTER(c_int)]),
     "nd_utnet_denoise_frame": (c_int, [c_int] * 4 + [c_void_p] * 3 + [c_int] * 8 + [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p,
                                                                                     PROGRESS_FN, c_void_p]),
+    "nd_utnet_denoise_frame_checked": (c_int, [c_int] * 4 + [c_void_p] * 3 + [c_int] * 8 + [c_void_p, c_size_t, c_void_p, c_size_t,
+                                                                                            c_void_p, PROGRESS_FN, c_void_p, c_void_p]),
     "nd_layer_packed_bytes": (c_size_t, [c_int] * 4),
     "nd_layer_pack": (c_int, [c_int] * 4 + [c_void_p, c_void_p, c_void_p, c_size_t]),
     "nd_layer_workspace_bytes": (c_size_t, [c_int] * 7),

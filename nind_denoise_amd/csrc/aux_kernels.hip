@@ -820,12 +820,15 @@ int nd_launch_final1x1(const QpBuf &src, int cin, const float *w, const float *b
 }
 
 // fused: final 1x1 (+ Sigmoid) + crop + useful crop + seamless edges + canvas += (no NCHW tile batch in HBM).  noise_img: the
-// contribution of a tile is frame pixel - result (UNet's find_noise; a useful pixel of a tile is the frame's pixel (Y, X) itself)
-template <int DT>
-__global__ void k_final1x1_stitch(const typename Elem<DT>::vec *__restrict__ src, long np, int Hb, int Wb, int planes, int cin,
-                                  const float *__restrict__ w, const float *__restrict__ bias, int crop,
-                                  float *__restrict__ canvas, TileGeo g, int tile_begin, int tile_count, int y_first, int sigmoid,
-                                  const float *__restrict__ noise_img) {
+// contribution of a tile is frame pixel - result (UNet's find_noise; a useful pixel of a tile is the frame's pixel (Y, X) itself).
+// GUARD (the checked frame loop): a covering tile whose tile_ok[global tile index] is 0 is skipped, and a pixel that no good
+// tile of the launch covers is not written.  The unguarded form never reads tile_ok
+template <int DT, bool GUARD>
+__device__ __forceinline__ void final1x1_stitch_pixel(const typename Elem<DT>::vec *__restrict__ src, long np, int Hb, int Wb, int planes,
+                                                      int cin, const float *__restrict__ w, const float *__restrict__ bias, int crop,
+                                                      float *__restrict__ canvas, const TileGeo &g, int tile_begin, int tile_count,
+                                                      int y_first, int sigmoid, const float *__restrict__ noise_img,
+                                                      const unsigned char *__restrict__ tile_ok) {
     const int X = blockIdx.x * blockDim.x + threadIdx.x;
     const int Y = y_first + blockIdx.y;
     if (X >= g.W || Y >= g.H) return;
@@ -839,6 +842,7 @@ __global__ void k_final1x1_stitch(const typename Elem<DT>::vec *__restrict__ src
     }
     bool any = false;
     for_each_cover(g, X, Y, tile_begin, tile_count, [&](int t, int iy, int ix, float f) {
+        if (GUARD && !tile_ok[tile_begin + t]) return;
         float o0 = bias[0], o1 = bias[1], o2 = bias[2];
         dot3<DT>(src + ((size_t)t * Hb + iy + crop) * Wb + ix + crop, np, planes, w, cin, o0, o1, o2);
         if (sigmoid) {   // UNet head (ThirdPartyNets.py:169), as k_final1x1
@@ -863,21 +867,110 @@ __global__ void k_final1x1_stitch(const typename Elem<DT>::vec *__restrict__ src
     }
 }
 
+template <int DT>
+__global__ void k_final1x1_stitch(const typename Elem<DT>::vec *__restrict__ src, long np, int Hb, int Wb, int planes, int cin,
+                                  const float *__restrict__ w, const float *__restrict__ bias, int crop,
+                                  float *__restrict__ canvas, TileGeo g, int tile_begin, int tile_count, int y_first, int sigmoid,
+                                  const float *__restrict__ noise_img) {
+    final1x1_stitch_pixel<DT, false>(src, np, Hb, Wb, planes, cin, w, bias, crop, canvas, g, tile_begin, tile_count, y_first, sigmoid,
+                                     noise_img, nullptr);
+}
+
+template <int DT>
+__global__ void k_final1x1_stitch_ok(const typename Elem<DT>::vec *__restrict__ src, long np, int Hb, int Wb, int planes, int cin,
+                                     const float *__restrict__ w, const float *__restrict__ bias, int crop,
+                                     float *__restrict__ canvas, TileGeo g, int tile_begin, int tile_count, int y_first,
+                                     const unsigned char *__restrict__ tile_ok) {
+    final1x1_stitch_pixel<DT, true>(src, np, Hb, Wb, planes, cin, w, bias, crop, canvas, g, tile_begin, tile_count, y_first, 0, nullptr,
+                                    tile_ok);
+}
+
+// Verdict of the checked frame loop: tile_ok[tile_begin + t] = 0 when any value k_final1x1_stitch would add for tile t of the launch
+// is not finite.  It EVALUATES the 1x1 (the same dot3 over the same activations, bias included) on the 3 channels x the tile's
+// useful rectangle as for_each_cover truncates it at the frame's edges, before the seam factor -- it does not test the stored
+// activations' exponent bits, so a head whose own fp32 weights are not finite is seen too.  One thread per pixel of the rectangle;
+// it reads what the stitch reads of the tile and nothing else.  Flags are preset to 1 by the caller and only ever cleared: every
+// writer stores the same byte, so neither an atomic nor an order among them is needed
+template <int DT>
+__global__ __launch_bounds__(256) void k_tile_verdict(const typename Elem<DT>::vec *__restrict__ src, long np, int Hb, int Wb,
+                                                      int planes, int cin, const float *__restrict__ w,
+                                                      const float *__restrict__ bias, int crop, TileGeo g, int tile_begin,
+                                                      int tile_count, unsigned char *__restrict__ tile_ok) {
+    const int t = blockIdx.y;
+    if (t >= tile_count) return;
+    const int i = tile_begin + t;
+    const int yi = i / g.cols, xi = i - yi * g.cols;
+    const int ax = xi * g.stride, ay = yi * g.stride;
+    const int x1pad = max(0, ax - g.pad + g.cs - g.W), y1pad = max(0, ay - g.pad + g.cs - g.H);
+    const int uw = min(g.cs - max(g.pad, x1pad) - g.pad, g.W - ax), uh = min(g.cs - max(g.pad, y1pad) - g.pad, g.H - ay);
+    if (uw <= 0 || uh <= 0) return;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= uw * uh) return;
+    const int dy = p / uw, dx = p - dy * uw;
+    float o0 = bias[0], o1 = bias[1], o2 = bias[2];
+    dot3<DT>(src + ((size_t)t * Hb + g.pad + dy + crop) * Wb + g.pad + dx + crop, np, planes, w, cin, o0, o1, o2);
+    // exponent all ones: inf or NaN (a bit test, so no floating-point mode can fold it away)
+    const unsigned e = 0x7f800000u;
+    if ((__float_as_uint(o0) & e) == e || (__float_as_uint(o1) & e) == e || (__float_as_uint(o2) & e) == e) tile_ok[i] = 0;
+}
+
+// geometry and source checks of the stitch launchers; the canvas rows [*yf, *yf + *yr) the launch's tiles reach
+static int stitch_launch_geo(const QpBuf &src, int crop, int W, int H, int cs, int ucs, int ol, int tile_begin, int tile_count, TileGeo *g,
+                             int *yf, int *yr) {
+    ND_TRY(make_geo(W, H, cs, ucs, ol, g));
+    if (src.pad != 0 || src.Hb != cs + 2 * crop || src.Wb != cs + 2 * crop || tile_count > src.B)
+        ND_FAIL(ND_EINVAL, "final1x1_stitch: bad source geometry");
+    stitch_band(*g, tile_begin, tile_count, yf, yr);
+    return ND_OK;
+}
+
 int nd_launch_final1x1_stitch(const QpBuf &src, int cin, const float *w, const float *bias, int crop, float *canvas,
                               int W, int H, int cs, int ucs, int ol, int tile_begin, int tile_count, hipStream_t s, int sigmoid,
                               const float *noise_img) {
     TileGeo g;
-    ND_TRY(make_geo(W, H, cs, ucs, ol, &g));
-    if (src.pad != 0 || src.Hb != cs + 2 * crop || src.Wb != cs + 2 * crop || tile_count > src.B)
-        ND_FAIL(ND_EINVAL, "final1x1_stitch: bad source geometry");
     int yf, yr;
-    stitch_band(g, tile_begin, tile_count, &yf, &yr);
+    ND_TRY(stitch_launch_geo(src, crop, W, H, cs, ucs, ol, tile_begin, tile_count, &g, &yf, &yr));
     if (yr <= 0) return ND_OK;
     dim3 grid((W + 255) / 256, yr);
     const int n = nd_cpp(src.dt);
     ND_DISPATCH_DT(src.dt, hipLaunchKernelGGL(k_final1x1_stitch<DT>, grid, dim3(256), 0, s, (const typename Elem<DT>::vec *)src.base,
                                               src.np(), src.Hb, src.Wb, (cin + n - 1) / n, cin, w, bias, crop, canvas, g,
                                               tile_begin, tile_count, yf, sigmoid, noise_img));
+    ND_HIP(hipGetLastError());
+    return ND_OK;
+}
+
+int nd_launch_tile_verdict(const QpBuf &src, int cin, const float *w, const float *bias, int crop, int W, int H, int cs, int ucs, int ol,
+                           int tile_begin, int tile_count, unsigned char *tile_ok, hipStream_t s) {
+    TileGeo g;
+    int yf, yr;
+    ND_TRY(stitch_launch_geo(src, crop, W, H, cs, ucs, ol, tile_begin, tile_count, &g, &yf, &yr));
+    if (!tile_ok || tile_begin < 0 || tile_count <= 0 || tile_count > 65535 || tile_begin + tile_count > g.cols * g.rows)
+        ND_FAIL(ND_EINVAL, "tile_verdict: tiles [%d,+%d) outside the grid of %d (at most 65535 per launch), or no flags", tile_begin,
+                tile_count, g.cols * g.rows);
+    const int uwmax = g.cs - 2 * g.pad;
+    if (uwmax <= 0) return ND_OK;
+    dim3 grid((uwmax * uwmax + 255) / 256, tile_count);
+    const int n = nd_cpp(src.dt);
+    ND_DISPATCH_DT(src.dt, hipLaunchKernelGGL(k_tile_verdict<DT>, grid, dim3(256), 0, s, (const typename Elem<DT>::vec *)src.base,
+                                              src.np(), src.Hb, src.Wb, (cin + n - 1) / n, cin, w, bias, crop, g, tile_begin, tile_count,
+                                              tile_ok));
+    ND_HIP(hipGetLastError());
+    return ND_OK;
+}
+
+int nd_launch_final1x1_stitch_ok(const QpBuf &src, int cin, const float *w, const float *bias, int crop, float *canvas, int W, int H,
+                                 int cs, int ucs, int ol, int tile_begin, int tile_count, const unsigned char *tile_ok, hipStream_t s) {
+    TileGeo g;
+    int yf, yr;
+    ND_TRY(stitch_launch_geo(src, crop, W, H, cs, ucs, ol, tile_begin, tile_count, &g, &yf, &yr));
+    if (!tile_ok) ND_FAIL(ND_EINVAL, "final1x1_stitch_ok: no flags");
+    if (yr <= 0) return ND_OK;
+    dim3 grid((W + 255) / 256, yr);
+    const int n = nd_cpp(src.dt);
+    ND_DISPATCH_DT(src.dt, hipLaunchKernelGGL(k_final1x1_stitch_ok<DT>, grid, dim3(256), 0, s, (const typename Elem<DT>::vec *)src.base,
+                                              src.np(), src.Hb, src.Wb, (cin + n - 1) / n, cin, w, bias, crop, canvas, g,
+                                              tile_begin, tile_count, yf, tile_ok));
     ND_HIP(hipGetLastError());
     return ND_OK;
 }

@@ -302,6 +302,26 @@ int nd_launch_final1x1(const QpBuf &src, int cin, const float *w, const float *b
 int nd_launch_final1x1_stitch(const QpBuf &src, int cin, const float *w, const float *bias, int crop, float *canvas,
                               int width, int height, int cs, int ucs, int ol, int tile_begin, int tile_count,
                               hipStream_t s, int sigmoid = 0, const float *noise_img = nullptr);
+// The checked frame loop (nd_utnet_denoise_frame_checked).  tile_ok: HBM, one byte per tile of the grid, indexed by the global tile
+// index.  nd_launch_tile_verdict clears the flag of every tile of the launch for which the stitch would add a value that is not
+// finite (k_tile_verdict evaluates the 1x1 on the tile's useful rectangle); nd_launch_final1x1_stitch_ok is the stitch above
+// (UtNet head: no sigmoid, no noise image) that skips the tiles whose flag is 0 and leaves a pixel no good tile covers unwritten
+int nd_launch_tile_verdict(const QpBuf &src, int cin, const float *w, const float *bias, int crop, int width, int height, int cs, int ucs,
+                           int ol, int tile_begin, int tile_count, unsigned char *tile_ok, hipStream_t s);
+int nd_launch_final1x1_stitch_ok(const QpBuf &src, int cin, const float *w, const float *bias, int crop, float *canvas, int width,
+                                 int height, int cs, int ucs, int ol, int tile_begin, int tile_count, const unsigned char *tile_ok,
+                                 hipStream_t s);
+// the verdict + guarded stitch where tile_ok is given, the plain stitch where it is null: the one tail of the UtNet frame launches
+static inline int nd_launch_utnet_stitch(const QpBuf &src, int cin, const float *w, const float *bias, float *canvas, int width, int height,
+                                         int cs, int ucs, int ol, int tile_begin, int tile_count, unsigned char *tile_ok, hipStream_t s) {
+    if (!tile_ok) return nd_launch_final1x1_stitch(src, cin, w, bias, 2, canvas, width, height, cs, ucs, ol, tile_begin, tile_count, s);
+    ND_TRY(nd_launch_tile_verdict(src, cin, w, bias, 2, width, height, cs, ucs, ol, tile_begin, tile_count, tile_ok, s));
+    return nd_launch_final1x1_stitch_ok(src, cin, w, bias, 2, canvas, width, height, cs, ucs, ol, tile_begin, tile_count, tile_ok, s);
+}
+// nd_utnet_denoise_tiles with the flags of the checked loop (utnet.hip; tile_ok null: the plain launch)
+int nd_utnet_denoise_tiles_ok(int funit, int act, int dtype, int flags, const void *packed, const float *img, float *canvas, int width,
+                              int height, int cs, int ucs, int ol, int tile_begin, int tile_count, int batch, void *ws, size_t ws_bytes,
+                              void *stream, unsigned char *tile_ok);
 // gather (+symmetric mirror) of tiles into plane 0 of a first-layer input of (cs + 2 * border)^2.  reflect: the border is
 // ReflectionPad2d(border) of the tile (UtNet); else only the interior is written and the border stays as it is (UNet: zero)
 int nd_launch_gather_pack(const float *img, int width, int height, int cs, int ucs, int ol, int tile_begin,

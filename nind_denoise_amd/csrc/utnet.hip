@@ -135,6 +135,13 @@ extern "C" int nd_utnet_forward_hw(int funit, int act, int dtype, int flags, con
 extern "C" int nd_utnet_denoise_tiles(int funit, int act, int dtype, int flags, const void *packed, const float *img,
                                       float *canvas, int width, int height, int cs, int ucs, int ol, int tile_begin,
                                       int tile_count, int batch, void *ws, size_t ws_bytes, void *stream) {
+    return nd_utnet_denoise_tiles_ok(funit, act, dtype, flags, packed, img, canvas, width, height, cs, ucs, ol, tile_begin, tile_count, batch,
+                                     ws, ws_bytes, stream, nullptr);
+}
+
+int nd_utnet_denoise_tiles_ok(int funit, int act, int dtype, int flags, const void *packed, const float *img, float *canvas, int width,
+                              int height, int cs, int ucs, int ol, int tile_begin, int tile_count, int batch, void *ws, size_t ws_bytes,
+                              void *stream, unsigned char *tile_ok) {
     ND_TRY(nd_check_flags(flags));
     Plan pl;
     ND_TRY(forward_common(funit, act, dtype, packed, batch, tile_count, cs, cs, ws, ws_bytes, &pl));
@@ -152,9 +159,8 @@ extern "C" int nd_utnet_denoise_tiles(int funit, int act, int dtype, int flags, 
     if (!(flags & ND_FLAG_FULL_TILES) && plan_rois(pl, crop, crop, rois) && rois_supported(funit, dtype, flags, pl, bl, rois)) o.rois = rois;
     ND_TRY(run_stack(funit, act, dtype, blob, pl, s, o));
     const float *fw = blob + bl.off[kNumLayers - 1];
-    ND_TRY(nd_launch_final1x1_stitch(pl.buf[T4B], funit, fw, fw + 3 * funit, 2, canvas, width, height, cs, ucs, ol,
-                                     tile_begin, tile_count, s));
-    return ND_OK;
+    return nd_launch_utnet_stitch(pl.buf[T4B], funit, fw, fw + 3 * funit, canvas, width, height, cs, ucs, ol, tile_begin, tile_count,
+                                  tile_ok, s);
 }
 
 namespace {

@@ -615,10 +615,11 @@ extern "C" int nd_utnet_frame_folds(int funit, int dtype, int flags, int width, 
     return ND_OK;
 }
 
-extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, const void *packed, const float *img, float *canvas,
-                                      int width, int height, int cs, int ucs, int ol, int tile_begin, int tile_count, int batch,
-                                      void *ws, size_t ws_bytes, void *fws, size_t fws_bytes, void *stream, nd_progress_fn progress,
-                                      void *progress_ctx) {
+// the frame loop; tile_ok null: nd_utnet_denoise_frame, else nd_utnet_denoise_frame_checked -- every launch then ends in the verdict
+// and the guarded stitch instead of the plain stitch, and nothing else differs
+static int denoise_frame(int funit, int act, int dtype, int flags, const void *packed, const float *img, float *canvas, int width,
+                         int height, int cs, int ucs, int ol, int tile_begin, int tile_count, int batch, void *ws, size_t ws_bytes, void *fws,
+                         size_t fws_bytes, void *stream, nd_progress_fn progress, void *progress_ctx, unsigned char *tile_ok) {
     ND_TRY(nd_check_flags(flags, true));
     Frame c = {funit, act, dtype, flags, (const float *)packed, img, canvas, width, height, cs, ucs, ol, batch, (hipStream_t)stream};
     FramePlan &fp = c.fp;
@@ -635,8 +636,8 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
         for (int t0 = tile_begin; t0 < end; t0 += batch, ++n) {
             const int cnt = end - t0 < batch ? end - t0 : batch;
             if (progress) progress(progress_ctx, n, t0, cnt);
-            ND_TRY(nd_utnet_denoise_tiles(funit, act, dtype, flags & ~(ND_FLAG_TILE_LEVEL2 | ND_FLAG_TILE_SKIPS), packed, img, canvas, width, height, cs, ucs, ol, t0, cnt, batch, ws,
-                                          ws_bytes, stream));
+            ND_TRY(nd_utnet_denoise_tiles_ok(funit, act, dtype, flags & ~(ND_FLAG_TILE_LEVEL2 | ND_FLAG_TILE_SKIPS), packed, img, canvas, width, height, cs, ucs, ol, t0, cnt, batch, ws,
+                                             ws_bytes, stream, tile_ok));
         }
         return ND_OK;
     }
@@ -685,8 +686,25 @@ extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, 
             ND_TRY(assemble_output(c, l, tp, cp, t0, cnt));
         }
         ND_TRY(run_stack(funit, act, dtype, c.blob, tp, c.s, dec));
-        ND_TRY(nd_launch_final1x1_stitch(tp.buf[T4B], funit, fw, fw + 3 * funit, 2, canvas, width, height, cs, ucs, ol, t0, cnt, c.s));
+        ND_TRY(nd_launch_utnet_stitch(tp.buf[T4B], funit, fw, fw + 3 * funit, canvas, width, height, cs, ucs, ol, t0, cnt, tile_ok, c.s));
         t0 += cnt;
     }
     return ND_OK;
+}
+
+extern "C" int nd_utnet_denoise_frame(int funit, int act, int dtype, int flags, const void *packed, const float *img, float *canvas,
+                                      int width, int height, int cs, int ucs, int ol, int tile_begin, int tile_count, int batch,
+                                      void *ws, size_t ws_bytes, void *fws, size_t fws_bytes, void *stream, nd_progress_fn progress,
+                                      void *progress_ctx) {
+    return denoise_frame(funit, act, dtype, flags, packed, img, canvas, width, height, cs, ucs, ol, tile_begin, tile_count, batch, ws, ws_bytes,
+                         fws, fws_bytes, stream, progress, progress_ctx, nullptr);
+}
+
+extern "C" int nd_utnet_denoise_frame_checked(int funit, int act, int dtype, int flags, const void *packed, const float *img, float *canvas,
+                                              int width, int height, int cs, int ucs, int ol, int tile_begin, int tile_count, int batch,
+                                              void *ws, size_t ws_bytes, void *fws, size_t fws_bytes, void *stream,
+                                              nd_progress_fn progress, void *progress_ctx, unsigned char *tile_ok) {
+    if (!tile_ok) ND_FAIL(ND_EINVAL, "nd_utnet_denoise_frame_checked: null tile_ok");
+    return denoise_frame(funit, act, dtype, flags, packed, img, canvas, width, height, cs, ucs, ol, tile_begin, tile_count, batch, ws, ws_bytes,
+                         fws, fws_bytes, stream, progress, progress_ctx, tile_ok);
 }

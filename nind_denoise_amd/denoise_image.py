@@ -147,7 +147,8 @@ def build_parser():
                              'UtNet: funit, activation (guessed from the model path only when this option is absent) and '
                              'compute_dtype=f32|bf16|f16: bf16 / f16 store activations and weights in 16 bits with fp32 accumulation '
                              '(funit a multiple of 16; several times faster; UtNet(64) at cs 264 against the f32 output: bf16 70.6 dB '
-                             'PSNR, f16 89.7 dB). A 16-bit result that is not finite (f16 overflows at 65504) is refused, not written')
+                             'PSNR, f16 89.7 dB). A 16-bit result that is not finite (f16 overflows at 65504) is refused, not written; '
+                             'fallback_dtype=bf16|f32 (for f16; f32 for bf16) recomputes just the tiles that overflow in that type')
     parser.add_argument('--max_subpixels', type=int, help='Max. number of sub-pixels, abort if exceeded.')
     parser.add_argument('--whole_image', action='store_true', help='Ignore cs and ucs, denoise whole image')
     parser.add_argument('--pad', type=int, help='Padding amt per side, only used for whole image (otherwise (cs-ucs)/2')
@@ -269,11 +270,20 @@ def denoise_file(model, inpath, outpath, cs, ucs, overlap, batch=32, whole_image
             if debug:
                 newimg = _denoise_frame_debug(model, ds, cs, ucs, overlap, batch, outpath, dbg_dir)
             else:
-                newimg = pipeline.denoise_frame(model, ds.inimg, cs, ucs, overlap, batch=batch, progress=progress)
+                report = {}
+                newimg = pipeline.denoise_frame(model, ds.inimg, cs, ucs, overlap, batch=batch, progress=progress, report=report)
+                if pipeline.fallback_line(report):      # (tiles recomputed in the model's fallback_dtype)
+                    print(pipeline.fallback_line(report))
         dtype = getattr(model, 'compute_dtype', 'f32')
         if dtype != 'f32' and not torch.isfinite(newimg).all():
-            # 16-bit storage with weights or activations past its range (fp16: 65504): nothing is written.  fp32 runs are not checked
+            # 16-bit storage with weights or activations past its range (fp16: 65504): nothing is written.  fp32 runs are not checked.
+            # With a fallback_dtype only what the fallback could not mend arrives here: a NaN in the input, a fallback that overflows too
             bad = int((~torch.isfinite(newimg)).sum())
+            fallback = getattr(model, 'fallback_dtype', None)
+            if fallback is not None and not whole_image and not debug:
+                raise FloatingPointError(f'{bad} of {newimg.numel()} output samples are not finite with compute_dtype={dtype}, '
+                                         f'fallback_dtype={fallback} for {inpath if raw_path else "the frame"}; nothing written: the '
+                                         'input is not finite, or the fallback overflows too (use f32)')
             raise FloatingPointError(f'{bad} of {newimg.numel()} output samples are not finite with compute_dtype={dtype} '
                                      f'for {inpath if raw_path else "the frame"}; nothing written: use bf16 or f32')
         # (sample conversion / HWC transpose on the GPU, then the download: the device section ends inside this call)

@@ -27,6 +27,27 @@ def canonical_compute_dtype(name):
     return _SHORT_DTYPE[_lib.DTYPE[name]]
 
 
+# compute dtype -> the dtypes with more range that may redo its overflowing tiles (pipeline.denoise_frame)
+FALLBACK_DTYPES = {"f16": ("bf16", "f32"), "bf16": ("f32",)}
+
+
+def canonical_fallback_dtype(name):
+    """None for off (None, '' or 'none'), else the short form of any spelling compute_dtype takes."""
+    if name is None or (isinstance(name, str) and name.strip().lower() in ("", "none")):
+        return None
+    return canonical_compute_dtype(name)
+
+
+def check_fallback_pair(compute_dtype, fallback_dtype):
+    """The fallback of a compute dtype has more range than it: f16 -> bf16 | f32, bf16 -> f32.  Returns fallback_dtype (None: off);
+    ValueError with the choices otherwise."""
+    if fallback_dtype is None or fallback_dtype in FALLBACK_DTYPES.get(compute_dtype, ()):
+        return fallback_dtype
+    pairs = ", ".join(f"{c} -> {' | '.join(f)}" for c, f in FALLBACK_DTYPES.items())
+    raise ValueError(f"fallback_dtype={fallback_dtype!r} cannot serve compute_dtype={compute_dtype!r}; choose one of: {pairs} "
+                     "(or none)")
+
+
 def valid_cs(cs):
     """The network only accepts cs = 16k + 56 (the reference raises in torch.cat otherwise)."""
     return cs >= 104 and (cs - 56) % 16 == 0
@@ -63,10 +84,11 @@ class UtNet(nn.Module):
     share_level2 = True
     fold_skips = True
 
-    def __init__(self, funit=64, activation='PReLU', compute_dtype='f32'):
+    def __init__(self, funit=64, activation='PReLU', compute_dtype='f32', fallback_dtype=None):
         super().__init__()
         funit = int(funit)
         compute_dtype = canonical_compute_dtype(compute_dtype)
+        fallback_dtype = check_fallback_pair(compute_dtype, canonical_fallback_dtype(fallback_dtype))
         if activation not in _ACTIVATIONS:
             exit(f'UtNet: unknown activation function: {activation}')
         self.funit, self.activation = funit, activation
@@ -97,7 +119,10 @@ class UtNet(nn.Module):
         self.pack_on_device = True   # build the packed blob in HBM (nd_utnet_pack_weights_device); False: host packer
         self._workspaces = {}     # (device, h, w, batch, dtype) -> uint8 tensor
         self.max_cached_workspaces = 2
+        self._fallback_workspaces = {}   # the same for a dtype other than compute_dtype (workspace(dtype=...)): one at a time
         self.compute_dtype = compute_dtype   # storage of activations + weights inside the conv stack: "f32" | "bf16" | "f16"
+        # the frame loop redoes the tiles whose 16-bit result is not finite in this dtype (None: off; pipeline.denoise_frame)
+        self.fallback_dtype = fallback_dtype
         self.weights_generation = 0   # bumped by whoever rewrites the parameters through raw pointers (train.UtNetTrainer)
 
     def set_compute_dtype(self, name):
@@ -106,6 +131,18 @@ class UtNet(nn.Module):
         Same spellings as the constructor's compute_dtype (the model parameter `--model_parameters compute_dtype=...` sets)."""
         self.compute_dtype = canonical_compute_dtype(name)
         return self
+
+    def set_fallback_dtype(self, name):
+        """The dtype in which pipeline.denoise_frame recomputes the tiles whose result is not finite in compute_dtype: f16 -> bf16 or
+        f32, bf16 -> f32; None, '' or 'none': off (a non-finite 16-bit frame is then refused by its callers).  Same spellings as
+        compute_dtype (the model parameter `--model_parameters compute_dtype=f16,fallback_dtype=f32` sets both).  set_compute_dtype may
+        change the pair afterwards, so the frame loop checks it again (checked_fallback_dtype)."""
+        self.fallback_dtype = check_fallback_pair(self.compute_dtype, canonical_fallback_dtype(name))
+        return self
+
+    def checked_fallback_dtype(self):
+        """fallback_dtype (None: off) after checking it against the compute dtype as it stands now."""
+        return check_fallback_pair(self.compute_dtype, self.fallback_dtype)
 
     @property
     def _dt(self):
@@ -127,18 +164,21 @@ class UtNet(nn.Module):
     def _weights_key(self, device):
         return (str(device), self.weights_generation) + tuple((p.data_ptr(), p._version) for p in self.parameters())
 
-    def packed_weights(self, device):
-        """Packed blob in HBM (re-packed when a parameter changed or moved)."""
+    def packed_weights(self, device, dtype=None):
+        """Packed blob in HBM (re-packed when a parameter changed or moved).  dtype: pack for another storage type than
+        compute_dtype (the fallback's), which stays as it is."""
+        dtype = self.compute_dtype if dtype is None else canonical_compute_dtype(dtype)
+        dt = _lib.DTYPE[dtype]
         key = self._weights_key(device)
-        hit = self._packed.get(self.compute_dtype)
+        hit = self._packed.get(dtype)
         if hit is not None and hit[0] == key:
             return hit[1]
         lib = _lib.load()
         sd = self.state_dict()
         names = _lib.utnet_tensor_names()
-        nbytes = lib.nd_utnet_packed_bytes(self.funit, self._dt)
+        nbytes = lib.nd_utnet_packed_bytes(self.funit, dt)
         if nbytes == 0:
-            raise ValueError(f"UtNet: funit={self.funit} is not supported by the HIP path for {self.compute_dtype} "
+            raise ValueError(f"UtNet: funit={self.funit} is not supported by the HIP path for {dtype} "
                              "(multiple of 8 for f32, of 16 for bf16 / f16)")
         on_device = self.pack_on_device
         where = device if on_device else "cpu"     # pack in HBM (device-side packers), or on the host (the yardstick)
@@ -154,31 +194,36 @@ class UtNet(nn.Module):
         if on_device:
             dev_blob = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
             with torch.cuda.device(device):
-                _lib.check(lib.nd_utnet_pack_weights_device(self.funit, self._dt, ptrs, len(names), dev_blob.data_ptr(), nbytes,
+                _lib.check(lib.nd_utnet_pack_weights_device(self.funit, dt, ptrs, len(names), dev_blob.data_ptr(), nbytes,
                                                             _lib.stream_ptr(device)), "nd_utnet_pack_weights_device")
                 torch.cuda.current_stream(device).synchronize()     # `keep` may be freed after this
         else:
             blob = torch.empty(nbytes // 4, dtype=torch.float32)
-            _lib.check(lib.nd_utnet_pack_weights(self.funit, self._dt, ptrs, len(names), blob.data_ptr(), nbytes),
+            _lib.check(lib.nd_utnet_pack_weights(self.funit, dt, ptrs, len(names), blob.data_ptr(), nbytes),
                        "nd_utnet_pack_weights")
             dev_blob = blob.to(device)
-        self._packed[self.compute_dtype] = (key, dev_blob)
+        self._packed[dtype] = (key, dev_blob)
         return dev_blob
 
-    def workspace(self, cs, batch, device, width=None):
-        """Activation workspace for [batch,3,cs,width or cs] inputs (zero borders initialised once, then cached)."""
+    def workspace(self, cs, batch, device, width=None, dtype=None):
+        """Activation workspace for [batch,3,cs,width or cs] inputs (zero borders initialised once, then cached).  dtype: size it for
+        another storage type than compute_dtype (the fallback's); those are cached apart (one at a time), so that the frame
+        loop's own workspace stays where it is while a few tiles are redone."""
         h, w = int(cs), int(cs if width is None else width)
-        key = (str(device), h, w, int(batch), self.compute_dtype)
-        ws = self._workspaces.get(key)
+        other = dtype is not None and canonical_compute_dtype(dtype) != self.compute_dtype
+        dtype = canonical_compute_dtype(dtype) if other else self.compute_dtype
+        cache = self._fallback_workspaces if other else self._workspaces
+        key = (str(device), h, w, int(batch), dtype)
+        ws = cache.get(key)
         if ws is None:
             lib = _lib.load()
 
             def drop():
-                while len(self._workspaces) >= self.max_cached_workspaces:
-                    self._workspaces.pop(next(iter(self._workspaces)))
-            ws = _lib.make_workspace(lib.nd_utnet_workspace_bytes_hw, lib.nd_utnet_workspace_init_hw, (self.funit, h, w, batch, self._dt),
-                                     device, "UtNet", drop=drop)
-            self._workspaces[key] = ws
+                while len(cache) >= (1 if other else self.max_cached_workspaces):
+                    cache.pop(next(iter(cache)))
+            ws = _lib.make_workspace(lib.nd_utnet_workspace_bytes_hw, lib.nd_utnet_workspace_init_hw,
+                                     (self.funit, h, w, batch, _lib.DTYPE[dtype]), device, "UtNet", drop=drop)
+            cache[key] = ws
         return ws
 
     def frame_workspace(self, width, height, cs, ucs, ol, batch, device):
