@@ -125,11 +125,16 @@ __global__ void k_adam_guarded(float *__restrict__ p, const float *__restrict__ 
 }
 
 // ------------------------------------------------------------------ C ABI
+// Adam's bias correction 1 - b^step, in double on the host and rounded once for the kernel (as torch takes 1 - beta ** step).
+// In fp32 the subtraction cancels at small steps: 1 - 0.999^2 = 0.002 carries the 6e-8 spacing of 0.998, 1e-5 of itself, and
+// sqrt(bc2) scales every element's update (tests/test_adam_exact.py holds the step to float64 Adam)
+static float bias_correction(float b, int step) { return (float)(1.0 - pow((double)b, (double)step)); }
+
 // torch.optim.Adam(params, lr, betas=(b1,b2), eps, amsgrad) on flat buffers; step = 1, 2, ...
 extern "C" int nd_adam_step(float *params, const float *grads, float *m, float *v, float *vmax, size_t n, float lr, float b1,
                             float b2, float eps, int step, int amsgrad, void *stream) {
     if (!params || !grads || !m || !v || (amsgrad && !vmax) || step < 1) ND_FAIL(ND_EINVAL, "nd_adam_step: bad arguments");
-    const float bc1 = 1.f - powf(b1, (float)step), bc2 = 1.f - powf(b2, (float)step);
+    const float bc1 = bias_correction(b1, step), bc2 = bias_correction(b2, step);
     hipLaunchKernelGGL(k_adam, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, grads, m, v, vmax,
                        (long)n, lr, b1, b2, eps, bc1, bc2, amsgrad);
     ND_HIP(hipGetLastError());
@@ -161,7 +166,7 @@ extern "C" int nd_adam_step_guarded(float *params, const float *grads, float *m,
                                     float b2, float eps, int step, int amsgrad, const double *state, void *stream) {
     if (!params || !grads || !m || !v || (amsgrad && !vmax) || step < 1 || !state)
         ND_FAIL(ND_EINVAL, "nd_adam_step_guarded: bad arguments");
-    const float bc1 = 1.f - powf(b1, (float)step), bc2 = 1.f - powf(b2, (float)step);
+    const float bc1 = bias_correction(b1, step), bc2 = bias_correction(b2, step);
     hipLaunchKernelGGL(k_adam_guarded, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, grads, m, v,
                        vmax, (long)n, lr, b1, b2, eps, bc1, bc2, amsgrad, state);
     ND_HIP(hipGetLastError());
