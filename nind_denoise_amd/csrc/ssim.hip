@@ -27,6 +27,30 @@ constexpr int kTile = 32;
 constexpr int kIn = kTile + kWin - 1;   // 42
 constexpr int kScales = 5;
 __constant__ float c_gauss[kWin];
+__constant__ float c_gauss_defect;      // 1 - the sum of the 11 x 11 window of fp32 taps (6.1e-8)
+
+// The level both kernels subtract from x and y before they take moments: the mean of the two images at the pixel nearest the middle of
+// the workgroup's input patch.  Variances and covariances do not see a common shift, and E[xx] - mu^2 loses digits as mu^2 / variance:
+// on a bright flat patch (level 0.9, variance 1e-5) four of fp32's seven.  One level for x and y, so that x == y stays the same
+// arithmetic for all three moments.
+//
+// The 11 x 11 window of fp32 taps adds up to 1 - e, not to 1, and piqa's score is defined on those taps: its E[xx] - mu^2 does see
+// a shift, by e times the level squared -- 1e-6 of a textured score.  With m' the moments of x - lvl:  mu = p + lvl with
+// p = m0' - e lvl, and s_xx = (m2' + e lvl^2) - p^2 (s_yy, s_xy alike) are piqa's quantities, identically; d s_xx / d m0' = -2 p.
+struct Shifted {
+    float p0, p1, m2, m3, m4;
+};
+__device__ __forceinline__ Shifted shifted_moments(const float *m, float lvl) {
+#pragma clang fp contract(off)
+    const float el = c_gauss_defect * lvl, k = el * lvl;
+    return {m[0] - el, m[1] - el, m[2] + k, m[3] + k, m[4] + k};
+}
+__device__ __forceinline__ float patch_level(const float *__restrict__ xp, const float *__restrict__ yp, int H, int W, int cy, int cx) {
+    cy = min(max(cy, 0), H - 1);
+    cx = min(max(cx, 0), W - 1);
+    return 0.5f * (xp[(size_t)cy * W + cx] + yp[(size_t)cy * W + cx]);
+}
+
 const float kMsWeights[kScales] = {0.0448f, 0.2856f, 0.3001f, 0.2363f, 0.1333f};
 
 // grid (tiles_x, tiles_y, planes); x, y: [planes][H][W]
@@ -38,12 +62,13 @@ __global__ __launch_bounds__(256) void k_ssim_tile(const float *__restrict__ x, 
     const int plane = blockIdx.z;
     const int ox0 = blockIdx.x * kTile, oy0 = blockIdx.y * kTile;
     const float *xp = x + (size_t)plane * H * W, *yp = y + (size_t)plane * H * W;
+    const float lvl = patch_level(xp, yp, H, W, oy0 + kIn / 2, ox0 + kIn / 2);
     for (int i = threadIdx.x; i < kIn * kIn; i += 256) {
         const int r = i / kIn, c = i - r * kIn;
         const int gy = oy0 + r, gx = ox0 + c;
         const bool in = gy < H && gx < W;
-        sx[r][c] = in ? xp[(size_t)gy * W + gx] : 0.f;
-        sy[r][c] = in ? yp[(size_t)gy * W + gx] : 0.f;
+        sx[r][c] = in ? xp[(size_t)gy * W + gx] - lvl : 0.f;
+        sy[r][c] = in ? yp[(size_t)gy * W + gx] - lvl : 0.f;
     }
     __syncthreads();
     for (int i = threadIdx.x; i < kIn * kTile; i += 256) {
@@ -82,8 +107,10 @@ __global__ __launch_bounds__(256) void k_ssim_tile(const float *__restrict__ x, 
         {
 #pragma clang fp contract(off)
             // every product and sum below rounds once, as written: with x == y numerator and denominator are the same number
-            const float mxx = m[0] * m[0], myy = m[1] * m[1], mxy = m[0] * m[1];
-            const float sxx = fmaf(-m[0], m[0], m[2]), syy = fmaf(-m[1], m[1], m[3]), sxy = fmaf(-m[0], m[1], m[4]);
+            const Shifted t = shifted_moments(m, lvl);
+            const float ux = t.p0 + lvl, uy = t.p1 + lvl;   // the means themselves: only the luminance term sees the level
+            const float mxx = ux * ux, myy = uy * uy, mxy = ux * uy;
+            const float sxx = fmaf(-t.p0, t.p0, t.m2), syy = fmaf(-t.p1, t.p1, t.m3), sxy = fmaf(-t.p0, t.p1, t.m4);
             const float two_sxy = sxy + sxy, two_mxy = mxy + mxy;
             cs = (two_sxy + c2) / ((sxx + syy) + c2);
             ss = (two_mxy + c1) / ((mxx + myy) + c1) * cs;
@@ -172,6 +199,10 @@ __global__ __launch_bounds__(256) void k_sqdiff_partial(const float *__restrict_
 // (G^T = the same separable window applied as a FULL correlation over the valid score positions q).
 // One workgroup: 16 x 16 gradient pixels <- derivative maps at 26 x 26 score positions <- a 36 x 36 patch of x and y.
 // gx(u) (+)= coef[plane] * dF/dx(u) + gcoarse(u/2) / (pixels of that pooling window)      [avg_pool2d(2, ceil) backward]
+// The moments are k_ssim_tile's, operation for operation (explicit fmaf, the patch level subtracted, explicit roundings after them):
+// with x == y the gradient is exactly 0, and where x is within 2e-3 of y or the patch is bright and flat every edge class is within
+// 4x of what torch's fp32 autograd loses against float64 (tests/test_ssim_float64.py); left to the compiler's contraction on
+// unshifted moments it was up to 19x.
 constexpr int kBT = 16;
 constexpr int kBQ = kBT + kWin - 1;    // 26 score positions per side
 constexpr int kBI = kBQ + kWin - 1;    // 36 input pixels per side
@@ -187,25 +218,27 @@ __global__ __launch_bounds__(256) void k_ssim_bwd_tile(const float *__restrict__
     const int ux0 = blockIdx.x * kBT, uy0 = blockIdx.y * kBT;   // first gradient pixel of the tile
     const int qx0 = ux0 - (kWin - 1), qy0 = uy0 - (kWin - 1);   // first score position it depends on
     const float *xp = x + (size_t)plane * H * W, *yp = y + (size_t)plane * H * W;
+    const float lvl = patch_level(xp, yp, H, W, uy0 + kBT / 2, ux0 + kBT / 2);
     for (int i = threadIdx.x; i < kBI * kBI; i += 256) {
         const int r = i / kBI, c = i - r * kBI;
         const int gy_ = qy0 + r, gx_ = qx0 + c;
         const bool in = gy_ >= 0 && gy_ < H && gx_ >= 0 && gx_ < W;
-        sx[r][c] = in ? xp[(size_t)gy_ * W + gx_] : 0.f;
-        sy[r][c] = in ? yp[(size_t)gy_ * W + gx_] : 0.f;
+        sx[r][c] = in ? xp[(size_t)gy_ * W + gx_] - lvl : 0.f;
+        sy[r][c] = in ? yp[(size_t)gy_ * W + gx_] - lvl : 0.f;
     }
     __syncthreads();
+    // the moments of k_ssim_tile, operation for operation (explicit fmaf, the level subtracted)
     for (int i = threadIdx.x; i < kBI * kBQ; i += 256) {
         const int r = i / kBQ, c = i - r * kBQ;
         float a = 0.f, b = 0.f, aa = 0.f, bb = 0.f, ab = 0.f;
 #pragma unroll
         for (int k = 0; k < kWin; ++k) {
             const float g = c_gauss[k], u = sx[r][c + k], v = sy[r][c + k];
-            a += g * u;
-            b += g * v;
-            aa += g * (u * u);
-            bb += g * (v * v);
-            ab += g * (u * v);
+            a = fmaf(g, u, a);
+            b = fmaf(g, v, b);
+            aa = fmaf(g, u * u, aa);
+            bb = fmaf(g, v * v, bb);
+            ab = fmaf(g, u * v, ab);
         }
         hm[0][r][c] = a;
         hm[1][r][c] = b;
@@ -226,21 +259,30 @@ __global__ __launch_bounds__(256) void k_ssim_bwd_tile(const float *__restrict__
             for (int k = 0; k < kWin; ++k) {
                 const float g = c_gauss[k];
 #pragma unroll
-                for (int q = 0; q < 5; ++q) m[q] += g * hm[q][r + k][c];
+                for (int q = 0; q < 5; ++q) m[q] = fmaf(g, hm[q][r + k][c], m[q]);
             }
-            const float mx = m[0], my = m[1];
-            const float a2 = 2.f * (m[4] - mx * my) + c2, b2 = (m[2] - mx * mx) + (m[3] - my * my) + c2;
-            const float cs = a2 / b2;
-            const float dcs_mx = 2.f / b2 * (mx * cs - my), dcs_xx = -cs / b2, dcs_xy = 2.f / b2;
-            if (use_ss) {
-                const float b1 = mx * mx + my * my + c1, l = (2.f * mx * my + c1) / b1;
-                A = 2.f / b1 * (my - mx * l) * cs + l * dcs_mx;
-                B = l * dcs_xx;
-                C = l * dcs_xy;
-            } else {
-                A = dcs_mx;
-                B = dcs_xx;
-                C = dcs_xy;
+            {
+#pragma clang fp contract(off)
+                // Every product and sum rounds once, as written.  With x == y: cs = l = 1, A = 0 and C = -2 B, all exactly.
+                // Derivatives with respect to the moments of x - lvl (see shifted_moments).
+                const Shifted t = shifted_moments(m, lvl);
+                const float sxx = fmaf(-t.p0, t.p0, t.m2), syy = fmaf(-t.p1, t.p1, t.m3), sxy = fmaf(-t.p0, t.p1, t.m4);
+                const float b2 = (sxx + syy) + c2, cs = ((sxy + sxy) + c2) / b2;
+                const float inv = 1.f / b2;
+                const float dcs_mx = (inv + inv) * fmaf(t.p0, cs, -t.p1), dcs_xx = -cs * inv, dcs_xy = inv + inv;
+                if (use_ss) {
+                    const float ux = t.p0 + lvl, uy = t.p1 + lvl;
+                    const float mxx = ux * ux, myy = uy * uy, mxy = ux * uy;
+                    const float b1 = (mxx + myy) + c1, l = ((mxy + mxy) + c1) / b1;
+                    const float dl = 2.f / b1 * fmaf(-ux, l, uy);
+                    A = dl * cs + l * dcs_mx;
+                    B = l * dcs_xx;
+                    C = l * dcs_xy;
+                } else {
+                    A = dcs_mx;
+                    B = dcs_xx;
+                    C = dcs_xy;
+                }
             }
         }
         dm[0][r][c] = A;
@@ -255,9 +297,9 @@ __global__ __launch_bounds__(256) void k_ssim_bwd_tile(const float *__restrict__
 #pragma unroll
         for (int k = 0; k < kWin; ++k) {
             const float g = c_gauss[k];
-            a += g * dm[0][r][c + kWin - 1 - k];
-            b += g * dm[1][r][c + kWin - 1 - k];
-            d += g * dm[2][r][c + kWin - 1 - k];
+            a = fmaf(g, dm[0][r][c + kWin - 1 - k], a);
+            b = fmaf(g, dm[1][r][c + kWin - 1 - k], b);
+            d = fmaf(g, dm[2][r][c + kWin - 1 - k], d);
         }
         rm[0][r][c] = a;
         rm[1][r][c] = b;
@@ -266,6 +308,7 @@ __global__ __launch_bounds__(256) void k_ssim_bwd_tile(const float *__restrict__
     __syncthreads();
     const float cf = coef[plane];
     {
+#pragma clang fp contract(off)
         const int r = threadIdx.x / kBT, c = threadIdx.x - r * kBT;
         const int uy = uy0 + r, ux = ux0 + c;
         if (uy < H && ux < W) {
@@ -273,19 +316,20 @@ __global__ __launch_bounds__(256) void k_ssim_bwd_tile(const float *__restrict__
 #pragma unroll
             for (int k = 0; k < kWin; ++k) {
                 const float g = c_gauss[k];
-                a += g * rm[0][r + kWin - 1 - k][c];
-                b += g * rm[1][r + kWin - 1 - k][c];
-                d += g * rm[2][r + kWin - 1 - k][c];
+                a = fmaf(g, rm[0][r + kWin - 1 - k][c], a);
+                b = fmaf(g, rm[1][r + kWin - 1 - k][c], b);
+                d = fmaf(g, rm[2][r + kWin - 1 - k][c], d);
             }
+            // x and y less the level, as the moments took them; with x == y the two products are each other's negative
             const float xv = sx[r + kWin - 1][c + kWin - 1], yv = sy[r + kWin - 1][c + kWin - 1];
-            float g = cf * (a + 2.f * xv * b + yv * d);
+            float g = cf * ((a + (xv + xv) * b) + yv * d);
             if (gcoarse) {
                 const int oy = uy >> 1, ox = ux >> 1;
                 const int ny = 2 * oy + 1 < H ? 2 : 1, nx = 2 * ox + 1 < W ? 2 : 1;
                 g += gcoarse[((size_t)plane * H2 + oy) * W2 + ox] / (float)(ny * nx);
             }
             float *dst = gx + ((size_t)plane * H + uy) * W + ux;
-            *dst = accumulate ? *dst + g : g;
+            *dst = accumulate ? *dst + g : g;      // one fp32 add onto what gx held
         }
     }
 }
@@ -368,15 +412,25 @@ SsimPlan ssim_plan(int n, int c, int h, int w, char *base, bool with_grad = fals
 }
 
 int write_window() {
+    // fp32 values of torch's kernel / kernel.sum().  torch adds the 11 terms in an order that lands on the correctly rounded sum (a
+    // double sum, rounded once: as make_taps of ssim_padded.hip); added one after the other in fp32 the sum is one ulp lower, the taps
+    // add up to 1 + 4.5e-8 instead of 1 - 3.1e-8, and mu^2 (1 + 2 d) against E[xx] (1 + d) pulls a textured score 3e-6 down.
     float g[kWin];
-    float s = 0.f;   // fp32 throughout, like torch's kernel / kernel.sum()
+    double sum = 0.;
     for (int k = 0; k < kWin; ++k) {
         const float d = (float)k - (kWin - 1) / 2.f;
         g[k] = expf(-(d * d) / (2.f * 1.5f * 1.5f));
-        s += g[k];
+        sum += (double)g[k];
     }
-    for (int k = 0; k < kWin; ++k) g[k] /= s;
+    const float s = (float)sum;
+    double taps = 0.;
+    for (int k = 0; k < kWin; ++k) {
+        g[k] /= s;
+        taps += (double)g[k];
+    }
+    const float defect = (float)(1. - taps * taps);   // the window is the taps twice, along rows and along columns
     ND_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_gauss), g, sizeof(g)));
+    ND_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_gauss_defect), &defect, sizeof(defect)));
     return ND_OK;
 }
 int upload_window() {   // __constant__ memory is per device
