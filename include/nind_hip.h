@@ -103,6 +103,11 @@ typedef enum nd_flags {
                                  ConvTranspose2d(3) layers of a launch -- bottom.2, tconvs1.0 at cs 264 -- under one tile grid over a
                                  mosaic of the launch's images, nd_wino_mosaic; fp32 re-association in the tiles that straddle a seam).  Taken by every
                                  flags-taking entry point                                                                         */
+    ND_FLAG_UNET_WINOGRAD = 1024, /* the UNet inference entry points only (nd_unet_*_flags, nd_unet_denoise_frame, nd_unet_step_form,
+                                 nd_unet_profile_stack; an unknown bit everywhere else): the 3x3 layers in Winograd forms -- three-pass
+                                 F(6x6,3x3) where Cin >= 128, Cout >= 128 and Cin * Cout >= 128 * 256, fused F(4,3) below, direct for
+                                 the 3-channel first layer and where a form does not take the layer's geometry.  Opt-in: ~1e-6
+                                 re-association against the default path.  Blob, workspace and call must agree on the bit          */
     ND_FLAG_FULL_TILES = 8    /* nd_utnet_denoise_tiles / nd_utnet_profile_stack: compute every layer on the whole tile, as
                                  UtNet.forward does.  Default there: the last decoder levels compute only the pixels that the
                                  useful crop [pad, cs - pad) of a tile can reach (denoise_image.py:249-258 discards the rest of
@@ -314,6 +319,29 @@ int nd_unet_forward(int dtype, const void *packed_dev, const float *x_nchw, floa
 int nd_unet_pack_weights_device(int dtype, const float *const *dev_tensors, int n_tensors, void *packed_dev, size_t packed_bytes,
                                 void *stream);
 
+/* The same family with nd_flags; flags = 0 is the plain entry point above, byte for byte.  ND_FLAG_UNET_WINOGRAD: the packed blob
+ * carries the Winograd forms behind the default blob (no offset of the default blob moves; host and device packers write the same
+ * bytes), the workspace carries the three-pass V / M scratch behind the default workspace, and nd_unet_forward_flags /
+ * nd_unet_denoise_frame run the forms of nd_unet_step_form.  A blob or workspace made without the bit is too small for a call with it
+ * (ND_ENOMEM for the workspace; the caller keeps blob and call in step).  The zero borders of the activation buffers stay zero.
+ * nd_unet_forward_flags takes the known bits of nd_flags and ND_FLAG_UNET_WINOGRAD (ND_FLAG_DIRECT_CONV: every layer direct on the
+ * same blob; ND_FLAG_W1D_REGS: the F(4,3) layers through conv_w1d where the row fits it, else direct). */
+size_t nd_unet_packed_bytes_flags(int dtype, int flags);
+int nd_unet_pack_weights_flags(int dtype, int flags, const float *const *tensors, int n_tensors, void *packed_host, size_t packed_bytes);
+int nd_unet_pack_weights_device_flags(int dtype, int flags, const float *const *dev_tensors, int n_tensors, void *packed_dev,
+                                      size_t packed_bytes, void *stream);
+size_t nd_unet_workspace_bytes_flags(int h, int w, int batch, int dtype, int flags);
+int nd_unet_workspace_init_flags(void *workspace, size_t workspace_bytes, int h, int w, int batch, int dtype, int flags, void *stream);
+int nd_unet_forward_flags(int dtype, int flags, const void *packed_dev, const float *x_nchw, float *y_nchw, int batch, int h, int w,
+                          void *workspace, size_t workspace_bytes, void *stream);
+/* Host-only: the `form` code of nd_step_profile (-1 pool, 0 direct, 1 fused F(4,3), 3 three-pass F(6x6,3x3)) of step `step` in a
+ * whole forward of batch x 3 x h x w under `flags`; a bad argument gives ND_EINVAL - 100. */
+int nd_unet_step_form(int flags, int batch, int h, int w, int step);
+/* The UNet twin of nd_utnet_profile_stack: one pass of the 26 steps on `batch` tiles of cs x cs (whatever the workspace holds) with an
+ * event between steps; crop > 0 restricts the decoder as nd_unet_denoise_frame does.  blob and workspace: those of `flags`. */
+int nd_unet_profile_stack(int flags, const void *packed_dev, int batch, int cs, int crop, void *workspace, size_t workspace_bytes,
+                          void *stream, nd_step_profile *steps, int max_steps);
+
 /* Host-only: the step list of the UNet stack (26 steps: 22 conv launches and 4 pools, between the input pack and the final 1x1).
  * nd_unet_step_name: module path of the step's layer ("inc.conv.conv.0", "up1.up", ...), "pool" for pools.
  * nd_unet_useful_region: region {r0, c0, rows, cols} of step `step` that nd_unet_denoise_frame computes when the centre
@@ -332,8 +360,11 @@ int nd_unet_useful_region(int cs, int crop, int step, int *rect);
  * direct kernel) unless ND_FLAG_FULL_TILES is set: same canvas bit for bit under ND_FLAG_NO_SPLITK, else up to fp32
  * re-association of the split-K tail.  workspace: nd_unet_workspace_bytes(cs, cs, batch, ND_F32), initialised by
  * nd_unet_workspace_init.  dtype: ND_F32 only.  flags: ND_FLAG_NO_SPLITK, ND_FLAG_FULL_TILES and ND_FLAG_FIND_NOISE switch something
- * here; the other known bits of nd_flags (Winograd forms, fused pools, shared encoder: this stack has none of them) are accepted and
- * ignored; unknown bits are an error.  progress: as in nd_utnet_denoise_frame. */
+ * here; the other known bits of nd_flags (fused pools, shared encoder: this stack has none of them) are accepted and ignored; unknown
+ * bits are an error.  ND_FLAG_UNET_WINOGRAD: the Winograd forms, on the blob and the workspace of the *_flags entry points with the
+ * same bit; a restricted decoder layer runs in its form where the form takes the region, else direct (with it, ND_FLAG_DIRECT_CONV
+ * and ND_FLAG_W1D_REGS mean what they mean for UtNet; no UNet layer is a transposed 3x3, so none takes the mosaic that
+ * ND_FLAG_TILE_WINO switches off).  progress: as in nd_utnet_denoise_frame. */
 int nd_unet_denoise_frame(int dtype, int flags, const void *packed_dev, const float *img_chw, float *canvas_chw, int width,
                           int height, int cs, int ucs, int ol, int tile_begin, int tile_count, int batch, void *workspace,
                           size_t workspace_bytes, void *stream, nd_progress_fn progress, void *progress_ctx);

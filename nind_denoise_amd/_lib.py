@@ -18,6 +18,7 @@ FLAG_NO_SPLITK, FLAG_DIRECT_CONV, FLAG_W1D_REGS, FLAG_FULL_TILES, FLAG_UNFUSED_P
 FLAG_FIND_NOISE = 128   # nd_unet_denoise_frame only
 FLAG_TILE_SKIPS = 256   # frame-loop entry points only: the skip halves of tconvs4.0 / 3.0 / 2.0 stay in the per-tile sums
 FLAG_TILE_WINO = 512    # every three-pass Winograd layer on per-image tile grids (no mosaic of the launch's images: nd_wino_mosaic)
+FLAG_UNET_WINOGRAD = 1024   # UNet inference entry points only: the 3x3 layers in Winograd forms (UNet(winograd=True))
 # nd_progress_fn: (ctx, launch index, first tile, tile count)
 PROGRESS_FN = ctypes.CFUNCTYPE(None, c_void_p, c_int, c_int, c_int)
 
@@ -72,6 +73,14 @@ _SIGNATURES = {
     "nd_unet_workspace_init": (c_int, [c_void_p, c_size_t] + [c_int] * 4 + [c_void_p]),
     "nd_unet_forward": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "nd_unet_pack_weights_device": (c_int, [c_int, POINTER(c_void_p), c_int, c_void_p, c_size_t, c_void_p]),
+    "nd_unet_packed_bytes_flags": (c_size_t, [c_int, c_int]),
+    "nd_unet_pack_weights_flags": (c_int, [c_int, c_int, POINTER(c_void_p), c_int, c_void_p, c_size_t]),
+    "nd_unet_pack_weights_device_flags": (c_int, [c_int, c_int, POINTER(c_void_p), c_int, c_void_p, c_size_t, c_void_p]),
+    "nd_unet_workspace_bytes_flags": (c_size_t, [c_int] * 5),
+    "nd_unet_workspace_init_flags": (c_int, [c_void_p, c_size_t] + [c_int] * 5 + [c_void_p]),
+    "nd_unet_forward_flags": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "nd_unet_step_form": (c_int, [c_int] * 5),
+    "nd_unet_profile_stack": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_int]),
     "nd_unet_num_steps": (c_int, []),
     "nd_unet_step_name": (c_char_p, [c_int]),
     "nd_unet_useful_region": (c_int, [c_int, c_int, c_int, POINTER(c_int)]),

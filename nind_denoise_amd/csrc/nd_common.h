@@ -194,6 +194,10 @@ long nd_wino_launch_tiles(int T, const ConvDesc &d);
 // algorithmic HBM bytes of the two transform passes of a three-pass layer (X read + V written; M read + Y written); tiles: what its
 // launches ran (nd_wino_launch_tiles; 0: per-image grids)
 void nd_wino_xform_bytes(int T, const QpBuf &in, int cin, int cout, long tiles, double *bytes_in, double *bytes_out);
+// the tiles both networks' executors run the Winograd forms at (measurements: utnet_net.h)
+constexpr int kWinoTile = 6;     // three-pass F(6x6,3x3)
+constexpr int kW1dTile = 4;      // fused F(4,3)
+constexpr int kWinoChunk = 256;  // images per three-pass Winograd pass: bounds the V / M scratch
 // 1-D Winograd F(2,3) along x inside the implicit-GEMM kernel (conv_w1d.hip): fp32 inference form of the narrow 3x3 layers
 // (T = 2: F(2,3), 2/3 of the MFMAs;  T = 4: F(4,3), 1/2)
 size_t nd_w1d_packed_floats(int T, int cin, int cout);
@@ -231,10 +235,12 @@ int nd_check_int32(const char *who, const QpBuf &in);
 int nd_check_roi(const char *who, const ConvDesc &d, int Hv, int Wv, bool refused, const char *why);
 // the arithmetic switches every flags-taking entry point accepts (include/nind_hip.h: nd_flags); unknown bits are an error.
 // frame_loop: the frame-loop entry points (nd_utnet_frame_*, nd_utnet_denoise_frame) also take ND_FLAG_TILE_LEVEL2 and
-// ND_FLAG_TILE_SKIPS, which mean nothing anywhere else; unet_frame: nd_unet_denoise_frame also takes ND_FLAG_FIND_NOISE
-static inline int nd_check_flags(int flags, bool frame_loop = false, bool unet_frame = false) {
+// ND_FLAG_TILE_SKIPS, which mean nothing anywhere else; unet_frame: nd_unet_denoise_frame also takes ND_FLAG_FIND_NOISE; unet_wino:
+// the UNet inference entry points also take ND_FLAG_UNET_WINOGRAD
+static inline int nd_check_flags(int flags, bool frame_loop = false, bool unet_frame = false, bool unet_wino = false) {
     const int known = ND_FLAG_NO_SPLITK | ND_FLAG_DIRECT_CONV | ND_FLAG_W1D_REGS | ND_FLAG_FULL_TILES | ND_FLAG_UNFUSED_POOL |
-                      ND_FLAG_TILE_ENCODER | ND_FLAG_TILE_WINO | (frame_loop ? ND_FLAG_TILE_LEVEL2 | ND_FLAG_TILE_SKIPS : 0) | (unet_frame ? ND_FLAG_FIND_NOISE : 0);
+                      ND_FLAG_TILE_ENCODER | ND_FLAG_TILE_WINO | (frame_loop ? ND_FLAG_TILE_LEVEL2 | ND_FLAG_TILE_SKIPS : 0) | (unet_frame ? ND_FLAG_FIND_NOISE : 0) |
+                      (unet_wino ? ND_FLAG_UNET_WINOGRAD : 0);
     if (flags & ~known) ND_FAIL(ND_EINVAL, "unknown flag bits 0x%x", flags);
     return ND_OK;
 }
@@ -287,8 +293,13 @@ int nd_pack_layer_device(int kind, int cin, int cout, int dt, const float *w, co
 // operation by operation as the host packer of unet.hip does
 int nd_launch_bn_fold(int cout, const float *b, const float *g, const float *be, const float *rm, const float *rv, float *scale,
                       float *fbias, hipStream_t s);
-int nd_pack_w1d_device(int T, int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s);
-int nd_pack_wino_device(int T, int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s);
+// Winograd forms.  scale: as above (each weight times its channel's factor, rounded once, before the transform).  host_bits: the
+// transform in double, operation by operation as nd_w1d_pack / nd_wino_pack evaluate it -- the host packer's bytes (the default
+// evaluates it in fp32: ~1e-7 relative off them)
+int nd_pack_w1d_device(int T, int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s,
+                       const float *scale = nullptr, bool host_bits = false);
+int nd_pack_wino_device(int T, int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s,
+                        const float *scale = nullptr, bool host_bits = false);
 
 // ------------------------------------------------------------------ auxiliary kernels (aux_kernels.hip)
 int nd_launch_nchw_to_qp(const float *x, int C, const QpBuf &dst, int plane0, hipStream_t s);

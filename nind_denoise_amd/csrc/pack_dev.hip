@@ -2,7 +2,8 @@
 // live in HBM -- the training step re-packs every step (the weights change every step), and a model load packs here instead of
 // on host threads (the Winograd transforms of UtNet(64) take ~1 s there).  Same layouts, same maps.  The direct form packs every
 // storage type, bit for bit what the host packer writes; the Winograd forms are fp32 only and their transforms are
-// evaluated in fp32 here (the host packers use double): the packed values agree to ~1e-7 relative.
+// evaluated in fp32 here by default (the host packers use double): the packed values agree to ~1e-7 relative.  With host_bits
+// (the UNet blob) they are evaluated in double, operation by operation as on the host: the same bytes.
 #include "nd_common.h"
 
 namespace {
@@ -86,38 +87,43 @@ __global__ void k_bn_fold(int cout, const float *__restrict__ b, const float *__
     fbias[co] = d + be[co];
 }
 
-// one row of G g for F(T,3): u[0 .. T+2)
-__device__ __forceinline__ void wino_g(int T, const float *g, float *u) {
+// one row of G g for F(T,3): u[0 .. T+2).  R = float: the fp32 evaluation; R = double: the host packers' (Wino<T>::g / W1<T>::g,
+// the same operations in the same order -- no product feeds a sum, so nothing contracts into an FMA)
+template <typename R>
+__device__ __forceinline__ void wino_g(int T, const R *g, R *u) {
     if (T == 2) {
         u[0] = g[0];
-        u[1] = 0.5f * (g[0] + g[1] + g[2]);
-        u[2] = 0.5f * (g[0] - g[1] + g[2]);
+        u[1] = R(0.5) * (g[0] + g[1] + g[2]);
+        u[2] = R(0.5) * (g[0] - g[1] + g[2]);
         u[3] = g[2];
     } else if (T == 6) {
         u[0] = g[0];
-        u[1] = -2.f / 9.f * (g[0] + g[1] + g[2]);
-        u[2] = -2.f / 9.f * (g[0] - g[1] + g[2]);
-        u[3] = g[0] / 90.f + g[1] / 45.f + g[2] * 2.f / 45.f;
-        u[4] = g[0] / 90.f - g[1] / 45.f + g[2] * 2.f / 45.f;
-        u[5] = g[0] * 32.f / 45.f + g[1] * 16.f / 45.f + g[2] * 8.f / 45.f;
-        u[6] = g[0] * 32.f / 45.f - g[1] * 16.f / 45.f + g[2] * 8.f / 45.f;
+        u[1] = R(-2) / R(9) * (g[0] + g[1] + g[2]);
+        u[2] = R(-2) / R(9) * (g[0] - g[1] + g[2]);
+        u[3] = g[0] / R(90) + g[1] / R(45) + g[2] * R(2) / R(45);
+        u[4] = g[0] / R(90) - g[1] / R(45) + g[2] * R(2) / R(45);
+        u[5] = g[0] * R(32) / R(45) + g[1] * R(16) / R(45) + g[2] * R(8) / R(45);
+        u[6] = g[0] * R(32) / R(45) - g[1] * R(16) / R(45) + g[2] * R(8) / R(45);
         u[7] = g[2];
     } else {
-        u[0] = g[0] / 4.f;
-        u[1] = -(g[0] + g[1] + g[2]) / 6.f;
-        u[2] = -(g[0] - g[1] + g[2]) / 6.f;
-        u[3] = g[0] / 24.f + g[1] / 12.f + g[2] / 6.f;
-        u[4] = g[0] / 24.f - g[1] / 12.f + g[2] / 6.f;
+        u[0] = g[0] / R(4);
+        u[1] = -(g[0] + g[1] + g[2]) / R(6);
+        u[2] = -(g[0] - g[1] + g[2]) / R(6);
+        u[3] = g[0] / R(24) + g[1] / R(12) + g[2] / R(6);
+        u[4] = g[0] / R(24) - g[1] / R(12) + g[2] / R(6);
         u[5] = g[2];
     }
 }
-__device__ __forceinline__ float tap3(int kind, const float *w, int cin, int cout, int co, int ci, int ky, int kx) {
-    return kind == ND_CONV3 ? w[((long)co * cin + ci) * 9 + ky * 3 + kx] : w[((long)ci * cout + co) * 9 + (8 - (ky * 3 + kx))];
+// tap (ky, kx) of the layer as a valid correlation, times its output channel's factor where there is one (one rounding, in fp32)
+__device__ __forceinline__ float tap3(int kind, const float *w, int cin, int cout, int co, int ci, int ky, int kx, const float *scale) {
+    const float v = kind == ND_CONV3 ? w[((long)co * cin + ci) * 9 + ky * 3 + kx] : w[((long)ci * cout + co) * 9 + (8 - (ky * 3 + kx))];
+    return scale ? v * scale[co] : v;
 }
 
 // fused 1-D Winograd form (conv_w1d.hip: nd_w1d_pack): [mt][kb][ky*(T+2) + xi][lane][4] + bias
+template <typename R>
 __global__ void k_pack_w1d_dev(int T, int kind, int cin, int cout, int KB, const float *__restrict__ w, const float *__restrict__ bias,
-                               float *__restrict__ packed, long nw, int nb) {
+                               float *__restrict__ packed, long nw, int nb, const float *__restrict__ scale) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const int NP = T + 2;
     if (idx < nw) {
@@ -129,12 +135,14 @@ __global__ void k_pack_w1d_dev(int T, int kind, int cin, int cout, int KB, const
         const int ky = plane / NP, xi = plane - NP * ky;
         const int m = 32 * mt + (lane & 31), ci = 8 * kb + 4 * (lane >> 5) + s;
         float v = 0.f;
-        if (m < cout && ci < cin) {
-            float g[3], u[6];
+        // (the host packer transforms the zero taps of the padding rows and channels too: positions 1 and 2 of F(4,3) hold -0.0 there)
+        const bool real = m < cout && ci < cin;
+        if (real || sizeof(R) == sizeof(double)) {
+            R g[3], u[6];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) g[k] = tap3(kind, w, cin, cout, m, ci, ky, k);
-            wino_g(T, g, u);
-            v = u[xi];
+            for (int k = 0; k < 3; ++k) g[k] = real ? R(tap3(kind, w, cin, cout, m, ci, ky, k, scale)) : R(0);
+            wino_g<R>(T, g, u);
+            v = (float)u[xi];
         }
         packed[idx] = v;
     } else if (idx < nw + nb) {
@@ -145,8 +153,9 @@ __global__ void k_pack_w1d_dev(int T, int kind, int cin, int cout, int KB, const
 
 // three-pass Winograd form (winograd.hip: nd_wino_pack): P = (T+2)^2 1-tap GEMM blobs [mt][kb][lane][4] + zero bias each,
 // then bias[cout rounded up to 4].  gf = floats per position blob, nwp = packed weights per position
+template <typename R>
 __global__ void k_pack_wino_dev(int T, int kind, int cin, int cout, int KB, const float *__restrict__ w, const float *__restrict__ bias,
-                                float *__restrict__ packed, long gf, long nwp, int P) {
+                                float *__restrict__ packed, long gf, long nwp, int P, const float *__restrict__ scale) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const int A = T + 2;
     if (idx < (long)P * gf) {
@@ -160,18 +169,18 @@ __global__ void k_pack_wino_dev(int T, int kind, int cin, int cout, int KB, cons
             const int m = 32 * mt + (lane & 31), ci = 8 * kb + 4 * (lane >> 5) + s;
             if (m < cout && ci < cin) {
                 const int i = pos / A, j = pos - A * i;
-                float col[3];   // (G g)[i][kx] for kx = 0..2
+                R col[3];   // (G g)[i][kx] for kx = 0..2
 #pragma unroll
                 for (int kx = 0; kx < 3; ++kx) {
-                    float g[3], u[8];
+                    R g[3], u[8];
 #pragma unroll
-                    for (int ky = 0; ky < 3; ++ky) g[ky] = tap3(kind, w, cin, cout, m, ci, ky, kx);
-                    wino_g(T, g, u);
+                    for (int ky = 0; ky < 3; ++ky) g[ky] = tap3(kind, w, cin, cout, m, ci, ky, kx, scale);
+                    wino_g<R>(T, g, u);
                     col[kx] = u[i];
                 }
-                float u[8];
-                wino_g(T, col, u);
-                v = u[j];
+                R u[8];
+                wino_g<R>(T, col, u);
+                v = (float)u[j];
             }
         }
         packed[idx] = v;   // (the tail of a position blob is its zero bias)
@@ -206,24 +215,26 @@ int nd_pack_layer_device(int kind, int cin, int cout, int dt, const float *w, co
     return ND_OK;
 }
 
-int nd_pack_w1d_device(int T, int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s) {
+int nd_pack_w1d_device(int T, int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s,
+                       const float *scale, bool host_bits) {
     if ((T != 2 && T != 4) || (kind != ND_CONV3 && kind != ND_CONVT3)) ND_FAIL(ND_EINVAL, "device w1d packing: T = 2 | 4, 3x3 layers");
     const int MT = nd_mtiles(ND_CONV3, cout), KB = nd_kblocks(cin);
     const long nw = (long)nd_bias_offset(kind, cin, cout, ND_F32, T);
-    hipLaunchKernelGGL(k_pack_w1d_dev, dim3((unsigned)((nw + MT * 32 + 255) / 256)), dim3(256), 0, s, T, kind, cin, cout, KB, w, bias,
-                       packed, nw, MT * 32);
+    hipLaunchKernelGGL(host_bits ? k_pack_w1d_dev<double> : k_pack_w1d_dev<float>, dim3((unsigned)((nw + MT * 32 + 255) / 256)), dim3(256), 0, s, T,
+                       kind, cin, cout, KB, w, bias, packed, nw, MT * 32, scale);
     ND_HIP(hipGetLastError());
     return ND_OK;
 }
 
-int nd_pack_wino_device(int T, int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s) {
+int nd_pack_wino_device(int T, int kind, int cin, int cout, const float *w, const float *bias, float *packed, hipStream_t s,
+                        const float *scale, bool host_bits) {
     if ((T != 2 && T != 4 && T != 6) || (kind != ND_CONV3 && kind != ND_CONVT3)) ND_FAIL(ND_EINVAL, "device Winograd packing: T = 2 | 4 | 6, 3x3 layers");
     const int P = (T + 2) * (T + 2), KB = nd_kblocks(cin);
     const long gf = (long)nd_packed_floats(ND_CONV1, cin, cout, ND_F32);
     const long nwp = (long)nd_bias_offset(ND_CONV1, cin, cout);
     const long total = (long)P * gf + (cout + 3) / 4 * 4;
-    hipLaunchKernelGGL(k_pack_wino_dev, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, T, kind, cin, cout, KB, w, bias, packed,
-                       gf, nwp, P);
+    hipLaunchKernelGGL(host_bits ? k_pack_wino_dev<double> : k_pack_wino_dev<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, T, kind,
+                       cin, cout, KB, w, bias, packed, gf, nwp, P, scale);
     ND_HIP(hipGetLastError());
     return ND_OK;
 }

@@ -442,7 +442,7 @@ int unet_forward(const GradCtx &c, float *running, float momentum, const float *
     for (int si = 0; si < kNumSteps; ++si) {
         const UStep &st = kSteps[si];
         if (!c.train || st.layer < 0 || L[st.layer].bn.empty()) {
-            ND_TRY(run_step(st, pl, c.blobs, c.bl, nullptr, nosplit, s));
+            ND_TRY(run_step(st, pl, c.blobs, c.bl, nullptr, nosplit ? ND_FLAG_NO_SPLITK : 0, s));   // (every layer direct: no Winograd form here)
             continue;
         }
         // train mode, Conv3 + BatchNorm + ReLU: the convolution without activation into z, then stats1, stats2, apply

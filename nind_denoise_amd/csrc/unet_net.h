@@ -60,17 +60,46 @@ int name_index(const std::string &s) {
     return -1;
 }
 
+// Form of every layer of layers() under ND_FLAG_UNET_WINOGRAD (the `form` codes of nd_step_profile), by the rule of utnet_net.h
+// (wino_layer / step_form): three-pass F(6x6,3x3) where Cin >= 128, Cout >= 128 and Cin * Cout >= 128 * 256, the fused F(4,3) below,
+// direct for the 3-channel first layer and for everything that is no 3x3 layer.  A layer measured slower in its Winograd form at the
+// reference tile (20 tiles of 440: DESIGN section 4) is entered as direct here, with the measurement beside it.  step_form() falls
+// back to direct where the form does not take the call's geometry.
+enum UForm { UFORM_POOL = -1, UFORM_DIRECT = 0, UFORM_F43 = 1, UFORM_WINO3P = 3 };
+const signed char kWinoPlan[] = {
+    0, 1,      // inc.conv.conv.0 (Cin 3), .3
+    1, 1,      // down1: 64 -> 128, 128 -> 128
+    3, 3,      // down2
+    3, 3,      // down3
+    3, 3,      // down4
+    0, 3, 3,   // up1.up, up1.conv.conv.0 (1024 -> 256), .3
+    0, 3, 1,   // up2.up, up2.conv.conv.0 (512 -> 128), .3 (128 -> 128)
+    0, 1, 1,   // up3.up, up3.conv.conv.0 (256 -> 64), .3
+    0, 1, 1,   // up4.up, up4.conv.conv.0 (128 -> 64), .3
+    0,         // outc.conv
+};
+
 struct Blob {
     std::vector<size_t> off;
+    std::vector<size_t> woff;   // with ND_FLAG_UNET_WINOGRAD: the layer's Winograd form (F(4,3) or three-pass, kWinoPlan); 0: none
     size_t total;
 };
-Blob blob_layout() {
+// flags without ND_FLAG_UNET_WINOGRAD: the blob of the default path.  With it, the Winograd forms follow behind: no offset moves
+Blob blob_layout(int flags = 0) {
     Blob b;
     size_t o = 0;
-    for (const ULayer &l : layers()) {
+    const auto &L = layers();
+    for (const ULayer &l : L) {
         b.off.push_back(o);
         o += l.kind == ND_CONV1 ? (size_t)(3 * l.cin + 3 + 3) / 4 * 4 : nd_packed_floats(l.kind, l.cin, l.cout);
     }
+    b.woff.assign(L.size(), 0);
+    if (flags & ND_FLAG_UNET_WINOGRAD)
+        for (size_t i = 0; i < L.size(); ++i) {
+            if (kWinoPlan[i] == UFORM_DIRECT) continue;
+            b.woff[i] = o;
+            o += ((kWinoPlan[i] == UFORM_WINO3P ? nd_wino_packed_floats(kWinoTile, L[i].cin, L[i].cout) : nd_w1d_packed_floats(kW1dTile, L[i].cin, L[i].cout)) + 63) / 64 * 64;
+        }
     b.total = o;
     return b;
 }
@@ -79,10 +108,14 @@ enum UB { XIN, I1, CAT4, Q1, D1, CAT3, Q2, D2, CAT2, Q3, D3, CAT1, Q4, D4, X5, U
 struct UPlan {
     QpBuf buf[NUB];
     float *split;
+    char *wino;          // three-pass V / M scratch (ND_FLAG_UNET_WINOGRAD; else none)
+    size_t wino_bytes;
     size_t bytes;
 };
-// B: images the buffers hold (their plane stride); count: images in use (a partial last launch of the frame loop)
-UPlan make_plan(int h, int w, int B, char *base, int count = 0) {
+size_t wino_scratch(const UPlan &p, int B);   // (behind kSteps)
+// B: images the buffers hold (their plane stride); count: images in use (a partial last launch of the frame loop); flags: with
+// ND_FLAG_UNET_WINOGRAD the Winograd scratch follows behind everything else
+UPlan make_plan(int h, int w, int B, char *base, int count = 0, int flags = 0) {
     UPlan p;
     size_t off = 0;
     int hs[5] = {h}, ws[5] = {w};
@@ -113,6 +146,9 @@ UPlan make_plan(int h, int w, int B, char *base, int count = 0) {
     add(U4A, 64, 0, 1); add(U4B, 64, 0, 0);
     p.split = (float *)(base + off);
     off += kSplitScratchBytes;
+    p.wino = base + off;
+    p.wino_bytes = (flags & ND_FLAG_UNET_WINOGRAD) ? wino_scratch(p, B) : 0;
+    off += (p.wino_bytes + 255) & ~(size_t)255;
     p.bytes = off;
     return p;
 }
@@ -131,6 +167,18 @@ const UStep kSteps[] = {
 };
 
 constexpr int kNumSteps = (int)(sizeof(kSteps) / sizeof(kSteps[0]));
+// V / M scratch of the largest three-pass layer at min(B, kWinoChunk) images (a larger launch runs in chunks: run_step)
+size_t wino_scratch(const UPlan &p, int B) {
+    size_t bytes = 0;
+    for (const UStep &st : kSteps) {
+        if (st.layer < 0 || kWinoPlan[st.layer] != UFORM_WINO3P) continue;
+        QpBuf v = p.buf[st.src];
+        v.B = B < kWinoChunk ? B : kWinoChunk;
+        const size_t need = nd_wino_scratch_bytes(kWinoTile, v, layers()[st.layer].cin, layers()[st.layer].cout);
+        if (need > bytes) bytes = need;
+    }
+    return bytes;
+}
 constexpr int kFirstDecoderStep = 14;   // up1.up: everything before it feeds a skip and stays whole
 
 // Regions of the decoder layers when only the centre [crop_h, H - crop_h) x [crop_w, W - crop_w) of the output is kept (the useful
@@ -183,6 +231,22 @@ int check(int h, int w, int batch, int dtype) {
     return ND_OK;
 }
 
+// the kernel family that runs step `st` of a call with `flags` on plan pl (roi: the step's region, null or rows 0: the whole layer)
+UForm step_form(const UStep &st, const UPlan &pl, int flags, const Roi *roi) {
+    if (st.layer < 0) return UFORM_POOL;
+    const ULayer &l = layers()[st.layer];
+    if (l.kind != ND_CONV3 || !(flags & ND_FLAG_UNET_WINOGRAD) || (flags & ND_FLAG_DIRECT_CONV)) return UFORM_DIRECT;
+    const QpBuf &in = pl.buf[st.src];
+    switch (kWinoPlan[st.layer]) {
+        case UFORM_WINO3P: return l.cin % 16 == 0 && l.cout % 4 == 0 ? UFORM_WINO3P : UFORM_DIRECT;   // (takes a region: unpooled F(6x6))
+        case UFORM_F43:
+            if (nd_f43_w2d(in, l.cout, false, flags)) return UFORM_F43;            // conv_w2d: any row width, takes a region
+            if (roi && roi->rows > 0) return UFORM_DIRECT;                         // conv_w1d takes none
+            return nd_w1d_fits(kW1dTile, in) ? UFORM_F43 : UFORM_DIRECT;
+        default: return UFORM_DIRECT;
+    }
+}
+
 // one step of the stack: the launch both nd_unet_forward and nd_unet_denoise_frame make.  roi: the step's region (null or rows 0: whole)
 ConvDesc step_desc(const UStep &st, const UPlan &pl, const float *blob, const Blob &bl, const Roi *roi, bool nosplit) {
     const ULayer &l = layers()[st.layer];
@@ -208,15 +272,42 @@ ConvDesc step_desc(const UStep &st, const UPlan &pl, const float *blob, const Bl
     }
     return d;
 }
-int run_step(const UStep &st, const UPlan &pl, const float *blob, const Blob &bl, const Roi *roi, bool nosplit, hipStream_t s) {
+// flags: nd_flags of the call (ND_FLAG_NO_SPLITK; ND_FLAG_UNET_WINOGRAD: the blob and the plan were made with it).  ev2, tiles
+// (profiling, nullable): the events and the tile count of a three-pass layer, as in nd_launch_conv_wino / nd_wino_launch_tiles
+int run_step(const UStep &st, const UPlan &pl, const float *blob, const Blob &bl, const Roi *roi, int flags, hipStream_t s,
+             hipEvent_t *ev2 = nullptr, long *tiles = nullptr) {
     if (st.layer < 0) return nd_launch_maxpool2(pl.buf[st.src], 0, st.dst_plane0, pl.buf[st.dst], s);
-    return nd_launch_conv(step_desc(st, pl, blob, bl, roi, nosplit), s);
+    ConvDesc d = step_desc(st, pl, blob, bl, roi, (flags & ND_FLAG_NO_SPLITK) != 0);
+    const UForm form = step_form(st, pl, flags, roi);
+    if (form == UFORM_DIRECT) return nd_launch_conv(d, s);
+    if (!bl.woff[st.layer]) ND_FAIL(ND_EINVAL, "UNet: no Winograd form of %s in the blob", layers()[st.layer].key.c_str());
+    d.wpk = blob + bl.woff[st.layer];
+    if (form == UFORM_F43) {
+        d.bias = d.wpk + nd_bias_offset(d.kind, d.cin, d.cout, ND_F32, kW1dTile);
+        return nd_launch_conv_f43(d, flags, s);
+    }
+    // three-pass form, kWinoChunk images per pass (views of the same buffers)
+    d.bias = nullptr;
+    d.tile_wino = (flags & ND_FLAG_TILE_WINO) != 0;
+    const int nimg = d.in.B;
+    for (int b0 = 0; b0 < nimg; b0 += kWinoChunk) {
+        ConvDesc c = d;
+        c.in.B = c.out.B = nimg - b0 < kWinoChunk ? nimg - b0 : kWinoChunk;
+        c.in.base = d.in.base + (size_t)b0 * d.in.Hb * d.in.Wb * 4;
+        c.out.base = d.out.base + (size_t)b0 * d.out.Hb * d.out.Wb * 4;
+        ND_TRY(nd_launch_conv_wino(kWinoTile, c, pl.wino, pl.wino_bytes, s, nimg <= kWinoChunk ? ev2 : nullptr));
+        if (tiles) *tiles += nd_wino_launch_tiles(kWinoTile, c);
+    }
+    return ND_OK;
 }
-// every restricted layer finds a workgroup shape for its region; else no layer is restricted (a whole-tile layer needs whole-tile
-// producers: the rois_supported rule of utnet_net.h)
-bool rois_fit(const UPlan &pl, const float *blob, const Blob &bl, const Roi *rois) {
+// every restricted layer finds a workgroup shape for its region in the form that will run it (the Winograd forms that step_form
+// returns for a restricted step take any region); else no layer is restricted (a whole-tile layer needs whole-tile producers: the
+// rois_supported rule of utnet_net.h)
+bool rois_fit(const UPlan &pl, const float *blob, const Blob &bl, const Roi *rois, int flags) {
     for (int i = kFirstDecoderStep; i < kNumSteps; ++i)
-        if (rois[i].rows > 0 && !nd_conv_roi_fits(step_desc(kSteps[i], pl, blob, bl, &rois[i], false))) return false;
+        if (rois[i].rows > 0 && step_form(kSteps[i], pl, flags, &rois[i]) == UFORM_DIRECT &&
+            !nd_conv_roi_fits(step_desc(kSteps[i], pl, blob, bl, &rois[i], false)))
+            return false;
     return true;
 }
 

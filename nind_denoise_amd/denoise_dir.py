@@ -32,7 +32,7 @@ def build_parser():
     parser.add_argument('--noisy_dir', type=str, help='directory of test dataset (or any directory containing images to be denoised), must end with [CROPSIZE]_[USEFULCROPSIZE]')
     parser.add_argument('--g_network', '--network', type=str, help='Generator network architecture (typically UtNet or UNet)')
     parser.add_argument('--model_path', '--model_fpath', help='Generator pretrained model path (.pt for dictionary)')
-    parser.add_argument('--model_parameters', default="", type=str, help='Model parameters with format "parameter1=value1,parameter2=value2" (UtNet: funit, activation, compute_dtype=f32|bf16|f16; see denoise_image --help)')
+    parser.add_argument('--model_parameters', default="", type=str, help='Model parameters with format "parameter1=value1,parameter2=value2" (UtNet: funit, activation, compute_dtype=f32|bf16|f16; UNet: find_noise, winograd=1; see denoise_image --help)')
     parser.add_argument('--result_dir', default='../../results/NIND/test', type=str, help='directory where results are saved. Can also be set to "make_subdirs" to make a denoised/<model_directory_name> subdirectory')
     parser.add_argument('--no_scoring', action='store_true', help='Skip the obsolete res.txt scoring pass')
     parser.add_argument('--gen_score', action='store_true', help='Run the res.txt scoring pass (loss.gen_score: pytorch_ssim SSIM and MSE of every output against its set\'s base ISO) at the end')

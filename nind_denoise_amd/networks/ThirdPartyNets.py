@@ -7,6 +7,11 @@ The torch layers below are parameter containers only; ``forward`` never calls th
 Eval mode is differentiable: an input that requires a gradient gets one, and so do the parameters that require one (fine-tuning
 with frozen BatchNorm statistics) -- ``nd_unet_grad_forward`` / ``nd_unet_grad_backward``.  Train mode (batch statistics) raises
 here; the training step on batch statistics is ``nind_denoise_amd.train.UNetTrainer``, which drives this module's tensors.
+
+``UNet(winograd=True)`` (``--model_parameters winograd=1``) runs the 3x3 layers of the inference paths -- ``forward`` without a
+gradient and the frame loop -- in Winograd forms (ND_FLAG_UNET_WINOGRAD: three-pass F(6x6,3x3) on the wide layers, fused F(4,3) on
+the narrow ones).  It is inference only: the autograd halves (``forward`` on an input that requires a gradient, ``frame_grad``) and
+``UNetTrainer`` ignore it and run the direct kernels, so their bits do not depend on it.
 """
 import ctypes
 
@@ -38,7 +43,7 @@ class UNet(nn.Module):
     useful_only = True      # False: ND_FLAG_FULL_TILES (every decoder layer on the whole tile)
     pack_on_device = True   # False: fold BatchNorm and pack on the host (nd_unet_pack_weights), then upload
 
-    def __init__(self, n_channels=3, n_classes=3, funit=64, find_noise=False, compute_dtype='f32'):
+    def __init__(self, n_channels=3, n_classes=3, funit=64, find_noise=False, compute_dtype='f32', winograd=False):
         super().__init__()
         if canonical_compute_dtype(compute_dtype) != 'f32':
             raise NotImplementedError(f"UNet: compute_dtype={compute_dtype!r}: 16-bit storage exists for UtNet only "
@@ -52,11 +57,21 @@ class UNet(nn.Module):
             self.add_module(f"up{n}", _Box(up=nn.ConvTranspose2d(ci // 2, ci // 2, 2, stride=2), conv=_double_conv(ci, co)))
         self.outc = _Box(conv=nn.Conv2d(64, 3, 1))
         self.find_noise = find_noise in (True, "True", "true", "1")
+        if winograd in (True, "True", "true", "1"):
+            self.winograd = True
+        elif winograd in (False, "False", "false", "0", None, ""):
+            self.winograd = False
+        else:
+            raise ValueError(f"UNet: winograd={winograd!r}: expected True / 'True' / 'true' / '1' or a false spelling")
         self._packed = None
         self._workspaces = {}
 
+    @property
+    def _wino_flag(self):
+        return _lib.FLAG_UNET_WINOGRAD if self.winograd else 0
+
     def _weights_key(self, device):
-        return (str(device),) + tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
+        return (str(device), self.winograd, self.pack_on_device) + tuple((t.data_ptr(), t._version) for t in list(self.parameters()) + list(self.buffers()))
 
     def packed_weights(self, device):
         key = self._weights_key(device)
@@ -71,27 +86,28 @@ class UNet(nn.Module):
             t = sd[lib.nd_unet_tensor_name(i).decode()].detach().to(device=where, dtype=torch.float32).contiguous()
             keep.append(t)
             ptrs[i] = t.data_ptr()
-        nbytes = lib.nd_unet_packed_bytes(_lib.ND_F32)
+        nbytes = lib.nd_unet_packed_bytes_flags(_lib.ND_F32, self._wino_flag)
         if self.pack_on_device:
             dev_blob = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
             with torch.cuda.device(device):
-                _lib.check(lib.nd_unet_pack_weights_device(_lib.ND_F32, ptrs, n, dev_blob.data_ptr(), nbytes, _lib.stream_ptr(device)),
-                           "nd_unet_pack_weights_device")
+                _lib.check(lib.nd_unet_pack_weights_device_flags(_lib.ND_F32, self._wino_flag, ptrs, n, dev_blob.data_ptr(), nbytes,
+                                                                 _lib.stream_ptr(device)), "nd_unet_pack_weights_device_flags")
                 torch.cuda.current_stream(device).synchronize()     # `keep` may be freed after this
         else:
             blob = torch.empty(nbytes // 4, dtype=torch.float32)
-            _lib.check(lib.nd_unet_pack_weights(_lib.ND_F32, ptrs, n, blob.data_ptr(), nbytes), "nd_unet_pack_weights")
+            _lib.check(lib.nd_unet_pack_weights_flags(_lib.ND_F32, self._wino_flag, ptrs, n, blob.data_ptr(), nbytes),
+                       "nd_unet_pack_weights_flags")
             dev_blob = blob.to(device)
         self._packed = (key, dev_blob)
         return dev_blob
 
     @property
     def flags(self):
-        return (0 if self.split_k else _lib.FLAG_NO_SPLITK) | (0 if self.useful_only else _lib.FLAG_FULL_TILES)
+        return (0 if self.split_k else _lib.FLAG_NO_SPLITK) | (0 if self.useful_only else _lib.FLAG_FULL_TILES) | self._wino_flag
 
     @property
     def grad_flags(self):
-        """flags of nd_unet_grad_forward / nd_unet_grad_backward"""
+        """flags of nd_unet_grad_forward / nd_unet_grad_backward (``winograd`` is inference only: not among them)"""
         return (0 if self.split_k else _lib.FLAG_NO_SPLITK) | (_lib.FLAG_FIND_NOISE if self.find_noise else 0)
 
     # ------------------------------------------------------------------ under autograd in eval mode (NetFunction): BatchNorm fold +
@@ -122,12 +138,12 @@ class UNet(nn.Module):
                    "nd_unet_grad_backward")
 
     def workspace(self, h, w, batch, device):
-        key = (str(device), h, w, batch)
+        key = (str(device), h, w, batch, self.winograd)
         ws = self._workspaces.get(key)
         if ws is None:
             lib = _lib.load()
-            ws = _lib.make_workspace(lib.nd_unet_workspace_bytes, lib.nd_unet_workspace_init, (h, w, batch, _lib.ND_F32), device, "UNet",
-                                     drop=self._workspaces.clear)
+            ws = _lib.make_workspace(lib.nd_unet_workspace_bytes_flags, lib.nd_unet_workspace_init_flags,
+                                     (h, w, batch, _lib.ND_F32, self._wino_flag), device, "UNet", drop=self._workspaces.clear)
             self._workspaces[key] = ws
         return ws
 
@@ -151,6 +167,6 @@ class UNet(nn.Module):
             blob = self.packed_weights(x.device)
             ws = self.workspace(h, w, b, x.device)
             y = torch.empty_like(x)
-            _lib.check(lib.nd_unet_forward(_lib.ND_F32, blob.data_ptr(), x.data_ptr(), y.data_ptr(), b, h, w, ws.data_ptr(),
-                                           ws.numel(), _lib.stream_ptr(x.device)), "nd_unet_forward")
+            _lib.check(lib.nd_unet_forward_flags(_lib.ND_F32, self._wino_flag, blob.data_ptr(), x.data_ptr(), y.data_ptr(), b, h, w,
+                                                 ws.data_ptr(), ws.numel(), _lib.stream_ptr(x.device)), "nd_unet_forward_flags")
         return x - y if self.find_noise else y
